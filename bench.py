@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- tracer-DOF-steps/s of the prim_run tracer path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one prim_step of the reference's time loop (prescribed-field refresh + Prim_Advec_Tracers_remap_rk2: three
@@ -11,6 +11,8 @@ sharded over the N GPUs along the reference's space-filling curve (strong scalin
 synthetic (analytic DCMIP) data; the DSS halo is exchanged inside the library with RCCL send/recv.
 Without WORLD_SIZE in the environment and N > 1 this script starts the N rank processes itself (fresh children through
 torch.distributed.run; this parent never touches a GPU) and exits with their status.  Prints ONE JSON line on rank 0.
+--dump-outputs DIR: after the timed steps, the Qdp those steps left (a fixed seeded sample of whole elements, float64) goes to
+DIR/qdp.npy and the global ids of its elements to DIR/qdp_elements.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -203,6 +205,61 @@ def cpu_baseline(qsize):
                 why_sample="oracle/_ref/ref_harness (the reference itself) is not on this box; same ne30 sample as for kind=reference")
 
 
+DUMP_BYTES = 48 << 20     # --dump-outputs: at most this much Qdp (whole elements), well inside the 64 MB the files may take
+DUMP_SEED = 20240611
+
+
+def dump_elements(nelem_total, qsize):
+    """the global element ids --dump-outputs writes: all of them when their Qdp fits in DUMP_BYTES, else a fixed seeded sample
+    (sorted).  The sample comes from splitmix64 in plain integers, not from a library's generator, so it depends only on the
+    workload: any two builds run with the same arguments write the same elements."""
+    import numpy as np
+    k = max(1, min(nelem_total, DUMP_BYTES // (qsize * 72 * 16 * 8)))
+    if k == nelem_total:
+        return np.arange(nelem_total)
+    m = (1 << 64) - 1
+    state, ids = DUMP_SEED, set()
+    while len(ids) < k:
+        state = (state + 0x9E3779B97F4A7C15) & m
+        z = ((state ^ (state >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        ids.add((z ^ (z >> 31)) % nelem_total)
+    return np.array(sorted(ids), dtype=np.int64)
+
+
+def dump_outputs(run, tl, nelem_total, torch_mod, dist_mod, rank, world, out_dir):
+    """what the timed path leaves for its caller: Qdp(:,:,:,:,tl) after the last timed step, for the elements of dump_elements()
+    (each rank gathers those it owns on its device; rank 0 writes them in global-id order).  Files: qdp.npy (k, qsize, 72, 4, 4)
+    float64 and qdp_elements.npy (k,) float64, the global element ids of its rows."""
+    import numpy as np
+    want = dump_elements(nelem_total, run.qsize)
+    mine = np.asarray(run.mine)
+    rows = np.nonzero(np.isin(mine, want))[0]                     # local indices of the wanted elements this rank holds
+    per_elem = run.qsize * 72 * 16
+    ptr, nbytes = run.hip.device_ptr("qdp%d" % tl)
+    assert mine.size * per_elem * 8 <= nbytes, (mine.size, per_elem, nbytes)
+    run.hip.synchronize()
+    iface = {"shape": (mine.size, per_elem), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
+    holder = type("DevArr", (), {"__cuda_array_interface__": iface})()
+    dev = "cuda:%d" % run.hip_device
+    q = torch_mod.as_tensor(holder, device=dev)
+    part = q.index_select(0, torch_mod.as_tensor(rows, dtype=torch_mod.int64, device=dev)).cpu().numpy()
+    parts = [(mine[rows], part)]
+    if world > 1:
+        parts = [None] * world
+        dist_mod.all_gather_object(parts, (mine[rows], part))
+    if rank != 0:
+        return None
+    ids = np.concatenate([p[0] for p in parts]); vals = np.concatenate([p[1] for p in parts])
+    order = np.argsort(ids)
+    assert np.array_equal(ids[order], want), "dumped elements do not cover the sample"
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"qdp": vals[order].reshape(-1, run.qsize, 72, 4, 4), "qdp_elements": ids[order].astype(np.float64)}
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in files.items()}
+
+
 def self_launch(a):
     """start the N rank processes (fresh children; nothing in this process has touched a GPU) and relay their output"""
     import socket
@@ -221,7 +278,11 @@ def main():
     ap.add_argument("--ne", type=int, default=int(os.environ.get("TSE_BENCH_NE", "120")))
     ap.add_argument("--qsize", type=int, default=int(os.environ.get("TSE_BENCH_QSIZE", "35")))
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the final Qdp of a fixed seeded sample of elements as DIR/*.npy (float64)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(self_launch(a))
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -288,6 +349,7 @@ def main():
     run.run(a.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    assert run.nstep == a.warmup + a.steps, (run.nstep, a.warmup, a.steps)   # ms_per_step divides by exactly these steps
     np1_final = 2 if ((a.warmup + a.steps) % 2 == 1) else 1     # TimeLevel_Qdp: the last step wrote 3 - n0
     checksum = run.state_checksum(np1_final, torch)
     if world > 1:
@@ -298,6 +360,9 @@ def main():
         cs = torch.tensor([checksum], dtype=torch.int64, device=dev)
         dist.all_reduce(cs, op=dist.ReduceOp.SUM)
         checksum = int(cs.item())
+    dumped = None
+    if a.dump_outputs:   # (after the timed region: not part of ms_per_step; before the watchdog ends: it gathers over the ranks)
+        dumped = dump_outputs(run, np1_final, 6 * a.ne * a.ne, torch, dist, rank, world, a.dump_outputs)
     if watchdog:
         watchdog.cancel()
     ktimes = {k: run.hip.kernel_time(k) for k in ("advance0", "advance1", "advance2", "lap", "dss", "minmax", "remap", "level", "dcmip", "avg")}
@@ -361,6 +426,8 @@ def main():
             # (same steps/warmup) iff the result is bit-for-bit independent of the partition
             "state_checksum": checksum & 0xFFFFFFFFFFFFFFFF,
         }
+        if dumped:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.qsize)
         print(json.dumps(out), flush=True)

@@ -1,6 +1,6 @@
 """-m gpu: the drop-in boundary exercised from the reference's own language.
 
-tests/fortran_dropin/_build/hip_harness (tests/fortran_dropin/Makefile) is the reference's UNMODIFIED prim_advection_mod.F90 compiled with
+oracle/_ref/dropin/hip_harness (tests/fortran_dropin/Makefile) is the reference's UNMODIFIED prim_advection_mod.F90 compiled with
 -DUSE_CUDA_FORTRAN=1 and linked against transport_se_amd/fortran/cuda_mod_hip.F90 (a Fortran module named `cuda_mod`
 bound to libtransport_se_hip.so with ISO_C_BINDING): the reference's own `call euler_step_cuda(...)`,
 `call qdp_time_avg_cuda(...)`, `call vertical_remap_cuda(...)` hooks run on the MI355X.  Its output must equal the
@@ -18,7 +18,7 @@ import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "fortran_dropin", "_build", "hip_harness")
+HARNESS = os.path.join(ROOT, "oracle", "_ref", "dropin", "hip_harness")
 MPIEXEC = "/opt/conda/bin/mpiexec"
 from conftest import record_margin  # noqa: E402
 # Tolerance against the reference's own output: the per-step bound TOL_STEP = 5e-13 of the field maximum of test_gpu_parity.py
@@ -106,8 +106,8 @@ def test_rccl_mode_falls_back_to_the_mpi_exchange_when_the_communicator_cannot_b
     assert np.abs(q - g["qdp_step6"]).max() / np.abs(g["qdp_step6"]).max() < TOL_DROPIN["qdp_step6"]
 
 
-HARNESS_OMP = os.path.join(ROOT, "tests", "fortran_dropin", "_build", "hip_harness_omp")
-HARNESS_Q200 = os.path.join(ROOT, "tests", "fortran_dropin", "_build", "hip_harness_q200")
+HARNESS_OMP = os.path.join(ROOT, "oracle", "_ref", "dropin", "hip_harness_omp")
+HARNESS_Q200 = os.path.join(ROOT, "oracle", "_ref", "dropin", "hip_harness_q200")
 
 
 @pytest.mark.skipif(not (os.path.exists(HARNESS_OMP) and os.path.exists(MPIEXEC)), reason="OpenMP drop-in harness not built")

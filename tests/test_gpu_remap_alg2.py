@@ -17,7 +17,7 @@ from transport_se_amd import HipMod
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "fortran_dropin", "_build", "hip_harness")
+HARNESS = os.path.join(ROOT, "oracle", "_ref", "dropin", "hip_harness")
 MPIEXEC = "/opt/conda/bin/mpiexec"
 
 
