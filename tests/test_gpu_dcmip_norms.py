@@ -109,7 +109,7 @@ def test_ne120_norms_match_readme(name):
         os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
         rec = dict(kernel_source_hash=_lib.source_hash(), config="ne120/72L/qsize=4 DCMIP1-1, 12 days = 13824 tracer steps of 75 s, nu_q=1e13, rsplit=3 "
                    "(test/run_ne120_tests.sh), 1 MI355X, device-resident prim_run loop; norms as dcmip1-1_error_norm_ng.ncl:39-77",
-                   readme_line="README:152", wall_s=wall, ms_per_step=1e3 * wall / ref["nsteps"], patch_shape=os.environ.get("TSE_PATCH_SHAPE", "default"),
+                   readme_line="README:152", wall_s=wall, ms_per_step=1e3 * wall / ref["nsteps"],
                    **{k: float(got[k]) for k in ("L1", "L2", "Linf", "q_max", "q_min")})
         json.dump(rec, open(os.path.join(root, "gpurun_out", "l2_dcmip11_ne120.json"), "w"), indent=1)
     for k in ("L1", "L2", "Linf", "q_max"):

@@ -73,8 +73,8 @@ def _stale(so):
 
 def build(force=False, verbose=False, out=None, flags=(), hooks=True):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Builds the product library and, with hooks=True, its twin with
-    -DTSE_AB_HOOKS (libtransport_se_hip_hooks.so: the A/B switches, the fault injection the tests use, the tse_debug_* entry
-    points -- none of which the product library contains); all translation units compile side by side.
+    -DTSE_AB_HOOKS (libtransport_se_hip_hooks.so: the A/B switches and the fault injection the tests use -- none of which the
+    product library contains); all translation units compile side by side.
     out/flags: one A/B variant of the same sources instead (tools/ab_build.sh; always with the hooks)."""
     import tempfile
     if out is not None:

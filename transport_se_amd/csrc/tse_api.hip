@@ -27,7 +27,7 @@
 using namespace tse;
 
 namespace tse {   // tse_stage3.hip: k_advance<2,3> lives in a translation unit of its own (another scheduler strategy)
-void launch_advance23(int psz, unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
+void launch_advance23(unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
                       const double* B, const double* lapT, double* C, const double* vn0, const double* dp, const double* divdp,
                       const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga);
 }
@@ -37,8 +37,8 @@ static bool dss_on_read() { const char* e = getenv("TSE_DSS_ON_READ"); return !(
 // TSE_REMAP_FUSED=0: inside tse_prim_run_subcycle the last step of a cycle runs its own final DSS pass and the remap works in place
 static bool remap_fused() { const char* e = getenv("TSE_REMAP_FUSED"); return !(e && e[0] == '0'); }
 
-// Experiment and fault-injection switches (TSE_AB_*: A/B variants, some of them WRONG on purpose; TSE_TEST_*: failures on request for the
-// tests; the tse_debug_* entry points at the end of this file) exist only in a build with -DTSE_AB_HOOKS
+// Experiment and fault-injection switches (TSE_AB_*: A/B variants; TSE_TEST_*: failures on request for the tests) exist only in a build
+// with -DTSE_AB_HOOKS
 // (libtransport_se_hip_hooks.so: tools/ab_build.sh, _lib.build_hooks()); the product library does not read them at all.
 #ifdef TSE_AB_HOOKS
 static const char* hook_env(const char* name) { return getenv(name); }
@@ -56,17 +56,14 @@ static int fail(const char* fmt, ...) {
 
 struct KTimer { double ms = 0; long n = 0; };
 
-// the tables of one patch tiling (tse_kernels.h: Patch<PSZ>): built for the 4 x 4 storage tiling and for every wider block
-// shape some kernel was given
+// the tables of the patch tiling (tse_kernels.h: Patch)
 struct PatchSet {
-  int psz = 0, npatch = 0, np_bnd = 0, np_int = 0;
+  int npatch = 0, np_bnd = 0, np_int = 0;
   int *pslots = nullptr, *plist_bnd = nullptr, *plist_int = nullptr, *pering = nullptr;
   unsigned* pring = nullptr;
   unsigned short* plds = nullptr;
   unsigned char* pnb = nullptr;
 };
-// the DSS-on-read kernels of the whole-step path, as indices of tse_ctx::kshape
-enum { K_ADV1 = 0, K_LAP = 1, K_ADV2 = 2, K_DSS = 3 };
 
 struct tse_ctx {
   int nelemd = 0, qsize = 0, device = 0, rsplit = 3;
@@ -85,8 +82,6 @@ struct tse_ctx {
   double *T = nullptr, *B = nullptr, *C = nullptr;   // C: third scratch field (stage-3 output of the whole-step path)
   int place_n = 0, place_sel[5] = {0, 1, 2, 3, 4};   // field placement (place_fields): chunks tried, which try became T, Qdp1, Qdp2, B, C
   double place_bw[32] = {0};                         // their streaming-write GB/s, in the order tried
-  double* qorig[2] = {nullptr, nullptr};   // developer experiment: the tracer state's own allocations while it lives in pool chunks
-  std::vector<double*> pool;   // developer experiment (tools/placement_probe.py): scratch-sized allocations T, B, C can be re-assigned to
   double *vn0 = nullptr, *dp = nullptr, *divdp = nullptr, *divdp_proj = nullptr, *eta = nullptr, *omega_p = nullptr;
   double *dp3d = nullptr, *ps_v = nullptr, *lvl_tmp = nullptr;
   double *qmin = nullptr, *qmax = nullptr, *qmin2 = nullptr, *qmax2 = nullptr;
@@ -119,9 +114,7 @@ struct tse_ctx {
   // element patches of the scratch layout (tse_kernels.h): slot = patch*16 + position
   int nslots = 0;
   int* slot_of = nullptr;
-  PatchSet pset[3];                        // patch tilings of 16, 24, 32 slots (4x4, 6x4, 8x4 elements); [0] is also the storage order
-  int kshape[4] = {16, 16, 16, 16};        // block shape of k_advance<1,1>, k_lap1<1>, k_advance<2,3>, k_dss_patch (patch_shape)
-  const PatchSet& set_of(int k) const { return pset[kshape[k] == 32 ? 2 : kshape[k] == 24 ? 1 : 0]; }
+  PatchSet pset;                           // the patch tiling of the DSS-on-read kernels (4 x 4 elements), also the storage order
   unsigned long long* pperm = nullptr;   // point order inside every slot of the scratch layout
   unsigned char* pexp = nullptr;         // [slot] lines of the slot that hold points read from outside its patch (k_lap1<1> stores only those)
   unsigned* etab = nullptr;              // [e][16][3] entry (within a chunk) of the DSS contributions of a point: the remap's DSS on read (RemapFuse)
@@ -149,10 +142,10 @@ struct tse_ctx {
   Scr scr() const { return Scr{tps, cse}; }
   unsigned zero0() const { return (unsigned)nslots * 16; }          // entry index of the zero slot within a chunk
   unsigned halo0() const { return (unsigned)(nslots + 1) * 16; }    // entry index of halo column 0
-  GatherArgs gargs(const PatchSet& P, const int* order_, int nwork_, const int* plist_, int npwork_, const double* var_in = nullptr, int var_in_lev = 0,
+  GatherArgs gargs(const int* order_, int nwork_, const int* plist_, int npwork_, const double* var_in = nullptr, int var_in_lev = 0,
                    double* var_out = nullptr, int var_out_lev = 0) const {
-    return GatherArgs{scr(), slot_of, order_, nwork_, rspheremp, P.pslots, P.pring, P.plds, plist_, npwork_, var_in, var_in_lev, var_out, var_out_lev, nullptr,
-                      P.pering, P.pnb, pperm, nullptr};
+    return GatherArgs{scr(), slot_of, order_, nwork_, rspheremp, pset.pslots, pset.pring, pset.plds, plist_, npwork_, var_in, var_in_lev, var_out, var_out_lev,
+                      nullptr, pset.pering, pset.pnb, pperm, nullptr};
   }
   int mm_m() const { return mm_qpad(qsize) * NLEV; }   // entries per element of the bounds arrays (tse_kernels.h: mm_idx)
   size_t lev() const { return (size_t)nelemd * NLEV * 16; }
@@ -232,11 +225,11 @@ __global__ __launch_bounds__(256) void k_probe_copy(size_t n, const double2* __r
 // pad writes at another rate; in short bursts all chunks are alike), it is fixed for the life of the allocation -- and the kernels
 // follow it:
 //  * with a 5.5 TB/s chunk as T (written by stages 1 and 3a) a tracer step takes 2-3 ms longer than with any faster one (k_lap1 14.8
-//    instead of 13.4-13.7 ms, k_advance<0,0> 12.6 instead of 12.0; tools/placement_probe.py timed all 60-120 assignments of three out
-//    of five or six chunks with the real kernels);
+//    instead of 13.4-13.7 ms, k_advance<0,0> 12.6 instead of 12.0; a probe timed all 60-120 assignments of three out of five or six
+//    chunks with the real kernels);
 //  * k_dss_patch, which writes Qdp(np1), takes 16.3-17.1 ms into a chunk that streams at 5.9 TB/s or more and 18.5-19.3 ms into one
-//    at 5.5-5.7 (tools/dss_probe.py); with both time levels in one allocation it alternated between the two step by step, the
-//    first allocation of a process being a slow one nearly always (tools/step_probe.py).
+//    at 5.5-5.7; with both time levels in one allocation it alternated between the two step by step, the first allocation of a
+//    process being a slow one nearly always.
 // This was the unexplained "run-to-run modes" of rounds 1 and 2.  So tse_init places the five fields by trial: it allocates field-sized
 // chunks (up to 8 held at a time, memory allowing) and times a streaming write into each (3 x 5 ms); as long as fewer than three of the
 // held chunks reach TSE_PLACEMENT_GOOD (6000 GB/s) it frees the slowest, allocates a 256 MB pad and tries again -- at most
@@ -308,16 +301,6 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
   c->nelemd = a->nelemd; c->qsize = a->qsize; c->nu_q = a->nu_q; c->ps0 = a->ps0; c->rsplit = a->rsplit;
   c->exchange = a->exchange; c->exchange_user = a->exchange_user;
   c->remap_alg2 = a->vert_remap_q_alg == 2;
-  {
-    // block shapes of the DSS-on-read kernels (measured defaults); TSE_PATCH_SHAPE="adv1,lap,adv2,dss" overrides them (A/B)
-    const char* e = getenv("TSE_PATCH_SHAPE");
-    int v[4] = {c->kshape[0], c->kshape[1], c->kshape[2], c->kshape[3]};
-    if (e && sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) != 4) return fail("tse_init: TSE_PATCH_SHAPE=\"%s\" (expected four of 16|24|32)", e);
-    for (int k = 0; k < 4; k++) {
-      if (v[k] != 16 && v[k] != 24 && v[k] != 32) return fail("tse_init: patch shape %d (16, 24 or 32 element slots)", v[k]);
-      c->kshape[k] = v[k];
-    }
-  }
   memcpy(c->D.d, a->Dvv, sizeof c->D.d);
   { std::vector<double> dv(a->Dvv, a->Dvv + 16); if (upload(&c->dvv_d, dv)) return 1; }
   HIPCHK(hipStreamCreate(&c->stream));   // blocking w.r.t. the legacy default stream: see the note above split_stage
@@ -439,7 +422,7 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
     // earlier instead of a whole row of the face earlier.  Pure scheduling: results do not depend on it.
     const int S8 = (n + 7) / 8;
     std::vector<int> order(n);
-    const int W = getenv("TSE_DSS_STRIP") ? atoi(getenv("TSE_DSS_STRIP")) : 8;
+    constexpr int W = 8;
     for (int x = 0; x < 8; x++) {
       const int lo = x * S8, hi = std::min(n, lo + S8);
       if (lo >= hi) continue;
@@ -458,7 +441,6 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
         }
       }
     }
-    if (W <= 0) for (int e = 0; e < n; e++) order[e] = e;
     if (upload(&c->order, order)) return 1;
   }
   {
@@ -475,12 +457,11 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
   }
 
   {
-    // Patches: groups of neighbouring elements -- rows of up to PW elements joined by their east links, up to 4 rows joined by
+    // Patches: groups of neighbouring elements -- rows of up to 4 elements joined by their east links, up to 4 rows joined by
     // the north link of each row's first element (no coordinates are needed and a patch may take any shape next to a cube seam or
     // a rank boundary).  A DSS-on-read block owns one patch: what its slabs need from inside the patch travels through LDS, only
     // the patch's halo ring comes from global memory.  Elements are taken in host order, so the patches of a full face tile it
-    // from its south-west corner.  The 4 x 4 tiling (set 0) is also the STORAGE order of the scratch fields (slot = patch * 16 +
-    // position); the wider shapes (6 x 4, 8 x 4: sets 1, 2) are built only for the kernels that were given them (patch_shape).
+    // from its south-west corner.  The tiling is also the STORAGE order of the scratch fields (slot = patch * 16 + position).
     auto ring_key = [](const int2& t) { return t.x >= 0 ? (long)t.x * 16 + t.y : -(long)(-(t.x + 2)) - 1; };
     std::vector<char> isb(n, 0);   // elements that touch another rank
     for (const int2& q : send_src) isb[q.x] = 1;
@@ -490,9 +471,10 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
     // step (12.6 -> 13.0 ms in the loopback rehearsal, profiles/r03_ab_boundary_bands.txt), and the first launch only matters
     // where an exchange outlasts the interior launch -- 0.7 ms of xGMI transfer against 1.3-2.2 ms of interior work here.
     const bool strips = getenv("TSE_BOUNDARY_STRIPS") && atoi(getenv("TSE_BOUNDARY_STRIPS")) != 0;
-    auto build = [&](int psz, std::vector<std::vector<int>>& patches, std::vector<int>& pid) {
-      const int pw = psz / 4, nrmax = patch_nrmax(psz);
-      pid.assign(n, -1);
+    constexpr int nrmax = Patch::NRMAX;
+    std::vector<std::vector<int>> patches;
+    std::vector<int> pid(n, -1);
+    {
       auto ring_size = [&](const std::vector<int>& cand, int me) {
         std::vector<long> refs;
         for (int e : cand)
@@ -536,7 +518,7 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
           std::vector<int> cand{seed};
           pid[seed] = me;
           bool grew = true;
-          while (grew && (int)cand.size() < psz / 2) {   // the chain of boundary elements
+          while (grew && (int)cand.size() < PS / 2) {    // the chain of boundary elements
             grew = false;
             for (int back = (int)cand.size() - 1; back >= 0 && !grew; back--)
               for (int d = 0; d < 8 && !grew; d++) {
@@ -545,7 +527,7 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
               }
           }
           grew = true;
-          while (grew && (int)cand.size() < psz) {       // the elements behind it
+          while (grew && (int)cand.size() < PS) {        // the elements behind it
             grew = false;
             for (size_t i = 0; i < cand.size() && !grew; i++)
               for (int d = 0; d < 4 && !grew; d++) {
@@ -560,7 +542,7 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
         if (pid[seed] >= 0) continue;
         const int me = (int)patches.size();
         // fewer rows, then narrower rows, until the halo ring and the element ring fit the tables (one element always does)
-        for (int maxrows = 4, width = pw;; ) {
+        for (int maxrows = 4, width = 4;; ) {
           std::vector<int> cand;
           int rowstart = seed;
           for (int r = 0; r < maxrows && rowstart >= 0 && pid[rowstart] < 0; r++) {
@@ -574,39 +556,32 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
           if (maxrows > 1) maxrows--; else width--;
         }
       }
-    };
-    std::vector<std::vector<int>> patches[3];
-    std::vector<int> pid[3];
-    static const int shape_psz[3] = {16, 24, 32};
-    bool want[3] = {true, false, false};
-    for (int k = 0; k < 4; k++) for (int si = 0; si < 3; si++) if (c->kshape[k] == shape_psz[si]) want[si] = true;
-    for (int si = 0; si < 3; si++) if (want[si]) build(shape_psz[si], patches[si], pid[si]);
-    // ---- storage: the 4 x 4 tiling
-    c->nslots = (int)patches[0].size() * PS;
+    }
+    // ---- storage
+    c->nslots = (int)patches.size() * PS;
     std::vector<int> slot_of(n, -1);
-    for (size_t pi = 0; pi < patches[0].size(); pi++)
-      for (size_t i = 0; i < patches[0][pi].size(); i++) slot_of[patches[0][pi][i]] = (int)pi * PS + (int)i;
+    for (size_t pi = 0; pi < patches.size(); pi++)
+      for (size_t i = 0; i < patches[pi].size(); i++) slot_of[patches[pi][i]] = (int)pi * PS + (int)i;
     c->cse = (unsigned)(c->nslots + 1) * 16 + (unsigned)std::max(0, c->ncol_recv);
     // Point order inside every slot (tse_kernels.h: ppos).  An edge of an element is READ FROM OUTSIDE when the neighbour across it
-    // belongs to another patch of some tiling in use (that patch's halo ring) or to another rank (the pack kernel); such an edge
-    // gets a 128-byte line of its own, in the order S, N, W, E.  An edge that shares a corner point with an edge placed before
-    // it (the corner elements of a patch export two edges) brings only its remaining points into a fresh line: it then costs
-    // its reader two lines.  The points nobody reads from outside fill what is left.
-    // TSE_AB_FIXED_PERM=1: the former fixed perimeter-first order (A/B).
+    // belongs to another patch (that patch's halo ring) or to another rank (the pack kernel); such an edge gets a 128-byte line of
+    // its own, in the order S, N, W, E.  An edge that shares a corner point with an edge placed before it (the corner elements of a
+    // patch export two edges) brings only its remaining points into a fresh line: it then costs its reader two lines.  The points
+    // nobody reads from outside fill what is left.  Slots without an element keep round 2's fixed perimeter-first order (the A/B
+    // of that order for every slot: profiles/r03_ab_halo_ring_bound.txt).
     std::vector<unsigned long long> pperm((size_t)c->nslots, 0x67895FEA4DCB3210ULL);
-    // lines of a slot that k_lap1<1> must store: 1 + the last line that holds a point some patch's halo ring (of any tiling in use) or a
+    // lines of a slot that k_lap1<1> must store: 1 + the last line that holds a point some patch's halo ring or a
     // send column reads -- taken from those tables themselves below, so that it covers corner-only readers and irregular patches too;
     // the per-slot order packs the exported edges into the first lines, so this is a quarter of the field on average
     std::vector<unsigned char> pexp((size_t)c->nslots, 0);
-    if (!(hook_env("TSE_AB_FIXED_PERM") && atoi(hook_env("TSE_AB_FIXED_PERM")))) {
+    {
       static const int edge_dir[4] = {2, 3, 0, 1};   // S, N, W, E as direction indices (west, east, south, north = 0..3)
       for (int e = 0; e < n; e++) {
         int pos_of[16]; bool placed[16] = {false};
         int line = 0;
         for (int t = 0; t < 4; t++) {
           const int d = edge_dir[t], nb = nbr[e * 8 + d];
-          bool outside = nb <= -2;
-          for (int si = 0; si < 3; si++) if (want[si] && nb >= 0 && pid[si][nb] != pid[si][e]) outside = true;
+          const bool outside = nb <= -2 || (nb >= 0 && pid[nb] != pid[e]);
           if (!outside) continue;
           int cnt = 0;
           for (int k = 0; k < 4; k++) { const int pt = edge_point(d, k); if (!placed[pt]) { placed[pt] = true; pos_of[pt] = line * 4 + cnt++; } }
@@ -621,20 +596,17 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
         pperm[slot_of[e]] = w;
       }
     }
-    const bool ab_noring = hook_env("TSE_AB_NORING") && atoi(hook_env("TSE_AB_NORING"));   // A/B: no halo-ring loads at all (WRONG results; bounds what the ring costs)
-    // ---- the tables of every tiling in use
-    for (int si = 0; si < 3; si++) {
-      if (!want[si]) continue;
-      PatchSet& P = c->pset[si];
-      const int psz = shape_psz[si], nrmax = patch_nrmax(psz);
-      const std::vector<std::vector<int>>& pt = patches[si];
-      P.psz = psz; P.npatch = (int)pt.size();
-      const size_t nts = (size_t)P.npatch * psz;   // table slots
+    // ---- the tables of the kernels
+    {
+      PatchSet& P = c->pset;
+      const std::vector<std::vector<int>>& pt = patches;
+      P.npatch = (int)pt.size();
+      const size_t nts = (size_t)P.npatch * PS;   // table slots
       std::vector<int> pslots(nts, -1), tslot_of(n, -1);
       for (int pi = 0; pi < P.npatch; pi++)
-        for (size_t i = 0; i < pt[pi].size(); i++) { pslots[(size_t)pi * psz + i] = pt[pi][i]; tslot_of[pt[pi][i]] = pi * psz + (int)i; }
+        for (size_t i = 0; i < pt[pi].size(); i++) { pslots[(size_t)pi * PS + i] = pt[pi][i]; tslot_of[pt[pi][i]] = pi * PS + (int)i; }
       std::vector<unsigned> pring((size_t)P.npatch * nrmax, c->zero0());
-      const int lds_ring = psz * 20, lds_zero = lds_ring + nrmax;   // Patch<psz>::LDS_RING, LDS_ZERO
+      constexpr int lds_ring = Patch::LDS_RING, lds_zero = Patch::LDS_ZERO;
       std::vector<unsigned short> plds(nts * 48, (unsigned short)lds_zero);
       for (int pi = 0; pi < P.npatch; pi++) {
         std::map<long, int> ring;   // source -> ring entry
@@ -643,23 +615,22 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
           for (int k = 0; k < 48; k++) {
             const int2 t = tab[(size_t)e * 48 + k];
             unsigned short ent = (unsigned short)lds_zero;
-            if (t.x >= 0 && pid[si][t.x] == pi) ent = (unsigned short)lds_own_entry(tslot_of[t.x] - pi * psz, t.y);
+            if (t.x >= 0 && pid[t.x] == pi) ent = (unsigned short)lds_own_entry(tslot_of[t.x] - pi * PS, t.y);
             else if (t.x != -1) {
               const long key = ring_key(t);
               auto it = ring.find(key);
               if (it == ring.end()) {
                 if ((int)ring.size() >= nrmax) return fail("tse_init: halo ring of patch %d exceeds %d entries", pi, nrmax);
                 it = ring.emplace(key, (int)ring.size()).first;
-                if (!ab_noring)
-                  pring[(size_t)pi * nrmax + it->second] = t.x >= 0 ? (unsigned)slot_of[t.x] * 16 + ppos(pperm[slot_of[t.x]], t.y) : c->halo0() + (unsigned)(-(t.x + 2));
+                pring[(size_t)pi * nrmax + it->second] = t.x >= 0 ? (unsigned)slot_of[t.x] * 16 + ppos(pperm[slot_of[t.x]], t.y) : c->halo0() + (unsigned)(-(t.x + 2));
               }
               ent = (unsigned short)(lds_ring + it->second);
             }
-            plds[((size_t)pi * psz + i) * 48 + k] = ent;
+            plds[((size_t)pi * PS + i) * 48 + k] = ent;
           }
         }
       }
-      for (unsigned ent : pring)   // what this tiling's halo rings read from the slots
+      for (unsigned ent : pring)   // what the halo rings read from the slots
         if (ent < (unsigned)c->nslots * 16) pexp[ent / 16] = std::max<unsigned char>(pexp[ent / 16], (unsigned char)((ent % 16) / 4 + 1));
       // element ring and neighbour entries of every patch, for the bounds image of the stage-3 kernel (k_advance<2,3>)
       std::vector<int> pering((size_t)P.npatch * NER, 0);
@@ -672,14 +643,14 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
           for (int d = 0; d < 8; d++) {
             const int nb = nbr[e * 8 + d];
             if (nb == -1) continue;
-            if (nb >= 0 && pid[si][nb] == pi) { pnb[((size_t)pi * psz + i) * 8 + d] = (unsigned char)(tslot_of[nb] - pi * psz); continue; }
+            if (nb >= 0 && pid[nb] == pi) { pnb[((size_t)pi * PS + i) * 8 + d] = (unsigned char)(tslot_of[nb] - pi * PS); continue; }
             auto it = ring.find(nb);
             if (it == ring.end()) {
               if ((int)ring.size() >= NER) return fail("tse_init: patch %d has more than %d elements around it", pi, NER);
               it = ring.emplace(nb, (int)ring.size()).first;
               pering[(size_t)pi * NER + it->second] = nb >= 0 ? nb : n + (-(nb + 2));
             }
-            pnb[((size_t)pi * psz + i) * 8 + d] = (unsigned char)(psz + it->second);
+            pnb[((size_t)pi * PS + i) * 8 + d] = (unsigned char)(PS + it->second);
           }
         }
       }
@@ -800,16 +771,13 @@ void tse_finalize(tse_ctx* c) {
   for (hipEvent_t e : c->bad_ev) if (e) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; i++) { if (c->stage[i]) (void)hipHostFree(c->stage[i]); if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]); }
   void* ptrs[] = {c->dcmip_tab, c->dvv_d, c->Dinv, c->metdet, c->rmetdet, c->spheremp, c->rspheremp, c->hyai, c->hybi, c->dp0, c->dss_tab, c->send_src,
-                  c->nbr, c->mm_send_src, c->qorig[0] ? c->qorig[0] : c->qlev[0], c->qorig[0] ? c->qorig[1] : c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
+                  c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
                   c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
                   c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int};
   for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (c->pool.empty()) { for (double* p : {c->T, c->B, c->C}) if (p) (void)hipFree(p); }
-  else for (double* p : c->pool) if (p) (void)hipFree(p);
-  for (PatchSet& P : c->pset) {
-    void* tp[] = {P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb};
-    for (void* p : tp) if (p) (void)hipFree(p);
-  }
+  for (double* p : {c->T, c->B, c->C}) if (p) (void)hipFree(p);
+  const PatchSet& P = c->pset;
+  for (void* p : {(void*)P.pslots, (void*)P.plist_bnd, (void*)P.plist_int, (void*)P.pering, (void*)P.pring, (void*)P.plds, (void*)P.pnb}) if (p) (void)hipFree(p);
   resolve_timers(c);
   for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->sync_events) if (e) (void)hipEventDestroy(e);
@@ -844,10 +812,10 @@ int tse_placement(tse_ctx* c, int* ntried, double* write_gbs /* [32] */, int* ch
   if (chosen) for (int r = 0; r < 5; r++) chosen[r] = c->place_sel[r];
   return 0;
 }
-// patches of the storage tiling that touch another rank (launched first in every stage) and that do not
+// patches that touch another rank (launched first in every stage) and that do not
 int tse_patch_layout(tse_ctx* c, int* np_boundary, int* np_interior) {
-  if (np_boundary) *np_boundary = c->pset[0].np_bnd;
-  if (np_interior) *np_interior = c->pset[0].np_int;
+  if (np_boundary) *np_boundary = c->pset.np_bnd;
+  if (np_interior) *np_interior = c->pset.np_int;
   return 0;
 }
 int tse_invalidate_cache(tse_ctx* c) { set_bounds_cache(c, 0); c->dcmip_static = false; return 0; }
@@ -1184,8 +1152,8 @@ static int nbr_minmax_kernel(tse_ctx* c) {
   const int m = c->mm_m();
   {
     Scope s(c, "minmax");
-    hipLaunchKernelGGL(k_nbr_minmax_patch<8>, dim3(nbr_patch_blocks(c->pset[0].npatch, c->qsize)), dim3(512), 0, c->stream, c->pset[0].npatch, c->qsize, c->nbr,
-                       c->pset[0].pslots, c->slot_of, c->qmin, c->qmax, c->qmin2, c->qmax2, c->recvbuf_mm, 2 * m);
+    hipLaunchKernelGGL(k_nbr_minmax_patch<8>, dim3(nbr_patch_blocks(c->pset.npatch, c->qsize)), dim3(512), 0, c->stream, c->pset.npatch, c->qsize, c->nbr,
+                       c->pset.pslots, c->slot_of, c->qmin, c->qmax, c->qmin2, c->qmax2, c->recvbuf_mm, 2 * m);
     LAUNCH_CHECK();
   }
   std::swap(c->qmin, c->qmin2); std::swap(c->qmax, c->qmax2);
@@ -1214,34 +1182,22 @@ static int dss_level_var(tse_ctx* c, double** varp, int var_levels) {
 }
 // tracer DSS pass src (scratch layout, halo columns filled) -> dst (standard layout), optionally fused with qdp_time_avg and the
 // next step's bounds; over all patches (npwork < 0) or over the patch list of a split launch
-// run f(std::integral_constant<int, PSZ>) for the block shape psz
-template <class F>
-static int with_shape(int psz, F f) {
-  if (psz == 32) return f(std::integral_constant<int, 32>{});
-  if (psz == 24) return f(std::integral_constant<int, 24>{});
-  return f(std::integral_constant<int, 16>{});
-}
 static int dss_tracer_launch(tse_ctx* c, const double* src, double* dst, const double* Qn0_avg, const int* plist, int npwork,
                              double* var_out = nullptr, int var_out_lev = 0) {
   if (!npwork) return 0;
-  const PatchSet& P = c->set_of(K_DSS);
-  const GatherArgs ga = c->gargs(P, nullptr, c->nelemd, plist, npwork, nullptr, 0, var_out, var_out_lev);
+  const GatherArgs ga = c->gargs(nullptr, c->nelemd, plist, npwork, nullptr, 0, var_out, var_out_lev);
   const dim3 grid(patch_blocks(npwork));
-  with_shape(P.psz, [&](auto psz) {
-    constexpr int Z = decltype(psz)::value;
-    if (Qn0_avg)
-      hipLaunchKernelGGL((k_dss_patch<1, Z>), grid, dim3(Patch<Z>::THREADS), 0, c->stream, c->qsize, src, dst, Qn0_avg, (const double*)c->dp, c->qmin2, c->qmax2, ga);
-    else
-      hipLaunchKernelGGL((k_dss_patch<0, Z>), grid, dim3(Patch<Z>::THREADS), 0, c->stream, c->qsize, src, dst, (const double*)nullptr, (const double*)nullptr,
-                         (double*)nullptr, (double*)nullptr, ga);
-    return 0;
-  });
+  if (Qn0_avg)
+    hipLaunchKernelGGL(k_dss_patch<1>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, Qn0_avg, (const double*)c->dp, c->qmin2, c->qmax2, ga);
+  else
+    hipLaunchKernelGGL(k_dss_patch<0>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, (const double*)nullptr, (const double*)nullptr,
+                       (double*)nullptr, (double*)nullptr, ga);
   LAUNCH_CHECK();
   return 0;
 }
 static int dss_tracer_pass(tse_ctx* c, const double* src, double* dst, const double* Qn0_avg, double* var_out = nullptr, int var_out_lev = 0) {
   Scope s(c, "dss");
-  return dss_tracer_launch(c, src, dst, Qn0_avg, nullptr, c->set_of(K_DSS).npatch, var_out, var_out_lev);
+  return dss_tracer_launch(c, src, dst, Qn0_avg, nullptr, c->pset.npatch, var_out, var_out_lev);
 }
 
 // One euler_step of the per-stage API (prim_advection_mod.F90:667-970): every stage ends with a tracer DSS pass, because
@@ -1255,7 +1211,7 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
   const int var_levels = DSSopt == 1 ? NLEVP : NLEV;
   const int nq = c->qsize * NLEV;
   const dim3 grid(flat_blocks(c->nelemd)), blk(FLAT_THREADS);
-  const GatherArgs plain = c->gargs(c->pset[0], nullptr, c->nelemd, nullptr, 0);
+  const GatherArgs plain = c->gargs(nullptr, c->nelemd, nullptr, 0);
   if (rhs == 0) {
     if (fused_mm && c->mm_valid == n0_qdp) {
       // the previous step's last kernel (final DSS or remap) already left the element min/max of Qdp(n0)/dp in qmin2/qmax2
@@ -1342,28 +1298,28 @@ static hipEvent_t next_sync_event(tse_ctx* c) {
 }
 
 // the part of the local mesh one launch covers: everything (single rank), the elements / patches that touch another rank, the rest
-struct Work { const int* order; int nwork; const PatchSet* P; const int* plist; int npwork; };
-static Work work_of(const tse_ctx* c, int part, int kidx) {
-  const PatchSet& P = c->set_of(kidx);
-  if (part == 0) return Work{nullptr, c->nelemd, &P, nullptr, P.npatch};
-  if (part == 1) return Work{c->ord_bnd, c->n_bnd, &P, P.plist_bnd, P.np_bnd};
-  return Work{c->ord_int, c->n_int, &P, P.plist_int, P.np_int};
+struct Work { const int* order; int nwork; const int* plist; int npwork; };
+static Work work_of(const tse_ctx* c, int part) {
+  const PatchSet& P = c->pset;
+  if (part == 0) return Work{nullptr, c->nelemd, nullptr, P.npatch};
+  if (part == 1) return Work{c->ord_bnd, c->n_bnd, P.plist_bnd, P.np_bnd};
+  return Work{c->ord_int, c->n_int, P.plist_int, P.np_int};
 }
 
 // done_out == nullptr: the compute stream waits for the communication work before it goes on; otherwise the event that marks
 // its completion is handed back and whoever consumes the halo waits for it (the prefetched bounds exchange)
 template <class Launch, class CommWork>
-static int split_stage(tse_ctx* c, const char* timer, int kidx /* whose patch tiling the launches walk */, Launch launch /* (Work) */,
+static int split_stage(tse_ctx* c, const char* timer, Launch launch /* (Work) */,
                        CommWork comm_work /* () on c->comm_stream */, hipEvent_t* done_out = nullptr) {
   Scope s(c, timer);
-  if (!c->halo()) return launch(work_of(c, 0, kidx));
+  if (!c->halo()) return launch(work_of(c, 0));
   // The two launches touch disjoint elements and depend on the same predecessors, not on each other: the interior launch goes to a
   // stream of its own (lower priority) that waits for what the compute stream has seen so far, so its first blocks fill the CUs the
   // boundary launch's last, partial round of blocks leaves idle (a rank's boundary launch is 1-3 rounds of blocks); the compute stream
   // goes on when both are done.
   hipEvent_t evA = nullptr;
   if (c->int_stream) { evA = next_sync_event(c); HIPCHK(hipEventRecord(evA, c->stream)); }
-  if (launch(work_of(c, 1, kidx))) return 1;
+  if (launch(work_of(c, 1))) return 1;
   hipEvent_t evB = next_sync_event(c), evC = done_out ? c->ev_mm : next_sync_event(c);
   HIPCHK(hipEventRecord(evB, c->stream));
   HIPCHK(hipStreamWaitEvent(c->comm_stream, evB, 0));
@@ -1371,13 +1327,13 @@ static int split_stage(tse_ctx* c, const char* timer, int kidx /* whose patch ti
   if (c->int_stream) {
     HIPCHK(hipStreamWaitEvent(c->int_stream, evA, 0));
     std::swap(c->stream, c->int_stream);   // (the launch closures launch on c->stream)
-    const int rc = launch(work_of(c, 2, kidx));
+    const int rc = launch(work_of(c, 2));
     std::swap(c->stream, c->int_stream);
     if (rc) return 1;
     hipEvent_t evI = next_sync_event(c);
     HIPCHK(hipEventRecord(evI, c->int_stream));
     HIPCHK(hipStreamWaitEvent(c->stream, evI, 0));
-  } else if (launch(work_of(c, 2, kidx))) return 1;
+  } else if (launch(work_of(c, 2))) return 1;
   if (!c->comm) { if (comm_work()) return 1; HIPCHK(hipEventRecord(evC, c->comm_stream)); }
   if (done_out) *done_out = evC;
   else HIPCHK(hipStreamWaitEvent(c->stream, evC, 0));
@@ -1404,7 +1360,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   // the stage's extra DSS variable travels as plane qsize of the stage's scratch output and is assembled on read by the next
   // kernel (var_in / var_out of GatherArgs): divdp_proj with stage 1, eta_dot_dpdn with stage 2, omega_p with stage 3
   auto gargs = [&](const Work& w, const double* vin = nullptr, int vin_lev = 0, double* vout = nullptr, int vout_lev = 0) {
-    return c->gargs(*w.P, w.order, w.nwork, w.plist, w.npwork, vin, vin_lev, vout, vout_lev);
+    return c->gargs(w.order, w.nwork, w.plist, w.npwork, vin, vin_lev, vout, vout_lev);
   };
   const int nqv = nq + NLEV;   // layers of a tracer halo message with the extra variable behind the tracers
 
@@ -1433,7 +1389,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   }
   if (nbr_minmax_kernel(c)) return 1;
   if (join_inputs(c)) return 1;   // (the wind generator ran beside the neighbour min/max pass)
-  if (split_stage(c, "advance0", K_ADV1,
+  if (split_stage(c, "advance0",
         [&](Work w) -> int {
           if (!w.nwork) return 0;
           GatherArgs ga = gargs(w, c->divdp_proj, NLEV);
@@ -1444,40 +1400,34 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
         [&]() -> int { return pack_tracers(c, cs, c->T, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->T, nqv, nqv); })) return 1;
 
   // ---- stage 2 (rhs_multiplier 1, DSS extra = eta_dot_dpdn): T (+) edges -> B
-  if (split_stage(c, "advance1", K_ADV1,
+  if (split_stage(c, "advance1",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
-          with_shape(w.P->psz, [&](auto psz) {
-            constexpr int Z = decltype(psz)::value;
-            hipLaunchKernelGGL((k_advance<1, 1, true, Z>), dim3(patch_blocks(w.npwork)), dim3(Patch<Z>::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts,
-                               c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0,
-                               gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
-            return 0; });
+          hipLaunchKernelGGL((k_advance<1, 1, true>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts,
+                             c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0,
+                             gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
           LAUNCH_CHECK(); return 0; },
         [&]() -> int { return pack_tracers(c, cs, c->B, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->B, nqv, nqv); })) return 1;
 
   // ---- stage 3 (rhs_multiplier 2, DSS extra = omega_p)
   // 3a: B (+) edges -> first Laplacian (pre-DSS) of the stage-2 tracers in T, element min/max (the DSS'd tracers themselves are
   //     not stored: 3b assembles them again from B); the element bounds and the Laplacian halo travel together (biharmonic_wk_scalar_minmax packs lap, Qmin, Qmax into one message: viscosity_mod.F90:389-391)
-  if (split_stage(c, "lap", K_LAP,
+  if (split_stage(c, "lap",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
-          with_shape(w.P->psz, [&](auto psz) {
-            constexpr int Z = decltype(psz)::value;
-            GatherArgs ga = gargs(w, nullptr, 0, c->eta, NLEVP);
-            ga.pexp = c->pexp;   // only what other patches and ranks read of the first Laplacian is stored: stage 3b forms its own slots' itself
-            hipLaunchKernelGGL((k_lap1<1, Z>), dim3(patch_blocks(w.npwork)), dim3(Patch<Z>::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dts,
-                               (const double*)c->B, c->T, c->dp, c->divdp_proj, c->qmin, c->qmax, ga);
-            return 0; });
+          GatherArgs ga = gargs(w, nullptr, 0, c->eta, NLEVP);
+          ga.pexp = c->pexp;   // only what other patches and ranks read of the first Laplacian is stored: stage 3b forms its own slots' itself
+          hipLaunchKernelGGL(k_lap1<1>, dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dts,
+                             (const double*)c->B, c->T, c->dp, c->divdp_proj, c->qmin, c->qmax, ga);
           LAUNCH_CHECK(); return 0; },
         [&]() -> int { return pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs) || unpack_minmax(c, cs) || pack_tracers(c, cs, c->T, nq) ||
                               halo_exchange(c, nq, 0, cs) || unpack_halo(c, cs, c->T, nq); })) return 1;
   // (no neighbour min/max pass here: 3b forms it from the element bounds -- its patch's and the element ring's -- while it runs)
   // 3b: B (+) edges, T (+) edges -> C (2nd Laplacian + biharmonic scaling + advance + limiter)
-  if (split_stage(c, "advance2", K_ADV2,
+  if (split_stage(c, "advance2",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
-          launch_advance23(w.P->psz, patch_blocks(w.npwork), c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, c->B, c->T, c->C, c->vn0, c->dp,
+          launch_advance23(patch_blocks(w.npwork), c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, c->B, c->T, c->C, c->vn0, c->dp,
                            c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, gargs(w, c->omega_p, NLEV));   // (tse_stage3.hip)
           LAUNCH_CHECK(); return 0; },
         [&]() -> int { return pack_tracers(c, cs, c->C, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->C, nqv, nqv); })) return 1;
@@ -1489,7 +1439,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   // final DSS fused with qdp_time_avg (:645-662) and with the next step's element min/max
   if (prefetch && c->halo()) {
     hipEvent_t done = nullptr;
-    if (split_stage(c, "dss", K_DSS,
+    if (split_stage(c, "dss",
           [&](Work w) -> int { return dss_tracer_launch(c, c->C, Qnp1, Qn0, w.plist, w.npwork, c->omega_p, NLEV); },
           [&]() -> int { return pack_minmax(c, cs, c->qmin2, c->qmax2) || halo_exchange(c, 2 * c->mm_m(), 1, cs); }, &done)) return 1;
     set_bounds_cache(c, np1_qdp);
@@ -1571,13 +1521,13 @@ static int remap_launch(tse_ctx* c, double dt, int np1_qdp, bool prefetch) {
     const int nq = c->qsize * NLEV;
     hipStream_t cs = c->comm_stream;
     hipEvent_t done = nullptr;
-    if (split_stage(c, "remap", K_DSS, launch, [&]() -> int { return pack_minmax(c, cs, c->qmin2, c->qmax2) || halo_exchange(c, 2 * c->mm_m(), 1, cs); }, &done))
+    if (split_stage(c, "remap", launch, [&]() -> int { return pack_minmax(c, cs, c->qmin2, c->qmax2) || halo_exchange(c, 2 * c->mm_m(), 1, cs); }, &done))
       return 1;
     set_bounds_cache(c, np1_qdp);   // k_remap emitted the element min/max of the remapped field
     c->mm_halo = np1_qdp;
   } else {
     Scope s(c, "remap");
-    if (launch(work_of(c, 0, K_DSS))) return 1;
+    if (launch(work_of(c, 0))) return 1;
     set_bounds_cache(c, np1_qdp);
   }
   return 0;
@@ -1753,7 +1703,6 @@ int tse_prim_run_subcycle(tse_ctx* c, double tstep, int nsub, int* nstep_io) {
     fail("negative layer thickness.  timestep or remap time too large");
     return 2;
   };
-  const bool overlap_inputs = !(getenv("TSE_INPUT_OVERLAP") && getenv("TSE_INPUT_OVERLAP")[0] == '0');
   // the remap that closes the cycle assembles the last step's final DSS + time average on read (TSE_REMAP_FUSED=0: two kernels)
   const bool fuse_remap = remap_fused() && dss_on_read() && c->tps * 8 < ((size_t)1 << 32) && !(getenv("TSE_REMAP_NT") && atoi(getenv("TSE_REMAP_NT")) != 1);
   for (int s = 0; s < nsub; s++) {
@@ -1763,13 +1712,12 @@ int tse_prim_run_subcycle(tse_ctx* c, double tstep, int nsub, int* nstep_io) {
     }
     int n0 = 1, np1 = 2;
     for (int r = (s == 0 ? r0 : 0); r < c->rsplit; r++) {
-      if (overlap_inputs) {   // fork: behind everything launched so far (the previous step / remap read what this writes)
-        HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-        HIPCHK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-        if (dcmip_step_launch(c, nstep, tstep, c->aux_stream)) return 1;
-        HIPCHK(hipEventRecord(c->ev_inputs, c->aux_stream));
-        c->inputs_pending = true;   // joined by the step before its first kernel that reads them (join_inputs)
-      } else if (tse_dcmip_step_inputs(c, nstep, tstep)) return 1;
+      // the step's inputs on the auxiliary stream, forked behind everything launched so far (the previous step / remap read what this writes)
+      HIPCHK(hipEventRecord(c->ev_fork, c->stream));
+      HIPCHK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
+      if (dcmip_step_launch(c, nstep, tstep, c->aux_stream)) return 1;
+      HIPCHK(hipEventRecord(c->ev_inputs, c->aux_stream));
+      c->inputs_pending = true;   // joined by the step before its first kernel that reads them (join_inputs)
       if (nstep % 2 == 0) { n0 = 1; np1 = 2; } else { n0 = 2; np1 = 1; }  // TimeLevel_Qdp, time_mod.F90:85-109
       if (advec_step(c, tstep, n0, np1, r + 1 < c->rsplit, fuse_remap && r + 1 == c->rsplit)) return 1;   // (the remap follows the last one: its bounds would be stale)
       nstep++;
@@ -1801,60 +1749,6 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   if (nbytes) *nbytes = 0;
   return nullptr;
 }
-#ifdef TSE_AB_HOOKS
-// ---- developer experiment: where the scratch fields live (tools/placement_probe.py) ------------------------------------------
-// make the pool K scratch-sized allocations (the first three are T, B, C as allocated)
-extern "C" int tse_debug_scratch_pool(tse_ctx* c, int K) {
-  const size_t scr_n = (size_t)(c->qsize + 1) * c->tps;
-  if (c->pool.empty()) { c->pool = {c->T, c->B, c->C}; }
-  while ((int)c->pool.size() < K) {
-    double* p = nullptr;
-    if (hipMalloc((void**)&p, scr_n * 8) != hipSuccess) { (void)hipGetLastError(); return fail("tse_debug_scratch_pool: out of memory at %zu chunks", c->pool.size()); }
-    HIPCHK(hipMemset(p, 0, scr_n * 8));
-    c->pool.push_back(p);
-  }
-  HIPCHK(hipDeviceSynchronize());
-  return 0;
-}
-extern "C" int tse_debug_zero_pool(tse_ctx* c) {
-  const size_t scr_n = (size_t)(c->qsize + 1) * c->tps;
-  for (double* p : c->pool) HIPCHK(hipMemset(p, 0, scr_n * 8));
-  HIPCHK(hipDeviceSynchronize());
-  return 0;
-}
-extern "C" int tse_debug_assign_scratch(tse_ctx* c, int iT, int iB, int iC) {
-  const int K = (int)c->pool.size();
-  if (iT < 0 || iB < 0 || iC < 0 || iT >= K || iB >= K || iC >= K || iT == iB || iT == iC || iB == iC) return fail("tse_debug_assign_scratch: %d %d %d of %d", iT, iB, iC, K);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->T = c->pool[iT]; c->B = c->pool[iB]; c->C = c->pool[iC];
-  return 0;
-}
-// the tracer state's two time levels in pool chunks i1, i2 (the state must be set again afterwards)
-extern "C" int tse_debug_assign_qdp(tse_ctx* c, int i1, int i2) {
-  const int K = (int)c->pool.size();
-  if (i1 < 0 || i2 < 0 || i1 >= K || i2 >= K || i1 == i2) return fail("tse_debug_assign_qdp: %d %d of %d", i1, i2, K);
-  for (double* p : {c->T, c->B, c->C}) if (p == c->pool[i1] || p == c->pool[i2]) return fail("tse_debug_assign_qdp: chunk in use as scratch");
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (!c->qorig[0]) { c->qorig[0] = c->qlev[0]; c->qorig[1] = c->qlev[1]; }
-  c->qlev[0] = c->pool[i1]; c->qlev[1] = c->pool[i2];
-  c->mm_valid = 0;
-  return 0;
-}
-// GB/s of a streaming pass: src/dst = -1 none (write-only / read-only), 0..K-1 pool chunk, 100 | 101 = Qdp time level 1 | 2
-extern "C" int tse_debug_probe(tse_ctx* c, int src, int dst, double* gbps) {
-  const size_t n = std::min((size_t)c->qsize * c->tps, c->trc()) / 2;   // double2 units: the smaller of a scratch field and a tracer field
-  auto ptr = [&](int i) -> double2* { return i < 0 ? nullptr : i >= 100 ? (double2*)c->q(i - 99) : (double2*)c->pool[i]; };
-  hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-  hipLaunchKernelGGL(k_probe_copy, dim3(2048), dim3(256), 0, c->stream, n, (const double2*)ptr(src), ptr(dst));
-  HIPCHK(hipEventRecord(a, c->stream));
-  for (int r = 0; r < 2; r++) hipLaunchKernelGGL(k_probe_copy, dim3(2048), dim3(256), 0, c->stream, n, (const double2*)ptr(src), ptr(dst));
-  HIPCHK(hipEventRecord(b, c->stream)); HIPCHK(hipEventSynchronize(b));
-  float ms = 0; HIPCHK(hipEventElapsedTime(&ms, a, b));
-  *gbps = ((src >= 0) + (dst >= 0)) * (double)n * 16 / (ms / 2) / 1e6;
-  (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-  return 0;
-}
-#endif   // TSE_AB_HOOKS
 int tse_timing(tse_ctx* c, int enable) { resolve_timers(c); c->timing = enable != 0; c->timers.clear(); return 0; }
 int tse_kernel_time(tse_ctx* c, const char* name, double* ms, long* launches) {
   resolve_timers(c);

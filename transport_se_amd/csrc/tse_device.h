@@ -147,10 +147,6 @@ __device__ __forceinline__ void lap_q_of(const double qdp[4], const double rdp[4
 }
 __device__ __forceinline__ void laplace_lean_row(const Dvv_t& D, const LapGeo& L, const double s[4], double lap[4]) {
 #pragma clang fp contract(off)
-#ifdef TSE_NO_CONTRACTION   // A/B build: see k_advance
-  for (int i = 0; i < 4; i++) lap[i] = (L.A[i] + L.B[i] + L.C[i]) * s[i];
-  return;
-#endif
   // written point-by-point so that few cross-lane values are live at a time (register pressure)
   double w1[4], w2[4];
 #pragma unroll

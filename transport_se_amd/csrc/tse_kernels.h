@@ -30,17 +30,15 @@ constexpr int FLAT_THREADS = 256;
 constexpr int CL = 4;
 constexpr int NCHUNK = NLEV / CL;
 static_assert(NLEV % CL == 0 && CL % 2 == 0, "chunks hold whole level pairs");
-constexpr int PS = 16;        // element slots per patch of the STORAGE tiling (4 x 4 elements): slot = patch * PS + position
-// Block shapes of the DSS-on-read kernels.  A block owns a patch of PSZ element slots -- 4 x 4, 6 x 4 or 8 x 4 elements: 256, 384 or
-// 512 lanes -- whatever the storage tiling is: its tables (PatchSet, tse_api.hip) name the storage slot of every element and of
-// every halo-ring entry.  A wider patch has a shorter ring per element (0.375, 0.29, 0.25 of a field in whole lines), a narrower
-// one leaves room for more blocks per CU; each kernel takes the shape that suits its register and LDS budget.
-template <int PSZ> struct Patch {
-  static_assert(PSZ == 16 || PSZ == 24 || PSZ == 32, "patch shapes: 4x4, 6x4, 8x4 elements");
-  static constexpr int PS = PSZ, THREADS = PSZ * 16;
-  // halo-ring entries (distinct (element, point) pairs outside the patch: 68, 84, 100 for the full shapes; tse_api.hip gives a
-  // patch fewer rows if its ring would not fit); lanes 2r, 2r+1 load entry r
-  static constexpr int NRMAX = PSZ == 16 ? 96 : PSZ == 24 ? 112 : 128;
+constexpr int PS = 16;        // element slots per patch (4 x 4 elements): slot = patch * PS + position
+// Block shape of the DSS-on-read kernels: a block owns a patch of PS element slots, 256 lanes; its tables (PatchSet, tse_api.hip)
+// name the storage slot of every element and of every halo-ring entry.  (Wider blocks of 6 x 4 and 8 x 4 elements have a shorter
+// ring per element but cost occupancy: 3.4 and 8.5 ms per step more, same bits -- profiles/r03_ab_patch_shapes.txt; retired.)
+struct Patch {
+  static constexpr int THREADS = PS * 16;
+  // halo-ring entries (distinct (element, point) pairs outside the patch: 68 for a full patch; tse_api.hip gives a patch fewer
+  // rows if its ring would not fit); lanes 2r, 2r+1 load entry r
+  static constexpr int NRMAX = 96;
   // Entries of one LDS buffer (an entry = the CL levels of a point = 32 bytes = 8 of the 64 banks): the own points, the ring, one all-zero
   // entry.  The own points are SKEWED (lds_own_entry): a slot takes LDS_SLOT = 20 entries instead of 16, and point (j, i) of a slot sits at
   // position 4j + ((i + j) & 3).  A wave reads, in one ds_read_b64, the same edge of four slots (its rows' neighbour values): in the
@@ -49,11 +47,10 @@ template <int PSZ> struct Patch {
   // s, s+1 in complementary halves of the banks: 2 cycles.  (SQ_LDS_BANK_CONFLICT: more than half of the LDS cycles of the four
   // gathering kernels before; profiles/r03_ab_lds_skew.txt.)
   static constexpr int LDS_SLOT = 20;
-  static constexpr int LDS_RING = PSZ * LDS_SLOT, LDS_ZERO = LDS_RING + NRMAX, LDS_ENT = LDS_ZERO + 1;
+  static constexpr int LDS_RING = PS * LDS_SLOT, LDS_ZERO = LDS_RING + NRMAX, LDS_ENT = LDS_ZERO + 1;
   static_assert(2 * NRMAX <= THREADS, "one 16-byte ring load per lane");
 };
-__host__ __device__ inline int lds_own_entry(int sl, int p) { return sl * 20 + (p & ~3) + (((p & 3) + (p >> 2)) & 3); }   // (20 = Patch<>::LDS_SLOT)
-inline int patch_nrmax(int psz) { return psz == 16 ? Patch<16>::NRMAX : psz == 24 ? Patch<24>::NRMAX : Patch<32>::NRMAX; }
+__host__ __device__ inline int lds_own_entry(int sl, int p) { return sl * Patch::LDS_SLOT + (p & ~3) + (((p & 3) + (p >> 2)) & 3); }
 struct Scr { size_t tps; unsigned cse; };   // plane stride (doubles), entries per chunk
 // Inside a slot the 16 points are stored in a PER-SLOT order (nibble p of the slot's 64-bit word pperm[slot] = position of
 // point p).  The memory system moves whole 128-byte lines (tools/fetch_probe.hip: 32 bytes out of every line cost what the
@@ -327,7 +324,7 @@ __global__ __launch_bounds__(WB * 64) void k_nbr_minmax_patch(int npatch, int qs
 // plist/npwork: the patches this launch walks (nullptr: patches 0..npwork).  A multi-rank step launches every slab kernel
 // twice: first over the patches (plain kernels: elements, order/nwork) that touch another rank, so that their halo can travel
 // while the second launch computes the interior (tse_api.hip).
-constexpr int NER = 48;            // elements around a patch whose bounds the stage-3 kernel reads (full 4x4, 6x4, 8x4 patches: 20, 24, 28; a two-deep band
+constexpr int NER = 48;            // elements around a patch whose bounds the stage-3 kernel reads (a full patch: 20; a two-deep band
                                    // along a rank boundary: every received (element, direction) pair is an entry of its own, about 40)
 struct GatherArgs {
   Scr S;
@@ -350,8 +347,8 @@ struct GatherArgs {
   const unsigned char* pexp;       // [slot] exported lines of the slot (row_store_setup); null: every point is stored
 };
 // bounds image of the stage-3 kernel: [buffer][element entry: the patch's slots, then the element ring][min|max][level of the chunk]
-template <int PSZ> struct BoundsLds { static constexpr int ENT = PSZ + NER; double v[2][ENT][2][CL]; };   // 6-8 KB
-template <int PSZ> struct PatchLds { double v[2][Patch<PSZ>::LDS_ENT][CL]; };   // 2 x 11.3 | 15.9 | 20.5 KB
+struct BoundsLds { static constexpr int ENT = PS + NER; double v[2][ENT][2][CL]; };   // 8 KB
+struct PatchLds { double v[2][Patch::LDS_ENT][CL]; };   // 2 x 13.3 KB
 
 __device__ __forceinline__ double swz_xor4(double x) {   // value of lane ^ 4 (the other level of the pair)
   int lo = __double2loint(x), hi = __double2hiint(x);
@@ -361,9 +358,8 @@ __device__ __forceinline__ double swz_xor4(double x) {   // value of lane ^ 4 (t
 
 // block -> (patch, chunk), lane -> (slot of the patch, level of the chunk, row).  The 8 XCDs each take a contiguous range of
 // patches and walk it chunk by chunk, so that the patches whose own values are a block's ring are in flight on the same XCD.
-struct PatchId { int patch, tslot /* patch * PSZ + position: index into the patch tables */, slot /* storage slot of the element */, e, k, j; bool live, any; };
+struct PatchId { int patch, tslot /* patch * PS + position: index into the patch tables */, slot /* storage slot of the element */, e, k, j; bool live, any; };
 inline int patch_blocks(int npwork) { return 8 * ((npwork + 7) / 8) * NCHUNK; }
-template <int PSZ>
 __device__ __forceinline__ PatchId patch_slab(const GatherArgs& A) {
   const int npx = (A.npwork + 7) >> 3, x = blockIdx.x & 7, i = blockIdx.x >> 3;
   const int kc = i / npx, pi = x * npx + (i - kc * npx);
@@ -373,10 +369,10 @@ __device__ __forceinline__ PatchId patch_slab(const GatherArgs& A) {
   const int sl = threadIdx.x >> 4;
   P.k = kc * CL + ((threadIdx.x >> 2) & (CL - 1));
   P.j = threadIdx.x & 3;
-  P.tslot = P.patch * PSZ + sl;
+  P.tslot = P.patch * PS + sl;
   const int e = A.pslots[P.tslot];
   P.live = e >= 0;
-  P.e = P.live ? e : A.pslots[P.patch * PSZ];   // a hole recomputes the patch's first element and stores nothing
+  P.e = P.live ? e : A.pslots[P.patch * PS];   // a hole recomputes the patch's first element and stores nothing
   P.slot = A.slot_of[P.e];
   return P;
 }
@@ -389,11 +385,10 @@ struct RowGather {
   unsigned lr[5];      // LDS byte offsets (buffer 0) of the lane's five neighbour values
   double rs[4];
 };
-template <int PSZ>
-__device__ __forceinline__ void gather_setup(RowGather& R, PatchLds<PSZ>& L, const GatherArgs& A, const PatchId& P) {
-  constexpr int NRMAX = Patch<PSZ>::NRMAX, LDS_ZERO = Patch<PSZ>::LDS_ZERO;
+__device__ __forceinline__ void gather_setup(RowGather& R, PatchLds& L, const GatherArgs& A, const PatchId& P) {
+  constexpr int NRMAX = Patch::NRMAX, LDS_ZERO = Patch::LDS_ZERO;
   if (threadIdx.x < 2 * CL) L.v[threadIdx.x / CL][LDS_ZERO][threadIdx.x % CL] = 0.0;   // target of absent contributions (read after the first barrier)
-  const int j = P.j, kk = P.k & (CL - 1), kc = P.k / CL, sl = P.tslot - P.patch * PSZ;
+  const int j = P.j, kk = P.k & (CL - 1), kc = P.k / CL, sl = P.tslot - P.patch * PS;
   const bool edge = (j == 0) | (j == 3), odd = kk & 1;
   const int jt = j == 1 ? 0 : (j == 2 ? 3 : j);   // the edge row a middle row helps
   // (row, point, contribution index) of the row's five fetches
@@ -418,7 +413,7 @@ __device__ __forceinline__ void gather_setup(RowGather& R, PatchLds<PSZ>& L, con
   const int r = min((int)(threadIdx.x >> 1), NRMAX - 1), half = threadIdx.x & 1;
   const unsigned ent = A.pring[(size_t)P.patch * NRMAX + r];
   R.ring = ((chunk0 + ent) * CL + half * 2) * 8u;
-  R.lwr = (unsigned)((Patch<PSZ>::LDS_RING + r) * CL + half * 2) * 8u;
+  R.lwr = (unsigned)((Patch::LDS_RING + r) * CL + half * 2) * 8u;
 #pragma unroll
   for (int m = 0; m < 5; m++) R.lr[m] = ((unsigned)le[m] * CL + kk) * 8u;
   load4(A.rspheremp + (size_t)P.e * 16 + j * 4, R.rs);
@@ -435,8 +430,7 @@ __device__ __forceinline__ void gather_issue(RowGather& R, const GatherArgs& A, 
 }
 // publish the lane's loads of tracer q in LDS buffer `b` and keep its own 4 values (level pair exchange: keep my level's half
 // of what I loaded, send the other half to lane ^ 4).  Holes publish their copy into their own (unreferenced) entries.
-template <int PSZ>
-__device__ __forceinline__ void gather_publish(const RowGather& R, PatchLds<PSZ>& L, int b, int k, const GatherRaw& raw, double v[4]) {
+__device__ __forceinline__ void gather_publish(const RowGather& R, PatchLds& L, int b, int k, const GatherRaw& raw, double v[4]) {
   const bool odd = k & 1;
   char* base = reinterpret_cast<char*>(&L.v[b][0][0]);
   *reinterpret_cast<double2*>(base + R.lw) = raw.w[0];
@@ -472,32 +466,28 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // tracer) -- what these kernels did before -- leaves every line to be filled by four tracers at four different times, and the memory
 // system pays for a partial line as for a whole one and more: 1.6 ms of k_lap1's 12.8 and 1.65 of k_dss_patch's 16.8 for 6 % of their
 // bytes (profiles/r03_ab_bounds_lines.txt).
-template <int PSZ> struct BoundsStage { double v[2][2][PSZ][4][CL]; };   // [group parity][min|max][slot][tracer & 3][level]: 8 KB (4x4 patch)
-template <int PSZ>
-__device__ __forceinline__ void stage_init(BoundsStage<PSZ>& S) {   // (the pad tracers of the last group are written too: defined values)
+struct BoundsStage { double v[2][2][PS][4][CL]; };   // [group parity][min|max][slot][tracer & 3][level]: 8 KB
+__device__ __forceinline__ void stage_init(BoundsStage& S) {   // (the pad tracers of the last group are written too: defined values)
   double2* p = reinterpret_cast<double2*>(&S.v[0][0][0][0][0]);
-  p[threadIdx.x] = make_double2(0., 0.); p[threadIdx.x + PSZ * 16] = make_double2(0., 0.);   // PSZ*16 lanes x 2 x 16 B = 2*2*PSZ*16*8
+  p[threadIdx.x] = make_double2(0., 0.); p[threadIdx.x + PS * 16] = make_double2(0., 0.);   // PS*16 lanes x 2 x 16 B = 2*2*PS*16*8
 }
-template <int PSZ>
-__device__ __forceinline__ void stage_bounds(BoundsStage<PSZ>& S, int q, double mn, double mx) {   // lane = (slot, level, row): rows 0 and 1 write
+__device__ __forceinline__ void stage_bounds(BoundsStage& S, int q, double mn, double mx) {   // lane = (slot, level, row): rows 0 and 1 write
   const int t = threadIdx.x, sl = t >> 4, kk = (t >> 2) & (CL - 1), j = t & 3;
   if (j == 0) S.v[(q >> 2) & 1][0][sl][q & 3][kk] = mn;
   if (j == 1) S.v[(q >> 2) & 1][1][sl][q & 3][kk] = mx;
 }
 // the two lines per slot of tracers 4g .. 4g+3: one 16-byte store per lane; call behind a workgroup barrier that follows their stage_bounds
-template <int PSZ>
-__device__ __forceinline__ void flush_bounds(const BoundsStage<PSZ>& S, int g, const int* __restrict__ pslots, int patch, int kchunk, int qsize,
+__device__ __forceinline__ void flush_bounds(const BoundsStage& S, int g, const int* __restrict__ pslots, int patch, int kchunk, int qsize,
                                              double* __restrict__ mn_out, double* __restrict__ mx_out) {
-  const int t = threadIdx.x, a = t / (PSZ * 8), sl = (t >> 3) % PSZ, piece = t & 7;
-  const int el = pslots[patch * PSZ + sl];
+  const int t = threadIdx.x, a = t / (PS * 8), sl = (t >> 3) % PS, piece = t & 7;
+  const int el = pslots[patch * PS + sl];
   if (el < 0) return;   // hole
   const double2 v = *reinterpret_cast<const double2*>(&S.v[g & 1][a][sl][piece >> 1][(piece & 1) * 2]);
   double* dst = (a ? mx_out : mn_out) + (((size_t)el * NCHUNK + kchunk) * mm_qpad(qsize) + g * 4) * CL + piece * 2;
   *reinterpret_cast<double2*>(dst) = v;
 }
 // the reference's order per point: edge contributions (S, E, N, W) first, then the corner; an absent one adds +0.0
-template <int PSZ>
-__device__ __forceinline__ void gather_sum(const RowGather& R, const PatchLds<PSZ>& L, int b, int j, const double v[4], double out[4]) {
+__device__ __forceinline__ void gather_sum(const RowGather& R, const PatchLds& L, int b, int j, const double v[4], double out[4]) {
   const bool edge = (j == 0) | (j == 3);
   const char* base = reinterpret_cast<const char*>(&L.v[b][0][0]);
   const double f0 = *reinterpret_cast<const double*>(base + R.lr[0]), f1 = *reinterpret_cast<const double*>(base + R.lr[1]),
@@ -516,8 +506,7 @@ __device__ __forceinline__ void gather_sum(const RowGather& R, const PatchLds<PS
 }
 // DSS of the extra plane on read, before the tracer loop of a DSS-on-read kernel (LDS buffer 1: the loop starts on buffer 0, and
 // its barrier of tracer 0 separates these reads from the publish of tracer 1 into buffer 1).  All lanes of the block call it.
-template <int PSZ>
-__device__ __forceinline__ void gather_var_plane(RowGather& R, PatchLds<PSZ>& L, const GatherArgs& A, const double* __restrict__ src, int plane,
+__device__ __forceinline__ void gather_var_plane(RowGather& R, PatchLds& L, const GatherArgs& A, const double* __restrict__ src, int plane,
                                                  int j, int k, double x[4]) {
   GatherRaw raw;
   double own[4];
@@ -598,31 +587,27 @@ __global__ void k_zero_slot(int qsize, double* __restrict__ dst, Scr S, unsigned
 // (the exported lines k_lap1<1> stored) -- and so are the element bounds.  Stage 3 never needs the DSS'd stage-2 tracers in memory.
 // Register tiers (512 VGPRs per SIMD lane): 128 -> 4 waves, 168 -> 3, 256 -> 2.  Forcing the stage-2 DSS-on-read kernel
 // (170) into the 3-wave tier with amdgpu_waves_per_eu costs 2 spills and gains nothing measurable.
-template <int RHS, int GIN = 0, bool DB = (GIN != 0), int PSZ = 16 /* block shape (GIN != 0): Patch<PSZ> */>
-#ifndef TSE_ADV2_WPE
-#define TSE_ADV2_WPE 1   // A/B: minimum waves per SIMD asked of the compiler for k_advance<2,3,.,16> (3 = the 168-register tier)
-#endif
-__global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS, (GIN == 3 && PSZ == 16) ? TSE_ADV2_WPE : 1) void k_advance(int nelemd, Dvv_t D, GeoPtrs G, int qsize, double dt, double nu_q,
+template <int RHS, int GIN = 0, bool DB = (GIN != 0)>
+__global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_advance(int nelemd, Dvv_t D, GeoPtrs G, int qsize, double dt, double nu_q,
                                                           const double* __restrict__ Qn0, const double* __restrict__ lap,
                                                           double* __restrict__ Tout, const double* __restrict__ vn0,
                                                           const double* __restrict__ dp, const double* __restrict__ divdp,
                                                           const double* __restrict__ divdp_proj, double* __restrict__ qmin,
                                                           double* __restrict__ qmax, const double* __restrict__ dp0, GatherArgs GA) {
   static_assert(GIN == 0 || GIN == 1 || (GIN == 3 && RHS == 2), "plain inputs, gathered tracers, or gathered tracers and Laplacian");
-  static_assert(GIN != 0 || PSZ == 16, "the plain kernels have no block shape");
-  __shared__ PatchLds<PSZ> lds_[GIN == 3 ? 2 : 1];   // (unused and removed by the compiler when GIN == 0)
-  __shared__ BoundsLds<PSZ> bnd_;                    // (GIN == 3 only)
+  __shared__ PatchLds lds_[GIN == 3 ? 2 : 1];   // (unused and removed by the compiler when GIN == 0)
+  __shared__ BoundsLds bnd_;                    // (GIN == 3 only)
   // Stage 3 forms the first Laplacian and the element bounds of its patch's OWN slots itself (OWNLAP; below): k_lap1 only has to
   // leave what other patches and ranks read
   constexpr bool OWNLAP = GIN == 3;
-  constexpr int BND_ENT = BoundsLds<PSZ>::ENT, LDS_ZERO = Patch<PSZ>::LDS_ZERO;
-  static_assert(BND_ENT * 4 <= Patch<PSZ>::THREADS, "one 16-byte load per lane fills the bounds image");
+  constexpr int BND_ENT = BoundsLds::ENT, LDS_ZERO = Patch::LDS_ZERO;
+  static_assert(BND_ENT * 4 <= Patch::THREADS, "one 16-byte load per lane fills the bounds image");
   constexpr bool NBR = GIN == 3;                // the limiter bounds are the min/max over the element and its neighbours of qmin/qmax, formed here
   int e, k, kc, slot;
   const int j = threadIdx.x & 3;
   PatchId pid{};
   if (GIN) {
-    pid = patch_slab<PSZ>(GA);
+    pid = patch_slab(GA);
     if (!pid.any) return;   // whole block (uniform): before any barrier
     e = pid.e; kc = pid.k; k = pid.live ? pid.k : NLEV; slot = pid.slot;
   } else {
@@ -631,7 +616,7 @@ __global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS, (GIN == 3
   }
   const RowStore RS = row_store_setup(GA.S, GA.pperm, slot, j, kc);
   RowGather RG;
-  if (GIN) gather_setup<PSZ>(RG, lds_[0], GA, pid);
+  if (GIN) gather_setup(RG, lds_[0], GA, pid);
   double vdss[4] = {0, 0, 0, 0};   // the previous stage's extra variable, DSS'd on read (stage 2: divdp_proj, which this stage's dp needs)
   if (GIN && GA.var_out) {
     gather_var_plane(RG, lds_[0], GA, Qn0, qsize, j, kc, vdss);
@@ -697,19 +682,19 @@ __global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS, (GIN == 3
     const int t = threadIdx.x, u = min(t >> 2, BND_ENT - 1), w = (t >> 1) & 1, h = t & 1;   // lanes beyond the image repeat its last entry
     // (the bounds of the patch's own slots are formed in this kernel: the lanes that would load them repeat the first ring entry --
     // same address, same LDS word, same value)
-    const int ul = u < PSZ ? PSZ : u;
-    int el = GA.pering[pid.patch * NER + (ul - PSZ)];
+    const int ul = u < PS ? PS : u;
+    int el = GA.pering[pid.patch * NER + (ul - PS)];
     if (el < 0) el = pid.e;   // hole
     bsrc = (unsigned)((((size_t)el * NCHUNK + kc / CL) * mm_qpad(qsize)) * CL + h * 2);   // + q*CL: entry index in qmin / qmax (< 2^32: the arrays are < 32 GB)
     bbase = w ? qmax : qmin;
     bdst = (unsigned)(((ul * 2 + w) * CL + h * 2) * 8);
     // the 9 entries of a slab (its element, then the 8 neighbours) are shared out over the quad: row j takes entries j, j+4 (and 8)
-    const int sl = pid.live ? pid.tslot - pid.patch * PSZ : 0, kk = kc & (CL - 1);
+    const int sl = pid.live ? pid.tslot - pid.patch * PS : 0, kk = kc & (CL - 1);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
       const int d = j + 4 * i;   // 0: the element itself; d >= 1: neighbour d-1
       int n = sl;
-      if (d >= 1 && d < 9) { const int v = GA.pnb[((size_t)pid.patch * PSZ + sl) * 8 + (d - 1)]; if (v != 255) n = v; }
+      if (d >= 1 && d < 9) { const int v = GA.pnb[((size_t)pid.patch * PS + sl) * 8 + (d - 1)]; if (v != 255) n = v; }
       bnb[i] = (unsigned)((n * 2 * CL + kk) * 8);
     }
   }
@@ -820,10 +805,6 @@ __global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS, (GIN == 3
 #pragma unroll
     for (int i = 0; i < 4; i++) { gv1[i] = a1[i] * qn[i]; gv2[i] = a2[i] * qn[i]; }
     // d/dx in-register, d/dy across the quad (deriv_xy with the lane's dcol)
-#ifdef TSE_NO_CONTRACTION   // A/B build (tools/ab): the contractions replaced by a copy -- an upper bound on what a faster contraction could buy
-#pragma unroll
-    for (int i = 0; i < 4; i++) { dx[i] = gv1[i]; dy[i] = gv2[i]; }
-#else
 #pragma unroll
     for (int l = 0; l < 4; l++) {
       double sm = 0.0;
@@ -833,7 +814,6 @@ __global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS, (GIN == 3
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) dy[i] = quad_matvec(dcol, gv2[i]);
-#endif
 #pragma unroll
     for (int i = 0; i < 4; i++) x[i] = qn[i] - rm[i] * (dx[i] + dy[i]);   // Qtens = Qdp - dt*div
     bool changed = false;
@@ -868,18 +848,18 @@ __global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS, (GIN == 3
 // Q = Qdp/dp, element min/max, first weak Laplacian (pre-DSS) -> Bout
 // GIN == 1 (whole-step path; block = patch x chunk): Qn0 is the stage-2 pre-DSS scratch; the DSS'd Qdp is assembled on read
 // and not stored (k_advance<2,3> of stage 3 assembles it again itself).
-template <int GIN = 0, int PSZ = 16>
-__global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS) void k_lap1(int nelemd, Dvv_t D, GeoPtrs G, int qsize, double rdt,
+template <int GIN = 0>
+__global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(int nelemd, Dvv_t D, GeoPtrs G, int qsize, double rdt,
                                                        const double* __restrict__ Qn0, double* __restrict__ Bout,
                                                        const double* __restrict__ dp, const double* __restrict__ divdp_proj,
                                                        double* __restrict__ qmin, double* __restrict__ qmax, GatherArgs GA) {
-  __shared__ PatchLds<PSZ> lds_;
-  __shared__ BoundsStage<PSZ> stg_;   // (GIN only)
+  __shared__ PatchLds lds_;
+  __shared__ BoundsStage stg_;   // (GIN only)
   int e, k, kc, slot;
   const int j = threadIdx.x & 3;
   PatchId pid{};
   if (GIN) {
-    pid = patch_slab<PSZ>(GA);
+    pid = patch_slab(GA);
     if (!pid.any) return;   // whole block (uniform): before any barrier
     e = pid.e; kc = pid.k; k = pid.live ? pid.k : NLEV; slot = pid.slot;
   } else {
@@ -901,7 +881,7 @@ __global__ __launch_bounds__(GIN ? Patch<PSZ>::THREADS : FLAT_THREADS) void k_la
   RowGather RG;
   GatherRaw graw;
   if (GIN) {
-    gather_setup<PSZ>(RG, lds_, GA, pid);
+    gather_setup(RG, lds_, GA, pid);
     if (GA.var_out) {   // the previous stage's extra variable (stage 3: eta_dot_dpdn), DSS'd on read
       double vdss[4];
       gather_var_plane(RG, lds_, GA, Qn0, qsize, j, kc, vdss);
@@ -990,18 +970,18 @@ __device__ __forceinline__ DssLane dss_lane(int nelemd) {
 // neighbour contributions are LDS reads; remote contributions sit in the halo columns of the scratch planes (k_unpack_halo).
 // mn_out/mx_out (MODE 1 only, may be null): element min/max of Q = Qdp/dp of the field just written, i.e. what the
 // next tracer step's first stage would compute with k_qminmax (prim_advection_mod.F90:764-775) -- saves that pass.
-template <int MODE, int PSZ = 16>
-__global__ __launch_bounds__(Patch<PSZ>::THREADS) void k_dss_patch(int qsize, const double* __restrict__ src, double* __restrict__ dst,
+template <int MODE>
+__global__ __launch_bounds__(Patch::THREADS) void k_dss_patch(int qsize, const double* __restrict__ src, double* __restrict__ dst,
                                                             const double* __restrict__ Qn0, const double* __restrict__ dpnext,
                                                             double* __restrict__ mn_out, double* __restrict__ mx_out, GatherArgs GA) {
-  __shared__ PatchLds<PSZ> lds_;
-  __shared__ BoundsStage<PSZ> stg_;   // (MODE 1 with mn_out only)
-  const PatchId pid = patch_slab<PSZ>(GA);
+  __shared__ PatchLds lds_;
+  __shared__ BoundsStage stg_;   // (MODE 1 with mn_out only)
+  const PatchId pid = patch_slab(GA);
   if (!pid.any) return;   // whole block (uniform): before any barrier
   const int e = pid.e, kc = pid.k, k = pid.live ? pid.k : NLEV, j = pid.j;
   RowGather RG;
   GatherRaw graw;
-  gather_setup<PSZ>(RG, lds_, GA, pid);
+  gather_setup(RG, lds_, GA, pid);
   double dn[4] = {1, 1, 1, 1}, q0x[4] = {0, 0, 0, 0};
   if (MODE == 1 && mn_out) {   // 1/dp of the next step's stage 1 (the bounds are Qdp * (1/dp) everywhere: k_qminmax)
     load4(dpnext + ((size_t)e * NLEV + kc) * 16 + j * 4, dn);
@@ -1200,10 +1180,7 @@ __global__ void k_time_avg(size_t n, int rkstage, const double* __restrict__ Qn0
 // Measured (profiles/r03_ab_remap_two_blocks.txt): 16.5 -> 16.0 ms per launch at ne120/q35 -- the launch is bound by the vector
 // issue of the column loop (two waves per SIMD in both forms), not by the phases following one another.
 constexpr int REMAP_THREADS = 256;   // 4 waves: one per SIMD and element
-#ifndef TSE_REMAP_PF
-#define TSE_REMAP_PF 8
-#endif
-constexpr int REMAP_PF = TSE_REMAP_PF;  // column loads kept in flight per thread = levels per unrolled block = levels per segment task
+constexpr int REMAP_PF = 8;   // column loads kept in flight per thread = levels per unrolled block = levels per segment task
 static_assert(NLEV % REMAP_PF == 0, "whole blocks");
 static_assert(REMAP_PF % CL == 0, "a block of REMAP_PF levels holds whole chunks of the bounds layout");
 constexpr int REMAP_SEG_MAX = 3;   // at most this many tracers of an element go through segment tasks (LDS for their mass prefixes)
@@ -1312,11 +1289,8 @@ __device__ __forceinline__ FuseLane fuse_lane(const RemapFuse& F, int e, int p) 
   L.rs = F.rspheremp[(size_t)e * 16 + p];
   return L;
 }
-// the loads of chunk kc of one tracer column: plane = &C[q][0] as bytes, q0col = &Qn0[e][q][0][p].  The Qdp(n0) values are issued
-// apart from the scratch entries: they are 4 registers a chunk against 12, so that stream is kept TSE_FUSE_QAHEAD chunks further ahead
-#ifndef TSE_FUSE_QAHEAD
-#define TSE_FUSE_QAHEAD 0   // (1, 2: measured, no gain -- profiles/r04_ab_remap_dss_on_read.txt)
-#endif
+// the loads of chunk kc of one tracer column: plane = &C[q][0] as bytes, q0col = &Qn0[e][q][0][p].  (Keeping the Qdp(n0) stream
+// one or two chunks further ahead than the scratch entries: measured, no gain -- profiles/r04_ab_remap_dss_on_read.txt)
 __device__ __forceinline__ void fuse_issue(FuseRaw& r, const char* __restrict__ plane, unsigned cstride /* bytes per chunk */, int kc, const FuseLane& L) {
   const char* b = plane + (size_t)kc * cstride;
   r.o[0] = *reinterpret_cast<const double2*>(b + L.oown); r.o[1] = *reinterpret_cast<const double2*>(b + L.oown + 16);
@@ -1496,7 +1470,7 @@ __device__ __forceinline__ void remap_columns_fast(const RemapLds& S, double* __
   // materialized in Q beforehand (k_remap)
   FuseLane FL{};
   FuseRaw fraw;
-  double fq[TSE_FUSE_QAHEAD + 1][CL];   // Qdp(n0) of the chunk in fraw ([0]) and of the TSE_FUSE_QAHEAD chunks behind it
+  double fq[CL];   // Qdp(n0) of the chunk in fraw
   double fcur[CL] = {0, 0, 0, 0};
   const char* fplane = nullptr;
   const unsigned fcstride = FUSED ? F.S.cse * (CL * 8u) : 0u;
@@ -1525,13 +1499,12 @@ __device__ __forceinline__ void remap_columns_fast(const RemapLds& S, double* __
   auto prime_top = [&](auto fused_tag) __attribute__((always_inline)) {
     if constexpr (decltype(fused_tag)::value) {   // chunk 0 -> cells 1 .. 4 (the fourth waits in fcur[3]); chunk 1 on its way
       fuse_issue(fraw, fplane, fcstride, 0, FL);
-      fuse_issue_q(fq[0], 0, col[0]);
-      fuse_combine(fraw, fq[0], FL, fcur);
+      fuse_issue_q(fq, 0, col[0]);
+      fuse_combine(fraw, fq, FL, fcur);
       mk[0] = fcur[0]; mk1[0] = fcur[1]; mk2[0] = fcur[2];
       asm volatile("" : "+v"(fcur[3]) : : "memory");   // (the values have left fraw before the next loads are issued into it)
       fuse_issue(fraw, fplane, fcstride, 1, FL);
-#pragma unroll
-      for (int u = 0; u <= TSE_FUSE_QAHEAD; u++) fuse_issue_q(fq[u], 1 + u, col[0]);
+      fuse_issue_q(fq, 1, col[0]);
     } else {
 #pragma unroll
     for (int t = 0; t < NT; t++) {
@@ -1595,15 +1568,13 @@ __device__ __forceinline__ void remap_columns_fast(const RemapLds& S, double* __
         // issued four levels ago; combine them and send for the next chunk
         const int ci = (sl + 3) & (CL - 1);
         if (ci == 0) {
-          fuse_combine(fraw, fq[0], FL, fcur);
+          fuse_combine(fraw, fq, FL, fcur);
           asm volatile("" : "+v"(fcur[0]), "+v"(fcur[1]), "+v"(fcur[2]), "+v"(fcur[3]) : : "memory");
           const int kn = (r - 1) / CL + 1;
-          if (!TAIL || kn < NCHUNK) fuse_issue(fraw, fplane, fcstride, kn, FL);
-#pragma unroll
-          for (int u = 0; u < TSE_FUSE_QAHEAD; u++)
-#pragma unroll
-            for (int i = 0; i < CL; i++) fq[u][i] = fq[u + 1][i];   // (renamed away inside the unrolled block)
-          if (!TAIL || kn + TSE_FUSE_QAHEAD < NCHUNK) fuse_issue_q(fq[TSE_FUSE_QAHEAD], kn + TSE_FUSE_QAHEAD, col[0]);
+          if (!TAIL || kn < NCHUNK) {
+            fuse_issue(fraw, fplane, fcstride, kn, FL);
+            fuse_issue_q(fq, kn, col[0]);
+          }
         }
         mk3[0] = fcur[ci];
         ak3[0] = mk3[0] * c.rr;

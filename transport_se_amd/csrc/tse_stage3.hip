@@ -11,19 +11,12 @@
 
 namespace tse {
 
-// launch k_advance<2,3,true,psz> over `blocks` (patch, chunk) blocks; the arguments are the kernel's
-void launch_advance23(int psz, unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
+// launch k_advance<2,3,true> over `blocks` (patch, chunk) blocks; the arguments are the kernel's
+void launch_advance23(unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
                       const double* B, const double* lapT, double* C, const double* vn0, const double* dp, const double* divdp,
                       const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga) {
-  if (psz == 32)
-    hipLaunchKernelGGL((k_advance<2, 3, true, 32>), dim3(blocks), dim3(Patch<32>::THREADS), 0, stream, nelemd, D, G, qsize, dt, nu_q, B, lapT, C, vn0, dp, divdp,
-                       divdp_proj, qmin, qmax, dp0, ga);
-  else if (psz == 24)
-    hipLaunchKernelGGL((k_advance<2, 3, true, 24>), dim3(blocks), dim3(Patch<24>::THREADS), 0, stream, nelemd, D, G, qsize, dt, nu_q, B, lapT, C, vn0, dp, divdp,
-                       divdp_proj, qmin, qmax, dp0, ga);
-  else
-    hipLaunchKernelGGL((k_advance<2, 3, true, 16>), dim3(blocks), dim3(Patch<16>::THREADS), 0, stream, nelemd, D, G, qsize, dt, nu_q, B, lapT, C, vn0, dp, divdp,
-                       divdp_proj, qmin, qmax, dp0, ga);
+  hipLaunchKernelGGL((k_advance<2, 3, true>), dim3(blocks), dim3(Patch::THREADS), 0, stream, nelemd, D, G, qsize, dt, nu_q, B, lapT, C, vn0, dp, divdp,
+                     divdp_proj, qmin, qmax, dp0, ga);
 }
 
 }  // namespace tse
