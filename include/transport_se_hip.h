@@ -199,12 +199,28 @@ int tse_element_mass(tse_ctx *ctx, int nt, double *out);
  * qmin/qmax[ie][q] (may be null) = the element's minimum / maximum of Q, for the "qv=" line (:184-192). */
 int tse_element_qdiag(tse_ctx *ctx, int nt, double *mass, double *var, double *qmin, double *qmax);
 
+/* ---- the diagnostic fields prim_run_subcycle leaves in elem after the remap (prim_driver_mod.F90:803-822) ----
+ * tse_state_q forms, on the device, state%Q = Qdp(nt) / dp with dp = (hyai(k+1)-hyai(k))*ps0 + (hybi(k+1)-hybi(k))*ps_v -- the reference's
+ * operand order, no contraction, a true division: bit for bit the reference's host expression and the Q tse_element_qdiag takes its
+ * extrema of -- and state%lnps = log(ps_v), from the current ps_v.  The two fields are allocated by the first call (one tracer-sized
+ * field and one level); a context that never calls it holds neither.  They stay valid until the state changes: every entry that changes
+ * Qdp or ps_v (those that drop the bounds cache, see tse_invalidate_cache, and so tse_prim_run_subcycle, tse_vertical_remap,
+ * tse_dcmip_set_initial, tse_copy_qdp_h2d, tse_remap_q_ppm, the tracer steps) makes them stale, and the two copies then return nonzero
+ * instead of old data. */
+int tse_state_q(tse_ctx *ctx, int nt);
+/* elem(ie)%state%Q(np,np,nlev,qsize_d) <- device Q: tracers 1..qsize only, no other byte of the host element is written (same 2-D DMA /
+ * staged paths as tse_copy_qdp_d2h) */
+int tse_copy_q_d2h(tse_ctx *ctx, double *q_elem1, size_t elem_stride, int qsize_d);
+/* elem(ie)%state%lnps(:,:,np1) <- device lnps; lnps_elem1 = address of elem(1)%state%lnps(1,1,np1) */
+int tse_copy_lnps_d2h(tse_ctx *ctx, double *lnps_elem1, size_t elem_stride);
+
 /* ---- introspection for tests and the benchmark harness ---- */
 /* device pointers of internal fields: "qdp1", "qdp2" [nelemd][qsize][nlev][16] (the two time levels are two allocations), "vn0", "dp", "divdp", "divdp_proj",
- * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf" */
+ * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
+ * (both null before the first tse_state_q) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
- * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg" */
+ * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq" */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing */
 /* where the five tracer-sized fields were placed (device memory is not uniform for writes and the rate is a property of the

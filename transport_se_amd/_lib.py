@@ -111,7 +111,8 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_synchronize", "tse
            "tse_qdp_time_avg", "tse_vertical_remap", "tse_get_qminmax", "tse_dcmip_init", "tse_dcmip_set_initial",
            "tse_dcmip_step_inputs", "tse_prim_run_subcycle", "tse_device_ptr", "tse_kernel_time", "tse_timing",
            "tse_halo_layout", "tse_halo_minmax_layout", "tse_comm_unique_id", "tse_comm_init", "tse_comm_precheck", "tse_comm_version", "tse_comm_info", "tse_comm_abort",
-           "tse_boundary_layout", "tse_patch_layout", "tse_placement", "tse_invalidate_cache", "tse_divergence_sphere", "tse_laplace_sphere_wk", "tse_remap_q_ppm", "tse_host_register", "tse_element_mass", "tse_element_qdiag"]
+           "tse_boundary_layout", "tse_patch_layout", "tse_placement", "tse_invalidate_cache", "tse_divergence_sphere", "tse_laplace_sphere_wk", "tse_remap_q_ppm", "tse_host_register", "tse_element_mass", "tse_element_qdiag",
+           "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h"]
 COMM_ID_BYTES = 128
 
 
@@ -176,5 +177,8 @@ def lib(path=None):
     L.tse_host_register.argtypes = [vp, vp, sz]
     L.tse_element_mass.argtypes = [vp, i, vp]
     L.tse_element_qdiag.argtypes = [vp, i, vp, vp, vp, vp]
+    L.tse_state_q.argtypes = [vp, i]
+    L.tse_copy_q_d2h.argtypes = [vp, vp, sz, i]
+    L.tse_copy_lnps_d2h.argtypes = [vp, vp, sz]
     _libs[path] = L
     return L

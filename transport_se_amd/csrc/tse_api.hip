@@ -85,6 +85,10 @@ struct tse_ctx {
   double *vn0 = nullptr, *dp = nullptr, *divdp = nullptr, *divdp_proj = nullptr, *eta = nullptr, *omega_p = nullptr;
   double *dp3d = nullptr, *ps_v = nullptr, *lvl_tmp = nullptr;
   double *qmin = nullptr, *qmax = nullptr, *qmin2 = nullptr, *qmax2 = nullptr;
+  // state%Q = Qdp/dp and state%lnps of the state as tse_state_q last saw it: allocated by its first call (outside place_fields), valid
+  // until the next change of Qdp or ps_v (set_bounds_cache)
+  double *qmix = nullptr, *lnps = nullptr;
+  bool qmix_valid = false;
   int* bad = nullptr;
   int* bad_host = nullptr; hipEvent_t bad_ev[2] = {nullptr, nullptr};   // page-locked copies of `bad`, one per cycle in flight (tse_prim_run_subcycle)
   int mm_valid = 0;   // time level (1|2) whose element min/max of Q sit in qmin2/qmax2 (emitted by the previous step), 0 = none
@@ -157,8 +161,9 @@ struct tse_ctx {
 
 const char* tse_last_error(void) { return g_err; }
 
-// the element bounds of Qdp(tl)/dp now sit in qmin2/qmax2 (tl = 0: nothing cached); any halo of older bounds is stale
-static void set_bounds_cache(tse_ctx* c, int tl) { c->mm_valid = tl; c->mm_halo = 0; }
+// the element bounds of Qdp(tl)/dp now sit in qmin2/qmax2 (tl = 0: nothing cached); any halo of older bounds is stale.  Every entry that
+// changes Qdp or ps_v passes here, so the Q / lnps of tse_state_q go stale here too.
+static void set_bounds_cache(tse_ctx* c, int tl) { c->mm_valid = tl; c->mm_halo = 0; c->qmix_valid = false; }
 
 template <class T>
 static int dalloc(T** p, size_t n) {
@@ -772,7 +777,7 @@ void tse_finalize(tse_ctx* c) {
   for (int i = 0; i < 2; i++) { if (c->stage[i]) (void)hipHostFree(c->stage[i]); if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]); }
   void* ptrs[] = {c->dcmip_tab, c->dvv_d, c->Dinv, c->metdet, c->rmetdet, c->spheremp, c->rspheremp, c->hyai, c->hybi, c->dp0, c->dss_tab, c->send_src,
                   c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
-                  c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
+                  c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
                   c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (double* p : {c->T, c->B, c->C}) if (p) (void)hipFree(p);
@@ -990,6 +995,21 @@ int tse_copy_qdp_d2h(tse_ctx* c, double* q1, size_t stride, int qsize_d, int nt)
   if (nt < 1 || nt > 2 || qsize_d < c->qsize) return fail("tse_copy_qdp_d2h: nt=%d qsize_d=%d", nt, qsize_d);
   const size_t per = (size_t)c->qsize * NLEV * 16;
   if (copy_field(c, c->q(nt), per, (char*)q1 + (size_t)(nt - 1) * qsize_d * NLEV * 16 * 8, stride, per, false)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+// state%Q(np,np,nlev,qsize_d) of elem(:), tracers 1..qsize, and state%lnps(:,:,np1): the device fields tse_state_q formed
+int tse_copy_q_d2h(tse_ctx* c, double* q1, size_t stride, int qsize_d) {
+  if (qsize_d < c->qsize) return fail("tse_copy_q_d2h: qsize_d=%d < qsize=%d", qsize_d, c->qsize);
+  if (!c->qmix_valid) return fail("tse_copy_q_d2h: Q is stale (the state changed since the last tse_state_q, or there was none)");
+  const size_t per = (size_t)c->qsize * NLEV * 16;
+  if (copy_field(c, c->qmix, per, q1, stride, per, false)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int tse_copy_lnps_d2h(tse_ctx* c, double* lnps1, size_t stride) {
+  if (!c->qmix_valid) return fail("tse_copy_lnps_d2h: lnps is stale (the state changed since the last tse_state_q, or there was none)");
+  if (copy_field(c, c->lnps, 16, lnps1, stride, 16, false)) return 1;
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1635,6 +1655,30 @@ int tse_element_qdiag(tse_ctx* c, int nt, double* mass_out, double* var_out, dou
   return rc;
 }
 
+// state%Q = Qdp(nt)/dp(ps_v) and state%lnps = log(ps_v) of the current state, on the device (prim_driver_mod.F90:803-822); the two
+// fields are allocated by the first call and read by tse_copy_q_d2h / tse_copy_lnps_d2h
+int tse_state_q(tse_ctx* c, int nt) {
+  if (nt < 1 || nt > 2) return fail("tse_state_q: nt=%d", nt);
+  auto alloc = [&](double** p, size_t n, const char* what) -> int {
+    if (*p) return 0;
+    const hipError_t e = hipMalloc((void**)p, n * 8);
+    if (e == hipSuccess) return 0;
+    (void)hipGetLastError(); *p = nullptr;
+    return fail("tse_state_q: cannot allocate %s (%.3f GB of device memory): %s", what, n * 8 / 1e9, hipGetErrorString(e));
+  };
+  if (alloc(&c->qmix, c->trc(), "Q") || alloc(&c->lnps, (size_t)c->nelemd * 16, "lnps")) return 1;
+  c->qmix_valid = false;
+  {
+    Scope s(c, "stateq");
+    const size_t n = (size_t)c->nelemd * NLEV * 8;
+    hipLaunchKernelGGL(k_state_q<>, dim3((unsigned)((n + STATEQ_THREADS - 1) / STATEQ_THREADS)), dim3(STATEQ_THREADS), 0, c->stream, c->nelemd, c->qsize,
+                       (const double*)c->q(nt), (const double*)c->ps_v, (const double*)c->hyai, (const double*)c->hybi, c->ps0, c->qmix, c->lnps);
+    LAUNCH_CHECK();
+  }
+  c->qmix_valid = true;
+  return 0;
+}
+
 // ---- prescribed fields + device-resident driver ---------------------------------------------------
 int tse_dcmip_init(tse_ctx* c, int test, const double* lat, const double* lon, const double* hyam, const double* hybm) {
   if (test != 1 && test != 2) return fail("tse_dcmip_init: test_case=%d", test);
@@ -1741,7 +1785,7 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   const size_t m2 = (size_t)2 * c->mm_m() * 8;
   Ent ents[] = {{"qdp1", c->q(1), trc}, {"qdp2", c->q(2), trc}, {"T", c->T, scr + c->tps * 8}, {"B", c->B, scr + c->tps * 8}, {"C", c->C, scr + c->tps * 8}, {"vn0", c->vn0, 2 * lev}, {"dp", c->dp, lev},
                 {"divdp", c->divdp, lev}, {"divdp_proj", c->divdp_proj, lev}, {"eta_dot_dpdn", c->eta, (size_t)c->nelemd * NLEVP * 16 * 8},
-                {"omega_p", c->omega_p, lev}, {"dp3d", c->dp3d, lev}, {"ps_v", c->ps_v, (size_t)c->nelemd * 16 * 8}, {"qmin", c->qmin, mm},
+                {"omega_p", c->omega_p, lev}, {"dp3d", c->dp3d, lev}, {"ps_v", c->ps_v, (size_t)c->nelemd * 16 * 8}, {"q", c->qmix, trc}, {"lnps", c->lnps, (size_t)c->nelemd * 16 * 8}, {"qmin", c->qmin, mm},
                 {"qmax", c->qmax, mm}, {"sendbuf", c->sendbuf, (size_t)c->ncol_send * c->nlyr_halo * 8},
                 {"recvbuf", c->recvbuf, (size_t)c->ncol_recv * c->nlyr_halo * 8}, {"sendbuf_mm", c->sendbuf_mm, (size_t)c->nmm_send * m2},
                 {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}};

@@ -154,6 +154,15 @@ __global__ __launch_bounds__(128) void k_elem_mass(int qsize, const double* __re
   }
 }
 
+// dp of level k at a point, (hyai(k+1)-hyai(k))*ps0 + (hybi(k+1)-hybi(k))*ps_v, and the mixing ratio Q = Qdp/dp (prim_driver_mod.F90:810-815,
+// prim_state_mod.F90:604-655): the reference's operand order, no contraction, a true IEEE division (no reciprocal multiply), so that
+// every kernel that forms Q (k_elem_qdiag, k_state_q) gives the reference's host expression bit for bit.
+__device__ __forceinline__ double level_dp(const double* __restrict__ hyai, const double* __restrict__ hybi, double ps0, int k, double ps) {
+#pragma clang fp contract(off)
+  return (hyai[k + 1] - hyai[k]) * ps0 + (hybi[k + 1] - hybi[k]) * ps;
+}
+__device__ __forceinline__ double mixing_ratio(double qdp, double dpk) { return qdp / dpk; }
+
 // The element's share of the two integrals behind the "Q<q>,Q diss, dQ^2/dt:" line of prim_printstate (prim_state_mod.F90:352-385):
 // prim_diag_scalars (:604-655) forms, per point, Qmass = sum_k Qdp and Qvar = sum_k Qdp*Q with Q = Qdp/dp,
 // dp = (hyai(k+1)-hyai(k))*ps0 + (hybi(k+1)-hybi(k))*ps_v (prim_driver_mod.F90:810-815), and global_integral
@@ -172,8 +181,8 @@ __global__ __launch_bounds__(64) void k_elem_qdiag(int qsize, const double* __re
     const double ps = ps_v[(size_t)e * 16 + p];
     double m = 0.0, v = 0.0, mn = 1e300, mx = -1e300;
     for (int k = 0; k < NLEV; k++) {
-      const double dpk = (hyai[k + 1] - hyai[k]) * ps0 + (hybi[k + 1] - hybi[k]) * ps;
-      const double qd = x[(size_t)k * 16], qq = qd / dpk;
+      const double dpk = level_dp(hyai, hybi, ps0, k, ps);
+      const double qd = x[(size_t)k * 16], qq = mixing_ratio(qd, dpk);
       m = m + qd;
       v = v + qd * qq;
       mn = fmin(mn, qq); mx = fmax(mx, qq);
@@ -186,6 +195,36 @@ __global__ __launch_bounds__(64) void k_elem_qdiag(int qsize, const double* __re
     double jm = 0.0, jv = 0.0, mn = hn[0], mx = hx[0];
     for (int i = 0; i < 16; i++) { jm = jm + w[i] * hm[i]; jv = jv + w[i] * hv[i]; mn = fmin(mn, hn[i]); mx = fmax(mx, hx[i]); }
     mass_out[blockIdx.x] = jm; var_out[blockIdx.x] = jv; min_out[blockIdx.x] = mn; max_out[blockIdx.x] = mx;
+  }
+}
+
+// state%Q = Qdp(nt)/dp(ps_v) and state%lnps = log(ps_v), what prim_run_subcycle leaves in elem after the remap
+// (prim_driver_mod.F90:803-822), formed on request from the final state (tse_state_q).  A plain streaming pass: thread = (element,
+// level, point pair), 16-byte loads and stores along the points (the 8 threads of a level cover its 128 bytes, a wave 8 consecutive
+// levels), dp formed once and reused for every tracer.  Fields [e][q][k][16]; lnps [e][16] (written by the level-0 threads).
+constexpr int STATEQ_THREADS = 256;
+template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
+__global__ __launch_bounds__(STATEQ_THREADS) void k_state_q(int nelemd, int qsize, const double* __restrict__ Qdp, const double* __restrict__ ps_v,
+                                                            const double* __restrict__ hyai, const double* __restrict__ hybi, double ps0,
+                                                            double* __restrict__ Q, double* __restrict__ lnps) {
+  const size_t t = (size_t)blockIdx.x * STATEQ_THREADS + threadIdx.x;
+  if (t >= (size_t)nelemd * NLEV * 8) return;
+  const int pp = (int)(t & 7), k = (int)((t >> 3) % NLEV);
+  const size_t e = (t >> 3) / NLEV;
+  const double2 ps = reinterpret_cast<const double2*>(ps_v + e * 16)[pp];
+  const double dx = level_dp(hyai, hybi, ps0, k, ps.x), dy = level_dp(hyai, hybi, ps0, k, ps.y);
+  if (k == 0) reinterpret_cast<double2*>(lnps + e * 16)[pp] = make_double2(log(ps.x), log(ps.y));
+  const size_t plane = (size_t)NLEV * 16;   // one tracer of one element
+  const size_t off = e * qsize * plane + (size_t)k * 16 + 2 * pp;
+  constexpr int QB = 4;   // tracers per batch: all loads of a batch are issued before its first store (QB loads in flight per lane)
+  for (int q0 = 0; q0 < qsize; q0 += QB) {
+    double2 qd[QB];
+#pragma unroll
+    for (int i = 0; i < QB; i++)
+      if (q0 + i < qsize) qd[i] = *reinterpret_cast<const double2*>(Qdp + off + (size_t)(q0 + i) * plane);
+#pragma unroll
+    for (int i = 0; i < QB; i++)
+      if (q0 + i < qsize) *reinterpret_cast<double2*>(Q + off + (size_t)(q0 + i) * plane) = make_double2(mixing_ratio(qd[i].x, dx), mixing_ratio(qd[i].y, dy));
   }
 }
 

@@ -226,5 +226,14 @@ class PrimRun:
         n, q = self.mine.size, self.qsize
         return self.hip.fetch("qdp%d" % tl, (n, q, 72, 4, 4))   # (one time level: the two are separate allocations)
 
+    def fetch_q(self, tl):
+        """(Q, lnps) of this rank's elements, formed on the device from Qdp(tl) and the current ps_v (what prim_run_subcycle leaves in
+        elem%state%Q and elem%state%lnps(:,:,np1)): Q[ie][q][k][j][i], lnps[ie][j][i]"""
+        n = self.mine.size
+        out = dict(Q=np.empty((n, self.qsize, 72, 4, 4)), lnps=np.empty((n, 4, 4)))
+        self.hip.state_q(tl)
+        self.hip.copy_q_d2h(out); self.hip.copy_lnps_d2h(out)
+        return out["Q"], out["lnps"]
+
     def close(self):
         self.hip.close()

@@ -27,6 +27,7 @@ module cuda_mod
   use control_mod,    only : nu_q, limiter_option, rsplit, qsplit, vert_remap_q_alg, hypervis_subcycle_q, hypervis_power, &
                              hypervis_scaling
   use schedtype_mod,  only : schedule
+  use time_mod,       only : TimeLevel_t, TimeLevel_update, TimeLevel_Qdp
   implicit none
   private
 #include <mpif.h>
@@ -36,6 +37,11 @@ module cuda_mod
   ! wall time spent inside the seam (everything between entering a cuda_mod routine and returning to the host code), by entry
   public :: hip_seam_report
   real(kind=8), save :: t_seam(5) = 0d0   ! 1 copy_qdp_h2d, 2 copy_qdp_d2h, 3 euler_step_cuda/qdp_time_avg_cuda, 4 whole-step call, 5 vertical_remap_cuda
+  ! not in the reference's list either: the device-resident prim_run loop (INTEGRATION.md section 2b) -- prescribed DCMIP fields on the
+  ! device, nsub whole prim_run_subcycle calls in one device call, and the download of what prim_run_subcycle leaves in elem
+  public :: dcmip_init_hip, prim_run_subcycle_hip, copy_state_d2h_hip, hip_resident_report
+  real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
+  integer(c_int), save :: res_nstep = 0   ! the library's step count after the last prim_run_subcycle_hip
   integer(kind=8), save :: t_c0
 
   ! mirror of tse_init_args (include/transport_se_hip.h)
@@ -111,6 +117,25 @@ module cuda_mod
      end function
      integer(c_int) function tse_halo_minmax_layout(ctx, sl, rl) bind(C, name='tse_halo_minmax_layout')
        import; type(c_ptr), value :: ctx, sl, rl
+     end function
+     integer(c_int) function tse_dcmip_init(ctx, test, lat, lon, hyam, hybm) bind(C, name='tse_dcmip_init')
+       import; type(c_ptr), value :: ctx, lat, lon, hyam, hybm; integer(c_int), value :: test
+     end function
+     integer(c_int) function tse_dcmip_set_initial(ctx) bind(C, name='tse_dcmip_set_initial')
+       import; type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function tse_prim_run_subcycle(ctx, tstep, nsub, nstep) bind(C, name='tse_prim_run_subcycle')
+       import; type(c_ptr), value :: ctx; real(c_double), value :: tstep; integer(c_int), value :: nsub
+       integer(c_int), intent(inout) :: nstep
+     end function
+     integer(c_int) function tse_state_q(ctx, nt) bind(C, name='tse_state_q')
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: nt
+     end function
+     integer(c_int) function tse_copy_q_d2h(ctx, q, stride, qsize_d) bind(C, name='tse_copy_q_d2h')
+       import; type(c_ptr), value :: ctx, q; integer(c_size_t), value :: stride; integer(c_int), value :: qsize_d
+     end function
+     integer(c_int) function tse_copy_lnps_d2h(ctx, lnps, stride) bind(C, name='tse_copy_lnps_d2h')
+       import; type(c_ptr), value :: ctx, lnps; integer(c_size_t), value :: stride
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -458,5 +483,145 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine vertical_remap_cuda
+
+  ! ---- the device-resident prim_run loop ---------------------------------------------------------------------------------
+  ! A host that lets the library run whole prim_run_subcycle calls replaces, in prim_run (prim_driver_mod.F90:686-689, 701-943):
+  !     call cuda_mod_init(elem, hybrid, deriv, hvcoord)                  ! as for the per-stage hooks
+  !     call dcmip_init_hip(elem, hvcoord, 1)                             ! prescribed DCMIP 1-1 fields and initial state, on the device
+  !     call prim_run_subcycle_hip(elem, hvcoord, tl, dt, nsub)           ! nsub x prim_run_subcycle; Qdp never leaves the device
+  !     call copy_state_d2h_hip(elem, tl, want_qdp=.false., want_q=.true.) ! only when the host reads the state (output, diagnostics)
+  ! Qdp, dp3d and ps_v live on the device between the calls; elem(:) holds them only after copy_state_d2h_hip.
+
+  subroutine tic_res()
+    call system_clock(t_c0)
+  end subroutine tic_res
+  subroutine toc_res(i)
+    integer, intent(in) :: i
+    integer(kind=8) :: c1, rate
+    call system_clock(c1, rate)
+    t_res(i) = t_res(i) + dble(c1 - t_c0)/dble(rate)
+  end subroutine toc_res
+  subroutine hip_resident_report(nsteps)
+    integer, intent(in) :: nsteps
+    write(*,'(a,i6,a)') ' hip resident: wall seconds inside the resident-loop entries over ', nsteps, ' tracer steps'
+    write(*,'(a,3f10.4)') ' hip resident: dcmip_init_hip prim_run_subcycle_hip copy_state_d2h_hip =', t_res
+    write(*,'(a,es14.6)') ' hip resident: tracer-DOF-steps/s of prim_run_subcycle_hip + copy_state_d2h_hip = ', &
+         dble(nelemd)*np*np*nlev*qsize*nsteps/max(t_res(2) + t_res(3), 1d-30)
+  end subroutine hip_resident_report
+
+  ! the prescribed DCMIP fields of test_case (1: dcmip1-1, 2: dcmip1-2) on the device, and the initial state they define: what
+  ! set_dcmip_1_1_fields / set_dcmip_1_2_fields at time 0 and prim_init2's Qdp = Q*dp do (dcmip_wrapper_mod.F90:49-243,
+  ! prim_driver_mod.F90:646-669), for both Qdp time levels, dp3d and ps_v.  elem(:) is not written.
+  subroutine dcmip_init_hip(elem, hvcoord, test_case)
+    type(element_t), intent(in), target :: elem(:)
+    type(hvcoord_t), intent(in) :: hvcoord
+    integer,         intent(in) :: test_case
+    real(c_double), allocatable, target :: lat(:,:,:), lon(:,:,:), hyam(:), hybm(:)
+    integer :: ie, i, j
+    !$OMP BARRIER
+    !$OMP MASTER
+    call tic_res()
+    allocate(lat(np,np,nelemd), lon(np,np,nelemd), hyam(nlev), hybm(nlev))
+    do ie = 1, nelemd
+       do j = 1, np
+          do i = 1, np
+             lat(i,j,ie) = elem(ie)%spherep(i,j)%lat
+             lon(i,j,ie) = elem(ie)%spherep(i,j)%lon
+          enddo
+       enddo
+    enddo
+    hyam = hvcoord%hyam; hybm = hvcoord%hybm
+    call check(tse_dcmip_init(ctx, int(test_case,c_int), c_loc(lat), c_loc(lon), c_loc(hyam), c_loc(hybm)), 'dcmip_init_hip')
+    call check(tse_dcmip_set_initial(ctx), 'dcmip_init_hip')
+    deallocate(lat, lon, hyam, hybm)
+    call toc_res(1)
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine dcmip_init_hip
+
+  ! nsub calls of prim_run_subcycle (prim_driver_mod.F90:701-850) in one device call: per cycle rsplit x (the prescribed step inputs
+  ! + Prim_Advec_Tracers_remap_rk2) and vertical_remap, Qdp device-resident throughout.  tl advances as nsub calls of the reference's
+  ! routine advance it (qsplit = 1: rsplit leapfrog updates per cycle, time_mod.F90:111-140), and the library's step count must
+  ! then equal tl%nstep (it does unless tl%nstep lay inside an rsplit cycle).
+  subroutine prim_run_subcycle_hip(elem, hvcoord, tl, dt, nsub)
+    type(element_t),      intent(inout), target :: elem(:)
+    type(hvcoord_t),      intent(in)    :: hvcoord
+    type(TimeLevel_t),    intent(inout) :: tl
+    real(kind=real_kind), intent(in)    :: dt
+    integer,              intent(in)    :: nsub
+    integer(c_int) :: rc
+    integer :: n
+    character(len=120) :: text
+    !$OMP BARRIER
+    !$OMP MASTER
+    call tic_res()
+    res_nstep = int(tl%nstep, c_int)
+    rc = tse_prim_run_subcycle(ctx, dt*qsplit, int(nsub,c_int), res_nstep)
+    ! the reference aborts the job in vertical_remap (prim_advection_mod.F90:1323)
+    if (rc == 2) call seam_abort('negative layer thickness.  timestep or remap time too large')
+    call check(rc, 'prim_run_subcycle_hip')
+    call toc_res(2)
+#ifndef HORIZ_OPENMP
+    do n = 1, nsub*rsplit
+       call TimeLevel_update(tl, "leapfrog")
+    enddo
+#endif
+    !$OMP END MASTER
+    !$OMP BARRIER
+#ifdef HORIZ_OPENMP
+    do n = 1, nsub*rsplit    ! (every thread: TimeLevel_update synchronises the threads itself, time_mod.F90:118-139)
+       call TimeLevel_update(tl, "leapfrog")
+    enddo
+#endif
+    !$OMP MASTER
+    if (tl%nstep /= res_nstep) then
+       write(text,'(a,i0,a,i0)') 'prim_run_subcycle_hip: the library stepped to nstep = ', res_nstep, ', tl%nstep = ', tl%nstep
+       call seam_abort(trim(text))
+    endif
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine prim_run_subcycle_hip
+
+  ! What prim_run_subcycle leaves in elem (prim_driver_mod.F90:795-822), after prim_run_subcycle_hip: state%ps_v and state%dp3d of the
+  ! new dynamics level, state%lnps = log(ps_v) there, and -- only on request -- state%Q(:,:,:,1:qsize) = Qdp/dp (formed on the device)
+  ! and state%Qdp of the new tracer level (Q on request only: the first request allocates a tracer-sized device field).  The reference fills level np1 / np1_qdp and then advances tl once more (:840), so these are
+  ! tl%n0 and the n0 of TimeLevel_Qdp when the host calls this.  Nothing else is downloaded.
+  subroutine copy_state_d2h_hip(elem, tl, want_qdp, want_q)
+    type(element_t),   intent(inout), target :: elem(:)
+    type(TimeLevel_t), intent(in) :: tl
+    logical,           intent(in) :: want_qdp, want_q
+    integer(c_size_t) :: s
+    integer :: ie, nt, nq
+    real(kind=real_kind), allocatable, target :: dp3d(:,:,:,:)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call tic_res()
+    s = estride(elem)
+    nt = tl%n0
+    call TimeLevel_Qdp(tl, qsplit, nq)
+    ! ps_v(:,:,nt) is one contiguous (np,np) block per element: straight into elem; dp3d(:,:,:,nt) is a slice of a 4-D field: staged
+    allocate(dp3d(np,np,nlev,nelemd))
+    call check(tse_get_derived(ctx, c_null_ptr, 0_c_size_t, c_null_ptr, 0_c_size_t, c_null_ptr, 0_c_size_t, c_null_ptr, &
+                               0_c_size_t, c_loc(dp3d), int(np*np*nlev*8,c_size_t), c_loc(elem(1)%state%ps_v(1,1,nt)), s), &
+               'copy_state_d2h_hip')
+    do ie = 1, nelemd
+       elem(ie)%state%dp3d(:,:,:,nt) = dp3d(:,:,:,ie)
+    enddo
+    deallocate(dp3d)
+    if (want_q) then     ! Q and lnps from one device pass
+       call check(tse_state_q(ctx, int(nq,c_int)), 'copy_state_d2h_hip')
+       call check(tse_copy_q_d2h(ctx, c_loc(elem(1)%state%Q), s, int(qsize_d,c_int)), 'copy_state_d2h_hip')
+       call check(tse_copy_lnps_d2h(ctx, c_loc(elem(1)%state%lnps(1,1,nt)), s), 'copy_state_d2h_hip')
+    else                 ! no Q requested: the device holds no Q field, and lnps is the reference's own host expression (:809)
+       do ie = 1, nelemd
+          elem(ie)%state%lnps(:,:,nt) = LOG(elem(ie)%state%ps_v(:,:,nt))
+       enddo
+    endif
+    if (want_qdp) call check(tse_copy_qdp_d2h(ctx, c_loc(elem(1)%state%Qdp), s, int(qsize_d,c_int), int(nq,c_int)), &
+                             'copy_state_d2h_hip')
+    call toc_res(3)
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine copy_state_d2h_hip
 
 end module cuda_mod

@@ -8,7 +8,7 @@ include/transport_se_hip.h; `transport_se_amd/fortran/cuda_mod_hip.F90` is the I
 
 `elem` here is a dict of dense numpy arrays holding the element_t fields the path touches, in the reference's
 own index order reversed to C order (element index first):
-    Qdp[ie][tl][q][k][j][i]  (state%Qdp(np,np,nlev,qsize_d,2)),  vn0[ie][k][c][j][i], dp/divdp/divdp_proj/omega_p[ie][k][j][i],
+    Qdp[ie][tl][q][k][j][i]  (state%Qdp(np,np,nlev,qsize_d,2)),  Q[ie][q][k][j][i] (state%Q(np,np,nlev,qsize_d)),  lnps[ie][j][i],  vn0[ie][k][c][j][i], dp/divdp/divdp_proj/omega_p[ie][k][j][i],
     eta_dot_dpdn[ie][nlevp][j][i], Dinv[ie][j][i][b][a], metdet/rmetdet/spheremp/rspheremp[ie][j][i],
     putmapP/getmapP/reverse[ie][8]
 """
@@ -167,6 +167,21 @@ class HipMod:
     def copy_qdp_d2h(self, elem, nt):
         q = elem["Qdp"]; assert q.dtype == np.float64 and q.flags.c_contiguous
         self._chk(self.L.tse_copy_qdp_d2h(self.h, _vp(q), q.strides[0], q.shape[2], nt))
+
+    # ---- the diagnostic fields prim_run_subcycle leaves in elem after the remap (prim_driver_mod.F90:803-822) ----
+    def state_q(self, nt):
+        """state%Q = Qdp(nt)/dp(ps_v) and state%lnps = log(ps_v) of the current state, formed on the device"""
+        self._chk(self.L.tse_state_q(self.h, int(nt)))
+
+    def copy_q_d2h(self, elem):
+        """elem["Q"][ie][q][k][j][i] (state%Q(np,np,nlev,qsize_d)) <- device Q, tracers 0..qsize-1; TseError when Q is stale"""
+        q = elem["Q"]; assert q.dtype == np.float64 and q.flags.c_contiguous
+        self._chk(self.L.tse_copy_q_d2h(self.h, _vp(q), q.strides[0], q.shape[1]))
+
+    def copy_lnps_d2h(self, elem):
+        """elem["lnps"][ie][j][i] (state%lnps(:,:,np1)) <- device lnps; TseError when it is stale"""
+        x = elem["lnps"]; assert x.dtype == np.float64 and x.flags.c_contiguous and x[0].size >= 16
+        self._chk(self.L.tse_copy_lnps_d2h(self.h, _vp(x), x.strides[0]))
 
     # ---- per-step derived inputs/outputs (what euler_step_cuda stages from elem%derived, cuda_mod.F90:535-547) ----
     def set_derived(self, elem):
