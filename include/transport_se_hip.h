@@ -61,7 +61,8 @@ typedef struct {
   int qsize;           /* active tracers */
   int device;          /* HIP device ordinal, -1 = current */
   double nu_q;         /* control_mod nu_q */
-  int limiter_option;  /* must be 8 (the only limiter wired in the reference: prim_advection_mod.F90:858,880) */
+  int limiter_option;  /* 8: the optimization-based limiter (prim_advection_mod.F90:858,880); 0: no limiter (control_mod's default).
+                          Every other value is refused.  With 0 no tracer bounds are kept: tse_get_qminmax fails. */
   int rsplit;          /* control_mod rsplit (vertical remap frequency), informational */
   const double *Dvv;   /* deriv%Dvv(np,np), Fortran order */
   const double *hyai;  /* hvcoord%hyai(nlevp) */
@@ -169,7 +170,7 @@ int tse_remap_q_ppm(tse_ctx *ctx, double *Qdp, const double *dp1, const double *
 /* qmin/qmax(nlev,qsize,nelemd) module state of prim_advection_mod (:459), for inspection: out[ie][q][k].  Maintained as in the
  * reference by tse_euler_step (every stage leaves the bounds its limiter used); tse_advec_tracers_remap_rk2 keeps only what a later
  * stage reads (nothing reads them after stage 2, stage 3 and the next step recompute theirs) */
-int tse_get_qminmax(tse_ctx *ctx, double *qmin, double *qmax);
+int tse_get_qminmax(tse_ctx *ctx, double *qmin, double *qmax);   /* fails on a context without a limiter (limiter_option = 0) */
 
 /* ---- "next" rows: on-device prescribed fields + device-resident prim_run loop ---- */
 /* lat/lon: elem(ie)%spherep(np,np)%{lat,lon} dense [nelemd][np*np]; hyam/hybm(nlev) */

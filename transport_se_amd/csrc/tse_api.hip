@@ -29,7 +29,7 @@ using namespace tse;
 namespace tse {   // tse_stage3.hip: k_advance<2,3> lives in a translation unit of its own (another scheduler strategy)
 void launch_advance23(unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
                       const double* B, const double* lapT, double* C, const double* vn0, const double* dp, const double* divdp,
-                      const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga);
+                      const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga, bool lim);
 }
 
 // TSE_DSS_ON_READ=0 falls back to one DSS pass per stage in the whole-step call (the per-stage API always does that)
@@ -68,6 +68,9 @@ struct PatchSet {
 struct tse_ctx {
   int nelemd = 0, qsize = 0, device = 0, rsplit = 3;
   bool remap_alg2 = false;   // control_mod vert_remap_q_alg == 2: piecewise-constant boundary cells in the PPM remap
+  // control_mod limiter_option: 8 (true) or 0 (false).  Unlimited, no kernel reads or writes qmin/qmax(2): the kernels without the
+  // limiter (LIM = false) run, and no element bounds are formed, exchanged or reduced over neighbours (prim_advection_mod.F90:858,880).
+  bool lim = true;
   double nu_q = 0, ps0 = 0;
   Dvv_t D;
   hipStream_t stream = nullptr;
@@ -163,7 +166,7 @@ const char* tse_last_error(void) { return g_err; }
 
 // the element bounds of Qdp(tl)/dp now sit in qmin2/qmax2 (tl = 0: nothing cached); any halo of older bounds is stale.  Every entry that
 // changes Qdp or ps_v passes here, so the Q / lnps of tse_state_q go stale here too.
-static void set_bounds_cache(tse_ctx* c, int tl) { c->mm_valid = tl; c->mm_halo = 0; c->qmix_valid = false; }
+static void set_bounds_cache(tse_ctx* c, int tl) { c->mm_valid = c->lim ? tl : 0; c->mm_halo = 0; c->qmix_valid = false; }
 
 template <class T>
 static int dalloc(T** p, size_t n) {
@@ -306,6 +309,7 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
   c->nelemd = a->nelemd; c->qsize = a->qsize; c->nu_q = a->nu_q; c->ps0 = a->ps0; c->rsplit = a->rsplit;
   c->exchange = a->exchange; c->exchange_user = a->exchange_user;
   c->remap_alg2 = a->vert_remap_q_alg == 2;
+  c->lim = a->limiter_option == 8;
   memcpy(c->D.d, a->Dvv, sizeof c->D.d);
   { std::vector<double> dv(a->Dvv, a->Dvv + 16); if (upload(&c->dvv_d, dv)) return 1; }
   HIPCHK(hipStreamCreate(&c->stream));   // blocking w.r.t. the legacy default stream: see the note above split_stage
@@ -747,7 +751,8 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
 int tse_init(tse_ctx** out, const tse_init_args* a) {
   if (!out || !a) return fail("tse_init: null argument");
   *out = nullptr;
-  if (a->limiter_option != 8) return fail("tse_init: only limiter_option=8 is supported (got %d)", a->limiter_option);
+  if (a->limiter_option != 8 && a->limiter_option != 0)
+    return fail("tse_init: limiter_option=%d (supported: limiter_option=8, the optimization-based limiter, and 0, no limiter)", a->limiter_option);
   if (a->nelemd <= 0 || a->qsize <= 0) return fail("tse_init: nelemd=%d qsize=%d", a->nelemd, a->qsize);
   if (a->vert_remap_q_alg < 0 || a->vert_remap_q_alg > 2)
     return fail("tse_init: vert_remap_q_alg=%d (0|1: mirrored ghost cells, 2: piecewise-constant boundary cells; control_mod.F90:61-66)", a->vert_remap_q_alg);
@@ -1049,6 +1054,7 @@ int tse_get_derived(tse_ctx* c, double* divdp_proj, size_t s1, double* eta, size
   return 0;
 }
 int tse_get_qminmax(tse_ctx* c, double* qmin, double* qmax) {
+  if (!c->lim) return fail("tse_get_qminmax: this context runs without a limiter (limiter_option=0) and keeps no tracer bounds");
   const size_t mm = (size_t)c->nelemd * c->mm_m();
   HIPCHK(hipStreamSynchronize(c->stream));
   std::vector<double> h(mm);
@@ -1208,7 +1214,8 @@ static int dss_tracer_launch(tse_ctx* c, const double* src, double* dst, const d
   const GatherArgs ga = c->gargs(nullptr, c->nelemd, plist, npwork, nullptr, 0, var_out, var_out_lev);
   const dim3 grid(patch_blocks(npwork));
   if (Qn0_avg)
-    hipLaunchKernelGGL(k_dss_patch<1>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, Qn0_avg, (const double*)c->dp, c->qmin2, c->qmax2, ga);
+    hipLaunchKernelGGL(k_dss_patch<1>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, Qn0_avg, (const double*)c->dp,
+                       c->lim ? c->qmin2 : nullptr, c->lim ? c->qmax2 : nullptr, ga);   // (null: no bounds emitted, unlimited)
   else
     hipLaunchKernelGGL(k_dss_patch<0>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, (const double*)nullptr, (const double*)nullptr,
                        (double*)nullptr, (double*)nullptr, ga);
@@ -1232,7 +1239,17 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
   const int nq = c->qsize * NLEV;
   const dim3 grid(flat_blocks(c->nelemd)), blk(FLAT_THREADS);
   const GatherArgs plain = c->gargs(nullptr, c->nelemd, nullptr, 0);
-  if (rhs == 0) {
+  if (rhs == 0 && !c->lim) {
+    Scope s(c, "advance0");
+    hipLaunchKernelGGL((k_advance<0, 0, false, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
+                       c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr, c->dp0, plain);
+    LAUNCH_CHECK();
+  } else if (rhs == 1 && !c->lim) {
+    Scope s(c, "advance1");
+    hipLaunchKernelGGL((k_advance<1, 0, false, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
+                       c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr, c->dp0, plain);
+    LAUNCH_CHECK();
+  } else if (rhs == 0) {
     if (fused_mm && c->mm_valid == n0_qdp) {
       // the previous step's last kernel (final DSS or remap) already left the element min/max of Qdp(n0)/dp in qmin2/qmax2
       std::swap(c->qmin, c->qmin2); std::swap(c->qmax, c->qmax2);
@@ -1256,7 +1273,11 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
     c->t_zero_dirty = true;   // below, T receives rspheremp*DSS(lap) in the plain tracer layout
     {
       Scope s(c, "lap");
-      hipLaunchKernelGGL(k_lap1<0>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dt, Qn0, c->B, c->dp, c->divdp_proj, c->qmin, c->qmax, plain);
+      if (c->lim)
+        hipLaunchKernelGGL(k_lap1<0>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dt, Qn0, c->B, c->dp, c->divdp_proj, c->qmin, c->qmax, plain);
+      else
+        hipLaunchKernelGGL((k_lap1<0, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dt, Qn0, c->B, c->dp, c->divdp_proj,
+                           (double*)nullptr, (double*)nullptr, plain);
       LAUNCH_CHECK();
     }
     // biharmonic_wk_scalar_minmax: DSS(lap1) (+ min/max exchange) -> T = rspheremp*DSS(lap1).  The reference's message is
@@ -1265,10 +1286,14 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
     if (halo_exchange(c, nq, 0, c->stream)) return 1;
     if (unpack_halo(c, c->stream, c->B, nq)) return 1;
     if (dss_tracer_pass(c, c->B, c->T, nullptr)) return 1;
-    if (neighbor_minmax(c)) return 1;
+    if (c->lim && neighbor_minmax(c)) return 1;
     Scope s(c, "advance2");
-    hipLaunchKernelGGL(k_advance<2>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0, c->dp, c->divdp,
-                       c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    if (c->lim)
+      hipLaunchKernelGGL(k_advance<2>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0, c->dp, c->divdp,
+                         c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    else
+      hipLaunchKernelGGL((k_advance<2, 0, false, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0,
+                         c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr, c->dp0, plain);
     LAUNCH_CHECK();
   }
   double* pre = rhs == 2 ? c->B : c->T;
@@ -1385,37 +1410,45 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   const int nqv = nq + NLEV;   // layers of a tracer halo message with the extra variable behind the tracers
 
   // ---- stage 1 (rhs_multiplier 0, DSS extra = divdp_proj): bounds, neighbour min/max, advance Qdp(n0) -> T
-  const bool halo_ready = c->halo() && c->mm_valid == n0_qdp && c->mm_halo == n0_qdp;   // prefetched by the previous step / remap
-  if (c->mm_valid != n0_qdp && join_inputs(c)) return 1;   // k_qminmax reads dp
-  if (c->mm_valid == n0_qdp) {
-    // the previous step's last kernel (final DSS or remap) already left the element min/max of Qdp(n0)/dp in qmin2/qmax2
-    std::swap(c->qmin, c->qmin2); std::swap(c->qmax, c->qmax2);
-  } else {
-    Scope s(c, "minmax");
-    hipLaunchKernelGGL(k_qminmax<>, dim3(flat_blocks(c->nelemd)), blk, 0, c->stream, c->nelemd, c->qsize, 0.0, Qn0, c->dp, c->divdp_proj, c->qmin, c->qmax);
-    LAUNCH_CHECK();
+  // (unlimited: the advance alone)
+  if (c->lim) {
+    const bool halo_ready = c->halo() && c->mm_valid == n0_qdp && c->mm_halo == n0_qdp;   // prefetched by the previous step / remap
+    if (c->mm_valid != n0_qdp && join_inputs(c)) return 1;   // k_qminmax reads dp
+    if (c->mm_valid == n0_qdp) {
+      // the previous step's last kernel (final DSS or remap) already left the element min/max of Qdp(n0)/dp in qmin2/qmax2
+      std::swap(c->qmin, c->qmin2); std::swap(c->qmax, c->qmax2);
+    } else {
+      Scope s(c, "minmax");
+      hipLaunchKernelGGL(k_qminmax<>, dim3(flat_blocks(c->nelemd)), blk, 0, c->stream, c->nelemd, c->qsize, 0.0, Qn0, c->dp, c->divdp_proj, c->qmin, c->qmax);
+      LAUNCH_CHECK();
+    }
+    if (halo_ready) {
+      HIPCHK(hipStreamWaitEvent(c->stream, c->ev_mm, 0));
+    } else if (c->halo()) {
+      hipEvent_t ev0 = next_sync_event(c), evM = next_sync_event(c);
+      HIPCHK(hipEventRecord(ev0, c->stream));
+      HIPCHK(hipStreamWaitEvent(cs, ev0, 0));
+      if (pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs)) return 1;
+      HIPCHK(hipEventRecord(evM, cs));
+      HIPCHK(hipStreamWaitEvent(c->stream, evM, 0));
+    }
+    if (nbr_minmax_kernel(c)) return 1;
   }
   set_bounds_cache(c, 0);
   // (divdp = div(vn0) has no pass of its own here: stage 1's kernel forms it for its own slab and stores it for the later stages)
-  if (halo_ready) {
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_mm, 0));
-  } else if (c->halo()) {
-    hipEvent_t ev0 = next_sync_event(c), evM = next_sync_event(c);
-    HIPCHK(hipEventRecord(ev0, c->stream));
-    HIPCHK(hipStreamWaitEvent(cs, ev0, 0));
-    if (pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs)) return 1;
-    HIPCHK(hipEventRecord(evM, cs));
-    HIPCHK(hipStreamWaitEvent(c->stream, evM, 0));
-  }
-  if (nbr_minmax_kernel(c)) return 1;
   if (join_inputs(c)) return 1;   // (the wind generator ran beside the neighbour min/max pass)
   if (split_stage(c, "advance0",
         [&](Work w) -> int {
           if (!w.nwork) return 0;
           GatherArgs ga = gargs(w, c->divdp_proj, NLEV);
           ga.divdp_out = c->divdp;
-          hipLaunchKernelGGL(k_advance<0>, dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, (const double*)Qn0,
-                             (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, ga);
+          if (c->lim)
+            hipLaunchKernelGGL(k_advance<0>, dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, (const double*)Qn0,
+                               (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, ga);
+          else
+            hipLaunchKernelGGL((k_advance<0, 0, false, false>), dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q,
+                               (const double*)Qn0, (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr,
+                               c->dp0, ga);
           LAUNCH_CHECK(); return 0; },
         [&]() -> int { return pack_tracers(c, cs, c->T, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->T, nqv, nqv); })) return 1;
 
@@ -1423,9 +1456,14 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   if (split_stage(c, "advance1",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
-          hipLaunchKernelGGL((k_advance<1, 1, true>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts,
-                             c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0,
-                             gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
+          if (c->lim)
+            hipLaunchKernelGGL((k_advance<1, 1, true>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts,
+                               c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0,
+                               gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
+          else
+            hipLaunchKernelGGL((k_advance<1, 1, true, false>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(),
+                               c->qsize, dts, c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj,
+                               (double*)nullptr, (double*)nullptr, c->dp0, gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
           LAUNCH_CHECK(); return 0; },
         [&]() -> int { return pack_tracers(c, cs, c->B, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->B, nqv, nqv); })) return 1;
 
@@ -1437,18 +1475,22 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
           if (!w.npwork) return 0;
           GatherArgs ga = gargs(w, nullptr, 0, c->eta, NLEVP);
           ga.pexp = c->pexp;   // only what other patches and ranks read of the first Laplacian is stored: stage 3b forms its own slots' itself
-          hipLaunchKernelGGL(k_lap1<1>, dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dts,
-                             (const double*)c->B, c->T, c->dp, c->divdp_proj, c->qmin, c->qmax, ga);
+          if (c->lim)
+            hipLaunchKernelGGL(k_lap1<1>, dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dts,
+                               (const double*)c->B, c->T, c->dp, c->divdp_proj, c->qmin, c->qmax, ga);
+          else
+            hipLaunchKernelGGL((k_lap1<1, false>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dts,
+                               (const double*)c->B, c->T, c->dp, c->divdp_proj, (double*)nullptr, (double*)nullptr, ga);
           LAUNCH_CHECK(); return 0; },
-        [&]() -> int { return pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs) || unpack_minmax(c, cs) || pack_tracers(c, cs, c->T, nq) ||
-                              halo_exchange(c, nq, 0, cs) || unpack_halo(c, cs, c->T, nq); })) return 1;
+        [&]() -> int { return (c->lim && (pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs) || unpack_minmax(c, cs))) ||
+                              pack_tracers(c, cs, c->T, nq) || halo_exchange(c, nq, 0, cs) || unpack_halo(c, cs, c->T, nq); })) return 1;
   // (no neighbour min/max pass here: 3b forms it from the element bounds -- its patch's and the element ring's -- while it runs)
   // 3b: B (+) edges, T (+) edges -> C (2nd Laplacian + biharmonic scaling + advance + limiter)
   if (split_stage(c, "advance2",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
           launch_advance23(patch_blocks(w.npwork), c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, c->B, c->T, c->C, c->vn0, c->dp,
-                           c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, gargs(w, c->omega_p, NLEV));   // (tse_stage3.hip)
+                           c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, gargs(w, c->omega_p, NLEV), c->lim);   // (tse_stage3.hip)
           LAUNCH_CHECK(); return 0; },
         [&]() -> int { return pack_tracers(c, cs, c->C, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->C, nqv, nqv); })) return 1;
   if (defer_dss) {   // C (halo columns filled: the stage's exchange is ordered before the next launch on the compute stream) waits for the remap
@@ -1457,7 +1499,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
     return 0;
   }
   // final DSS fused with qdp_time_avg (:645-662) and with the next step's element min/max
-  if (prefetch && c->halo()) {
+  if (prefetch && c->halo() && c->lim) {
     hipEvent_t done = nullptr;
     if (split_stage(c, "dss",
           [&](Work w) -> int { return dss_tracer_launch(c, c->C, Qnp1, Qn0, w.plist, w.npwork, c->omega_p, NLEV); },
@@ -1525,7 +1567,8 @@ static int remap_launch(tse_ctx* c, double dt, int np1_qdp, bool prefetch) {
     const int* list = w.order == c->ord_bnd ? c->rl_bnd : w.order == c->ord_int ? c->rl_int : c->rl_all;   // the same elements, in slot order
     auto go = [&](auto kern, int threads) {
       hipLaunchKernelGGL(kern, dim3(8 * ((w.nwork + 7) / 8)), dim3(threads), sizeof(RemapLds), c->stream, c->qsize, dt, c->ps0, c->hyai, c->hybi,
-                         c->dp, c->divdp_proj, c->dp3d, c->ps_v, Qr, c->bad, c->qmin2, c->qmax2, generic, c->sink, (const double*)nullptr, list, w.nwork, c->lvl_tmp, F);
+                         c->dp, c->divdp_proj, c->dp3d, c->ps_v, Qr, c->bad, c->lim ? c->qmin2 : nullptr, c->lim ? c->qmax2 : nullptr, generic, c->sink,
+                         (const double*)nullptr, list, w.nwork, c->lvl_tmp, F);   // (null bounds: none emitted, unlimited)
     };
     if (fused_n0) { if (c->remap_alg2) go(k_remap<1, true, true>, REMAP_THREADS); else go(k_remap<1, false, true>, REMAP_THREADS); }
     else if (nt == 1) { if (c->remap_alg2) go(k_remap<1, true>, REMAP_THREADS); else go(k_remap<1, false>, REMAP_THREADS); }
@@ -1537,7 +1580,7 @@ static int remap_launch(tse_ctx* c, double dt, int np1_qdp, bool prefetch) {
     static const int one = 1;
     HIPCHK(hipMemcpyAsync(c->bad, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
   }
-  if (prefetch && c->halo()) {
+  if (prefetch && c->halo() && c->lim) {
     const int nq = c->qsize * NLEV;
     hipStream_t cs = c->comm_stream;
     hipEvent_t done = nullptr;

@@ -617,6 +617,8 @@ __global__ void k_zero_slot(int qsize, double* __restrict__ dst, Scr S, unsigned
 // ---------------------------------------------------------------------------------------------------
 // the fused euler_step advance (prim_advection_mod.F90:834-902) for one RK stage:
 //   Vstar = vn0/dp, dp_star = dp - dt*divdp, Qtens = Qdp - dt*div(Vstar*Qdp) [+ biharmonic], limiter8, *spheremp.
+// LIM = false (limiter_option = 0): Qtens = Qdp - dt*div(Vstar*Qdp) [+ biharmonic], *spheremp -- no dp_star, no bounds read,
+// formed or written, no limiter (:858,880 apply limiter_optim_iter_full only under limiter_option == 8).
 // RHS = rhs_multiplier.  RHS==1 folds in the local min/max update (:781-793).  RHS==2 folds in the second
 // Laplacian of the biharmonic and its scaling (viscosity_mod.F90:419-423 + prim_advection_mod.F90:813-826);
 // `lap` then holds rspheremp*DSS(laplace_sphere_wk(Q)).
@@ -626,7 +628,7 @@ __global__ void k_zero_slot(int qsize, double* __restrict__ dst, Scr S, unsigned
 // (the exported lines k_lap1<1> stored) -- and so are the element bounds.  Stage 3 never needs the DSS'd stage-2 tracers in memory.
 // Register tiers (512 VGPRs per SIMD lane): 128 -> 4 waves, 168 -> 3, 256 -> 2.  Forcing the stage-2 DSS-on-read kernel
 // (170) into the 3-wave tier with amdgpu_waves_per_eu costs 2 spills and gains nothing measurable.
-template <int RHS, int GIN = 0, bool DB = (GIN != 0)>
+template <int RHS, int GIN = 0, bool DB = (GIN != 0), bool LIM = true>
 __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_advance(int nelemd, Dvv_t D, GeoPtrs G, int qsize, double dt, double nu_q,
                                                           const double* __restrict__ Qn0, const double* __restrict__ lap,
                                                           double* __restrict__ Tout, const double* __restrict__ vn0,
@@ -635,13 +637,13 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
                                                           double* __restrict__ qmax, const double* __restrict__ dp0, GatherArgs GA) {
   static_assert(GIN == 0 || GIN == 1 || (GIN == 3 && RHS == 2), "plain inputs, gathered tracers, or gathered tracers and Laplacian");
   __shared__ PatchLds lds_[GIN == 3 ? 2 : 1];   // (unused and removed by the compiler when GIN == 0)
-  __shared__ BoundsLds bnd_;                    // (GIN == 3 only)
+  __shared__ BoundsLds bnd_;                    // (GIN == 3 with LIM only)
   // Stage 3 forms the first Laplacian and the element bounds of its patch's OWN slots itself (OWNLAP; below): k_lap1 only has to
   // leave what other patches and ranks read
   constexpr bool OWNLAP = GIN == 3;
   constexpr int BND_ENT = BoundsLds::ENT, LDS_ZERO = Patch::LDS_ZERO;
   static_assert(BND_ENT * 4 <= Patch::THREADS, "one 16-byte load per lane fills the bounds image");
-  constexpr bool NBR = GIN == 3;                // the limiter bounds are the min/max over the element and its neighbours of qmin/qmax, formed here
+  constexpr bool NBR = GIN == 3 && LIM;         // the limiter bounds are the min/max over the element and its neighbours of qmin/qmax, formed here
   int e, k, kc, slot;
   const int j = threadIdx.x & 3;
   PatchId pid{};
@@ -679,10 +681,10 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
     // it again from the vn0 it holds for Vstar anyway instead of reading the field back -- the same routine on the same inputs, the same
     // bits, 0.8 GB less to read at ne120.  (Stage 2 keeps the load: the divergence in its prologue costs k_advance<1,1> its third wave,
     // 164 -> 174 registers.)
-    if (mkdiv || GIN == 3) {
+    if (mkdiv || (GIN == 3 && LIM)) {
       divergence_sphere_row(D, g, vs1, vs2, t1);
       if (mkdiv && k < NLEV) store4(GA.divdp_out + lo, t1);
-    } else load4(divdp + lo, t1);
+    } else if (LIM) load4(divdp + lo, t1);   // (divdp only enters dp_star)
     if (GIN && GA.var_out && RHS == 1) {   // divdp_proj = what was just assembled (the array is being written by this launch)
 #pragma unroll
       for (int i = 0; i < 4; i++) t0[i] = vdss[i];
@@ -757,7 +759,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
     // (prim_advection_mod.F90:796-809: qmin = minval(...), not min(qmin, ...)), the next step starts from fresh ones (:765-779) -- so only
     // the plain kernels (stage 1 of the whole-step path, whose relaxed bounds stage 2 reuses, :781-793; every stage of the per-stage
     // API, where qmin/qmax are visible state) write them back
-    if (GIN == 0 && k < NLEV && j == 0 && o.ch) { const size_t m = mm_idx(e, q, k, qsize); qmin[m] = o.mn; qmax[m] = o.mx; }
+    if (LIM && GIN == 0 && k < NLEV && j == 0 && o.ch) { const size_t m = mm_idx(e, q, k, qsize); qmin[m] = o.mn; qmax[m] = o.mx; }
   };
   GatherRaw graw;
   double2 lring = make_double2(0., 0.);                  // OWNLAP: the lane's ring load of the first Laplacian
@@ -773,7 +775,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
     if (GIN == 0) load4(Qn0 + so, qnx);
     if (RHS == 2 && GIN != 3) load4(lap + so, lsx);
     if (NBR) braw = *reinterpret_cast<const double2*>(bbase + ((size_t)bsrc + (size_t)q * CL));
-    else { minx = qmin[mi]; maxx = qmax[mi]; }
+    else if (LIM) { minx = qmin[mi]; maxx = qmax[mi]; }
   };
   if (GIN == 3 && threadIdx.x < 2 * CL) lds_[GIN == 3 ? 1 : 0].v[threadIdx.x / CL][LDS_ZERO][threadIdx.x % CL] = 0.0;
   fetch(0);
@@ -821,7 +823,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
         char* im = reinterpret_cast<char*>(&lds_[GIN == 3 ? 1 : 0].v[q & 1][0][0]);
 #pragma unroll
         for (int i = 0; i < 4; i++) *reinterpret_cast<double*>(im + (lds_own_entry(sl, j * 4 + i) * CL + kk) * 8) = own2[i];
-        if (j == 0) { bnd_.v[q & 1][sl][0][kk] = emn; bnd_.v[q & 1][sl][1][kk] = emx; }
+        if (LIM && j == 0) { bnd_.v[q & 1][sl][0][kk] = emn; bnd_.v[q & 1][sl][1][kk] = emx; }
         lds_barrier();
         gather_sum(RG, lds_[GIN == 3 ? 1 : 0], q & 1, j, own2, ls);
       }
@@ -856,7 +858,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
 #pragma unroll
     for (int i = 0; i < 4; i++) x[i] = qn[i] - rm[i] * (dx[i] + dy[i]);   // Qtens = Qdp - dt*div
     bool changed = false;
-    if (RHS == 1) {
+    if (RHS == 1 && LIM) {
       double q0 = qn[0] * rdpk[0], q1 = qn[1] * rdpk[1], q2 = qn[2] * rdpk[2], q3 = qn[3] * rdpk[3];
       const double lmn = quad_min(fmin(fmin(q0, q1), fmin(q2, q3))), lmx = quad_max(fmax(fmax(q0, q1), fmax(q2, q3)));
       changed = (lmn < minp) | (lmx > maxp);
@@ -867,12 +869,17 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
 #pragma unroll
       for (int i = 0; i < 4; i++) x[i] = fma(visc[i], bih[i], x[i]);   // -rhs_viss*dt*nu_q*dp0*Qtens_biharmonic/spheremp (prim_advection_mod.F90:813-826)
     }
+    if (LIM) {
 #pragma unroll
-    for (int i = 0; i < 4; i++) x[i] = x[i] * rdps[i];
-    changed |= limiter8_quad(x, c, sumc, minp, maxp);
+      for (int i = 0; i < 4; i++) x[i] = x[i] * rdps[i];
+      changed |= limiter8_quad(x, c, sumc, minp, maxp);
 #pragma unroll
-    for (int i = 0; i < 4; i++) cur.x[i] = c[i] * x[i];   // spheremp * (x*dp_star)
-    cur.mn = minp; cur.mx = maxp; cur.ch = changed;   // unchanged bounds are not written back (3.5 GB per launch)
+      for (int i = 0; i < 4; i++) cur.x[i] = c[i] * x[i];   // spheremp * (x*dp_star)
+      cur.mn = minp; cur.mx = maxp; cur.ch = changed;   // unchanged bounds are not written back (3.5 GB per launch)
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++) cur.x[i] = spm[i] * x[i];   // spheremp * Qtens (:891)
+    }
   };
   Out A, B;
   if (DB) {
@@ -887,13 +894,14 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
 // Q = Qdp/dp, element min/max, first weak Laplacian (pre-DSS) -> Bout
 // GIN == 1 (whole-step path; block = patch x chunk): Qn0 is the stage-2 pre-DSS scratch; the DSS'd Qdp is assembled on read
 // and not stored (k_advance<2,3> of stage 3 assembles it again itself).
-template <int GIN = 0>
+// LIM = false (limiter_option = 0): the first Laplacian only -- no element bounds are formed or written.
+template <int GIN = 0, bool LIM = true>
 __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(int nelemd, Dvv_t D, GeoPtrs G, int qsize, double rdt,
                                                        const double* __restrict__ Qn0, double* __restrict__ Bout,
                                                        const double* __restrict__ dp, const double* __restrict__ divdp_proj,
                                                        double* __restrict__ qmin, double* __restrict__ qmax, GatherArgs GA) {
   __shared__ PatchLds lds_;
-  __shared__ BoundsStage stg_;   // (GIN only)
+  __shared__ BoundsStage stg_;   // (GIN with LIM only)
   int e, k, kc, slot;
   const int j = threadIdx.x & 3;
   PatchId pid{};
@@ -938,7 +946,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
       double mx = quad_max(fmax(fmax(x[0], x[1]), fmax(x[2], x[3])));
       laplace_lean_row(D, L, x, l1);
       store_row_pair(Bout + (size_t)q * GA.S.tps, RS, kc, k < NLEV, l1);   // scratch layout, as T
-      if (k < NLEV && j == 0) { qmin[mm_idx(e, q, k, qsize)] = mn; qmax[mm_idx(e, q, k, qsize)] = mx; }
+      if (LIM && k < NLEV && j == 0) { qmin[mm_idx(e, q, k, qsize)] = mn; qmax[mm_idx(e, q, k, qsize)] = mx; }
     }
     return;
   }
@@ -953,7 +961,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
   auto put = [&](const Out& o, int q) {   // stores of tracer q
     store_row_pair(Bout + (size_t)q * GA.S.tps, RS, kc, k < NLEV, o.l);
   };
-  stage_init(stg_);   // (ordered before its first use by the first tracer's barrier)
+  if (LIM) stage_init(stg_);   // (ordered before its first use by the first tracer's barrier)
   auto step = [&](int q, const Out* prev, int qprev, Out& cur) {
     double x[4], own[4];
     gather_publish(RG, lds_, q & 1, kc, graw, own);
@@ -962,18 +970,20 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
     gather_issue(RG, GA, Qn0, q + 1 < qsize ? q + 1 : q, graw);   // branch-free: the last step re-reads its own tracer
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();
-    if ((q & 3) == 0 && q) flush_bounds(stg_, (q >> 2) - 1, GA.pslots, pid.patch, kc / CL, qsize, qmin, qmax);   // the element bounds of the 4 tracers before
+    if (LIM && (q & 3) == 0 && q) flush_bounds(stg_, (q >> 2) - 1, GA.pslots, pid.patch, kc / CL, qsize, qmin, qmax);   // the element bounds of the 4 tracers before
     gather_sum(RG, lds_, q & 1, j, own, x);
     lap_q_of(x, dpk, x);
     cur.mn = quad_min(fmin(fmin(x[0], x[1]), fmin(x[2], x[3])));
     cur.mx = quad_max(fmax(fmax(x[0], x[1]), fmax(x[2], x[3])));
-    stage_bounds(stg_, q, cur.mn, cur.mx);
+    if (LIM) stage_bounds(stg_, q, cur.mn, cur.mx);
     laplace_lean_row(D, L, x, cur.l);
   };
   Out A, B;
   TSE_TRACER_PAIRS(step, put, qsize, A, B);
-  lds_barrier();
-  flush_bounds(stg_, (qsize - 1) >> 2, GA.pslots, pid.patch, kc / CL, qsize, qmin, qmax);
+  if (LIM) {
+    lds_barrier();
+    flush_bounds(stg_, (qsize - 1) >> 2, GA.pslots, pid.patch, kc / CL, qsize, qmin, qmax);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------

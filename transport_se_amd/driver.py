@@ -113,9 +113,10 @@ def check_schedules_match(sched, minmax_len, rank, dist_mod):
 
 class PrimRun:
     def __init__(self, ne, qsize, test_case=1, nu_q=None, tstep=None, rsplit=3, rank=0, world=1, device=0,
-                 dist_mod=None, torch_mod=None, exchange="rccl", vert_remap_q_alg=0):
+                 dist_mod=None, torch_mod=None, exchange="rccl", vert_remap_q_alg=0, limiter_option=8):
         """exchange (world > 1): "rccl" = in-library RCCL send/recv (production), "torch" = torch.distributed P2P ops in the
-        exchange callback, "staged" = callback with host-staged slots over a CPU backend (ranks may share a GPU)."""
+        exchange callback, "staged" = callback with host-staged slots over a CPU backend (ranks may share a GPU).
+        limiter_option: 8 (optimization-based limiter) or 0 (no limiter), as control_mod's."""
         self.ne, self.qsize, self.rsplit, self.test_case = ne, qsize, rsplit, test_case
         self.nu_q = NU_Q.get(ne, 1e15 * (30.0 / ne) ** 3.2) if nu_q is None else nu_q
         self.tstep = TSTEP.get(ne, 300.0 * 30.0 / ne) if tstep is None else tstep
@@ -145,7 +146,7 @@ class PrimRun:
         self.rank, self.world = rank, world
         self.hip = HipMod(self.elem, cm.dvv(), (self.hv.hyai, self.hv.hybi, self.hv.ps0), qsize, self.nu_q,
                           rsplit=rsplit, device=device, schedule=dict(send=desc["send"], recv=desc["recv"]), exchange=callback,
-                          vert_remap_q_alg=vert_remap_q_alg)
+                          vert_remap_q_alg=vert_remap_q_alg, limiter_option=limiter_option)
         if world > 1:
             check_schedules_match(desc, (self.hip.minmax_send_len, self.hip.minmax_recv_len), rank, dist_mod)
             if exchange == "rccl":

@@ -95,8 +95,8 @@ def settings(groups):
         s["nmax"] = int(s["ndays"] * 86400 / s["tstep"])       # namelist_mod.F90:347-351
     if s["nu_q"] < 0:
         s["nu_q"] = s["nu"]                                    # :700
-    if s["limiter_option"] != 8:
-        raise SystemExit("prim_main: only limiter_option = 8 is supported (the only limiter the reference wires)")
+    if s["limiter_option"] not in (0, 8):   # 0 (control_mod's default) runs unlimited; any other value would too in the reference
+        raise SystemExit("prim_main: limiter_option = %r is not supported (8: the optimization-based limiter, 0: no limiter)" % (s["limiter_option"],))
     if s["rsplit"] <= 0 or s["qsplit"] != 1:
         raise SystemExit("prim_main: needs rsplit > 0 (vertically lagrangian) and qsplit = 1")
     # what the device path does not implement is refused, never silently replaced (the Fortran seam aborts on the same keys)
@@ -244,7 +244,8 @@ def main(argv=None):
         print("prim_main: rank %d: %s" % (rank, msg), file=sys.stderr, flush=True)
         os._exit(2)
     run = PrimRun(s["ne"], s["qsize"], test_case=s["test"], nu_q=s["nu_q"], tstep=s["tstep"], rsplit=s["rsplit"], rank=rank, world=world,
-                  device=local, dist_mod=dist, torch_mod=torch, exchange=exchange, vert_remap_q_alg=s["vert_remap_q_alg"])
+                  device=local, dist_mod=dist, torch_mod=torch, exchange=exchange, vert_remap_q_alg=s["vert_remap_q_alg"],
+                  limiter_option=s["limiter_option"])
     hip, gid, nelem = run.hip, run.mine, run.nelem
     say = print if rank == 0 else (lambda *x, **k: None)
 
