@@ -1,7 +1,8 @@
 """N>1 path on CPU: world_size-2 (and 3) torch.distributed/gloo runs of the bndry_exchangeV replacement
 (transport_se_amd.driver.HaloExchange: one isend + one irecv per neighbour-rank slot) wrapped around a numpy emulation
 of the library's pack (k_pack) and gather-DSS (k_dss) that uses the SAME host tables the library builds from the
-reference-style descriptors.  Result must equal the single-rank DSS bit for bit."""
+reference-style descriptors (send_src and dss_tab of csrc/tse_tables.cpp, read through the hooks library in the parent
+process).  Result must equal the single-rank DSS bit for bit."""
 import os
 import sys
 
@@ -11,47 +12,22 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from host_tables import host_tables
 from transport_se_amd import cube_mesh as cm
 from transport_se_amd.driver import HaloExchange, check_schedules_match, partition
 
 NE, NLYR = 4, 5
 
 
-def _tables(desc):
-    """what tse_init derives from putmapP/getmapP/reverse + the Send/RecvCycle slots (tse_api.hip)"""
-    put, get, rev = desc["putmapP"], desc["getmapP"], desc["reverse"]
-    n = put.shape[0]
-    own = {}
-    for e in range(n):
-        for d in range(8):
-            if put[e, d] < 0:
-                continue
-            if d < 4:
-                for k in range(4):
-                    own[put[e, d] + (3 - k if rev[e, d] else k)] = (e, cm.edge_point(d, k))
-            else:
-                own[put[e, d]] = (e, cm.CORNER_POINT[d])
-    send_idx, recv_idx = {}, {}
-    for (_, ptr, ln) in desc["send"]:
-        for i in range(ln):
-            send_idx[ptr - 1 + i] = len(send_idx)
-    for (_, ptr, ln) in desc["recv"]:
-        for i in range(ln):
-            recv_idx[ptr - 1 + i] = len(recv_idx)
-    send_src = [own[c] for c in sorted(send_idx, key=send_idx.get)]
-    return own, send_src, recv_idx
-
-
-def _worker(rank, world, port, field, ref, q):
+def _worker(rank, world, port, field, ref, send_src, dss_tab, ncol_recv, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     topo = cm.topology(NE)
     owner = partition(NE, world)
     desc = cm.edge_descriptors(topo, owner, rank)
     mine = desc["elems"]
-    own, send_src, recv_idx = _tables(desc)
     f = field[mine]                                               # [nelemd][NLYR][16]
-    sendbuf = np.zeros((len(send_src), NLYR)); recvbuf = np.zeros((len(recv_idx), NLYR))
+    sendbuf = np.zeros((len(send_src), NLYR)); recvbuf = np.zeros((ncol_recv, NLYR))
     for c, (e, p) in enumerate(send_src):                         # k_pack
         sendbuf[c] = f[e, :, p]
     # entries of the compact min/max exchange per slot = (element, direction) pairs whose first column lies in the slot (tse_init)
@@ -60,18 +36,12 @@ def _worker(rank, world, port, field, ref, q):
     check_schedules_match(desc, (mm, mm), rank, dist)            # raises on any asymmetry between the ranks' slot lists
     ex = HaloExchange(desc, "cpu", dist, torch)
     assert ex(sendbuf.ctypes.data, recvbuf.ctypes.data, NLYR) == 0
-    out = f.copy()                                                # k_dss: gather in the reference's order
-    for e in range(mine.size):
-        for d in (cm.S, cm.E, cm.N, cm.W):
-            for k in range(4):
-                col = desc["getmapP"][e, d] + k
-                v = recvbuf[recv_idx[col]] if col in recv_idx else f[own[col][0], :, own[col][1]]
-                out[e, :, cm.edge_point(d, k)] += v
-        for d in (cm.SW, cm.SE, cm.NE, cm.NW):
-            col = desc["getmapP"][e, d]
-            if col >= 0:
-                v = recvbuf[recv_idx[col]] if col in recv_idx else f[own[col][0], :, own[col][1]]
-                out[e, :, cm.CORNER_POINT[d]] += v
+    out = f.copy()                                                # k_dss: gather in the reference's order (S, E, N, W, corners),
+    for e in range(mine.size):                                    # which is the order of a point's contributions in dss_tab
+        for p in range(16):
+            for (x, y) in dss_tab[e, p]:                          # local {element, point}, -1 none, <= -2 received column -(x+2)
+                if x != -1:
+                    out[e, :, p] += recvbuf[-(x + 2)] if x <= -2 else f[x, :, y]
     ok = np.array_equal(out, ref[mine])
     q.put((rank, bool(ok)))
     dist.barrier()
@@ -84,10 +54,14 @@ def test_halo_exchange_gloo(world):
     rng = np.random.default_rng(3)
     field = rng.uniform(size=(6 * NE * NE, NLYR, 16))
     ref = np.stack([cm.dss_sum(field[:, l], topo) for l in range(NLYR)], 1)
+    owner = partition(NE, world)
+    tabs = [host_tables(cm.edge_descriptors(topo, owner, r)) for r in range(world)]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = 29500 + os.getpid() % 1000 + world
-    procs = [ctx.Process(target=_worker, args=(r, world, port, field, ref, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, field, ref, tabs[r]["send_src"].copy(),
+                                               tabs[r]["dss_tab"].reshape(-1, 16, 3, 2).copy(), tabs[r]["ncol_recv"], q))
+             for r in range(world)]
     for p in procs:
         p.start()
     res = sorted(q.get(timeout=120) for _ in range(world))

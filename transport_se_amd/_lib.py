@@ -5,9 +5,11 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libtransport_se_hip.so")
-SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_kernels.h", "tse_device.h")]
-# the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own)
-UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"])]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_tables.cpp", "tse_kernels.h", "tse_device.h", "tse_layout.h",
+                                             "tse_tables.h")]
+# the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own;
+# tse_tables.cpp is host C++, which hipcc would otherwise compile as HIP)
+UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_tables.cpp", ["-x", "c++"])]
 # -fno-honor-nans: value-preserving (no reassociation, no reciprocal tricks); it only lets the compiler drop the
 # v_max_f64 x,x "canonicalize" it otherwise puts in front of every fmin/fmax operand (6 per limiter iteration)
 CFLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-honor-nans", "-fPIC"]
@@ -40,7 +42,7 @@ def _compile_units(tmp, tag, flags, verbose):
     """start the compiler on every translation unit (they run side by side); returns (objs, [(cmd, Popen)])"""
     objs, procs = [], []
     for name, extra in UNITS:
-        obj = os.path.join(tmp, tag + name.replace(".hip", ".o"))
+        obj = os.path.join(tmp, tag + os.path.splitext(name)[0] + ".o")
         cmd = ["hipcc"] + CFLAGS + extra + list(flags) + ["-c", "-o", obj, os.path.join(HERE, "csrc", name)]
         if verbose:
             print(" ".join(cmd))

@@ -23,6 +23,7 @@
 
 #include "../../include/transport_se_hip.h"
 #include "tse_kernels.h"
+#include "tse_tables.h"
 
 using namespace tse;
 
@@ -173,8 +174,10 @@ static int dalloc(T** p, size_t n) {
   HIPCHK(hipMalloc((void**)p, n * sizeof(T) > 0 ? n * sizeof(T) : sizeof(T)));
   return 0;
 }
-template <class T>
-static int upload(T** p, const std::vector<T>& h) {
+// H: the host element type, the same bytes as T (tse_tables.h: I2 is uploaded as int2)
+template <class T, class H>
+static int upload(T** p, const std::vector<H>& h) {
+  static_assert(sizeof(T) == sizeof(H) && alignof(T) >= alignof(H), "host and device element of the same layout");
   if (dalloc(p, h.size())) return 1;
   if (!h.empty()) HIPCHK(hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   return 0;
@@ -204,13 +207,6 @@ static void resolve_timers(tse_ctx* c) {
     c->free_events.push_back(p.a); c->free_events.push_back(p.b);
   }
   c->pending.clear();
-}
-
-static inline int edge_point(int d, int k) {  // d: 0 W, 1 E, 2 S, 3 N  (edge_mod.F90:407-422)
-  switch (d) { case 0: return k * 4 + 0; case 1: return k * 4 + 3; case 2: return k; default: return 12 + k; }
-}
-static inline int corner_point(int d) {  // d: 4 SW, 5 SE, 6 NW, 7 NE
-  switch (d) { case 4: return 0; case 5: return 3; case 6: return 12; default: return 15; }
 }
 
 static void gather_strided(std::vector<double>& out, const double* base, size_t stride_bytes, int n, int cnt) {
@@ -332,368 +328,25 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
     if (upload(&c->dp0, d0)) return 1;
   }
 
-  // ---- edge descriptors -> gather tables -------------------------------------------------------
-  int maxcol = 0;
-  for (int i = 0; i < n * 8; i++) { if (a->putmapP[i] + 4 > maxcol) maxcol = a->putmapP[i] + 4; if (a->getmapP[i] + 4 > maxcol) maxcol = a->getmapP[i] + 4; }
-  for (int s = 0; s < a->nsend; s++) maxcol = std::max(maxcol, a->send_ptrP[s] - 1 + a->send_lengthP[s]);
-  for (int s = 0; s < a->nrecv; s++) maxcol = std::max(maxcol, a->recv_ptrP[s] - 1 + a->recv_lengthP[s]);
-  std::vector<int> own_e(maxcol, -1), own_p(maxcol, -1), send_idx(maxcol, -1), recv_idx(maxcol, -1);
-  std::vector<int> put_start(maxcol, -1), get_start(maxcol, 0), mm_recv_idx(maxcol, -1);   // first column of an edge/corner -> element
-  for (int e = 0; e < n; e++)
-    for (int d = 0; d < 8; d++) {
-      int pm = a->putmapP[e * 8 + d];
-      if (pm < 0) continue;
-      put_start[pm] = e;
-      if (d < 4) {
-        for (int k = 0; k < 4; k++) {  // reversal is applied at pack time (edge_mod.F90:443-485)
-          int col = pm + (a->reverse[e * 8 + d] ? 3 - k : k);
-          own_e[col] = e; own_p[col] = edge_point(d, k);
-        }
-      } else { own_e[pm] = e; own_p[pm] = corner_point(d); }
-    }
-  c->ncol_send = 0;
-  for (int s = 0; s < a->nsend; s++) {
-    c->send_peer.push_back(a->send_peer[s]); c->send_len.push_back(a->send_lengthP[s]);
-    for (int i = 0; i < a->send_lengthP[s]; i++) send_idx[a->send_ptrP[s] - 1 + i] = c->ncol_send++;
-  }
-  c->ncol_recv = 0;
-  for (int s = 0; s < a->nrecv; s++) {
-    c->recv_peer.push_back(a->recv_peer[s]); c->recv_len.push_back(a->recv_lengthP[s]);
-    for (int i = 0; i < a->recv_lengthP[s]; i++) recv_idx[a->recv_ptrP[s] - 1 + i] = c->ncol_recv++;
-  }
-  // compact min/max exchange: one entry per (element, direction) pair that crosses the rank boundary.  Sender and
-  // receiver enumerate the edge/corner start columns of a slot in increasing column order, which is the same sequence
-  // on both ranks because the two slots are mirror images (the sender writes where the receiver reads).
-  for (int i = 0; i < n * 8; i++) if (a->getmapP[i] >= 0) get_start[a->getmapP[i]] = 1;
-  std::vector<int2> mm_src;
-  for (int s = 0; s < a->nsend; s++) {
-    int cnt = 0;
-    for (int i = 0; i < a->send_lengthP[s]; i++) {
-      int col = a->send_ptrP[s] - 1 + i;
-      if (put_start[col] >= 0) { mm_src.push_back(make_int2(put_start[col], 0)); cnt++; }
-    }
-    c->mm_send_len.push_back(cnt);
-  }
-  c->nmm_send = (int)mm_src.size();
-  for (int s = 0; s < a->nrecv; s++) {
-    int cnt = 0;
-    for (int i = 0; i < a->recv_lengthP[s]; i++) {
-      int col = a->recv_ptrP[s] - 1 + i;
-      if (get_start[col]) { mm_recv_idx[col] = c->nmm_recv++; cnt++; }
-    }
-    c->mm_recv_len.push_back(cnt);
-  }
-
-  std::vector<int2> send_src(c->ncol_send);
-  for (int col = 0; col < maxcol; col++)
-    if (send_idx[col] >= 0) {
-      if (own_e[col] < 0) return fail("tse_init: send column %d is written by no local element", col);
-      send_src[send_idx[col]] = make_int2(own_e[col], own_p[col]);
-    }
-  auto source_of = [&](int col, int2& s) -> int {
-    if (recv_idx[col] >= 0) { s = make_int2(-(recv_idx[col] + 2), 0); return 0; }
-    if (own_e[col] < 0) return 1;
-    s = make_int2(own_e[col], own_p[col]);
-    return 0;
-  };
-  std::vector<int2> tab((size_t)n * 48, make_int2(-1, 0));
-  std::vector<int> nbr((size_t)n * 8, -1);
-  static const int eorder[4] = {2, 1, 3, 0};  // S, E, N, W  (edge_mod.F90:685-700)
-  static const int corder[4] = {4, 5, 7, 6};  // SW, SE, NE, NW (:723-734)
-  for (int e = 0; e < n; e++) {
-    int cnt[16] = {0};
-    for (int t = 0; t < 4; t++) {
-      int d = eorder[t], gm = a->getmapP[e * 8 + d];
-      if (gm < 0) return fail("tse_init: element %d has no neighbour across edge %d", e, d);
-      for (int k = 0; k < 4; k++) {
-        int2 s;
-        if (source_of(gm + k, s)) return fail("tse_init: element %d edge %d reads column %d that nobody writes", e, d, gm + k);
-        int p = edge_point(d, k);
-        tab[((size_t)e * 16 + p) * 3 + cnt[p]++] = s;
-        if (k == 0) nbr[e * 8 + d] = s.x >= 0 ? s.x : -(mm_recv_idx[gm] + 2);  // remote: entry of the compact min/max exchange
-      }
-    }
-    for (int t = 0; t < 4; t++) {
-      int d = corder[t], gm = a->getmapP[e * 8 + d];
-      if (gm < 0) continue;
-      int2 s;
-      if (source_of(gm, s)) return fail("tse_init: element %d corner %d reads column %d that nobody writes", e, d, gm);
-      int p = corner_point(d);
-      tab[((size_t)e * 16 + p) * 3 + cnt[p]++] = s;
-      nbr[e * 8 + d] = s.x >= 0 ? s.x : -(mm_recv_idx[gm] + 2);
-    }
-  }
-  if (upload(&c->dss_tab, tab) || upload(&c->nbr, nbr) || upload(&c->send_src, send_src) || upload(&c->mm_send_src, mm_src)) return 1;
+  // ---- edge descriptors -> the tables of the kernels (tse_tables.cpp) ------------------------------
   {
-    // Walk order for the DSS kernels.  Each XCD processes a contiguous range of elements (L2 is per XCD); inside
-    // the range we follow a greedy neighbour walk over the local element graph (west/east/south/north links) in
-    // strips, so that the elements whose edge values a block gathers were touched by the same XCD a few blocks
-    // earlier instead of a whole row of the face earlier.  Pure scheduling: results do not depend on it.
-    const int S8 = (n + 7) / 8;
-    std::vector<int> order(n);
-    constexpr int W = 8;
-    for (int x = 0; x < 8; x++) {
-      const int lo = x * S8, hi = std::min(n, lo + S8);
-      if (lo >= hi) continue;
-      std::vector<char> used(hi - lo, 0);
-      int pos = lo;
-      auto in = [&](int e) { return e >= lo && e < hi && !used[e - lo]; };
-      for (int seed = lo; seed < hi; seed++) {
-        if (used[seed - lo]) continue;
-        // strip: from `seed` go east up to W elements (row segment), then continue with the northern neighbours' segment
-        int rowstart = seed;
-        while (rowstart >= 0 && in(rowstart)) {
-          int e = rowstart, cnt = 0, first = e;
-          while (e >= 0 && in(e) && cnt < W) { used[e - lo] = 1; order[pos++] = e; cnt++; int ee = nbr[e * 8 + 1]; e = ee; }
-          int nn = nbr[first * 8 + 3];   // north of the segment's first element
-          rowstart = nn;
-        }
-      }
-    }
-    if (upload(&c->order, order)) return 1;
-  }
-  {
-    // Boundary-first ordering (the reference's recv_external_indices / recv_internal_indices, cuda_mod.F90:358-401): the
-    // elements that own a column of a send slot are computed first in every stage, so that their halo travels while
-    // the remaining elements are computed.
-    std::vector<char> isb(n, 0);
-    for (const int2& s : send_src) isb[s.x] = 1;
-    for (const int2& s : mm_src) isb[s.x] = 1;
-    std::vector<int> ob, oi;
-    for (int e = 0; e < n; e++) (isb[e] ? ob : oi).push_back(e);
-    c->n_bnd = (int)ob.size(); c->n_int = (int)oi.size();
-    if (upload(&c->ord_bnd, ob) || upload(&c->ord_int, oi)) return 1;
-  }
-
-  {
-    // Patches: groups of neighbouring elements -- rows of up to 4 elements joined by their east links, up to 4 rows joined by
-    // the north link of each row's first element (no coordinates are needed and a patch may take any shape next to a cube seam or
-    // a rank boundary).  A DSS-on-read block owns one patch: what its slabs need from inside the patch travels through LDS, only
-    // the patch's halo ring comes from global memory.  Elements are taken in host order, so the patches of a full face tile it
-    // from its south-west corner.  The tiling is also the STORAGE order of the scratch fields (slot = patch * 16 + position).
-    auto ring_key = [](const int2& t) { return t.x >= 0 ? (long)t.x * 16 + t.y : -(long)(-(t.x + 2)) - 1; };
-    std::vector<char> isb(n, 0);   // elements that touch another rank
-    for (const int2& q : send_src) isb[q.x] = 1;
-    for (const int2& q : mm_src) isb[q.x] = 1;
-    // TSE_BOUNDARY_STRIPS=1: rank-boundary elements in patches of their own (below).  Off by default: on 8 ranks of ne120 it halves
-    // the first launch of a stage (25.8 -> 11.8 % of the patches) but the ragged tiling behind the band costs 3 % of a rank's
-    // step (12.6 -> 13.0 ms in the loopback rehearsal, profiles/r03_ab_boundary_bands.txt), and the first launch only matters
-    // where an exchange outlasts the interior launch -- 0.7 ms of xGMI transfer against 1.3-2.2 ms of interior work here.
+    // TSE_BOUNDARY_STRIPS=1: rank-boundary elements in patches of their own (tse_tables.cpp: Tiling::bands; off by default)
     const bool strips = getenv("TSE_BOUNDARY_STRIPS") && atoi(getenv("TSE_BOUNDARY_STRIPS")) != 0;
-    constexpr int nrmax = Patch::NRMAX;
-    std::vector<std::vector<int>> patches;
-    std::vector<int> pid(n, -1);
-    {
-      auto ring_size = [&](const std::vector<int>& cand, int me) {
-        std::vector<long> refs;
-        for (int e : cand)
-          for (int i = 0; i < 48; i++) {
-            const int2 t = tab[(size_t)e * 48 + i];
-            if (t.x == -1) continue;
-            if (t.x >= 0 && pid[t.x] == me) continue;                       // inside the candidate (marked below)
-            refs.push_back(ring_key(t));
-          }
-        std::sort(refs.begin(), refs.end());
-        return (int)(std::unique(refs.begin(), refs.end()) - refs.begin());
-      };
-      auto ering_size = [&](const std::vector<int>& cand, int me) {   // distinct elements (local or received) around the candidate
-        std::vector<long> refs;
-        for (int e : cand)
-          for (int d = 0; d < 8; d++) {
-            const int nb = nbr[e * 8 + d];
-            if (nb == -1 || (nb >= 0 && pid[nb] == me)) continue;
-            refs.push_back(nb);
-          }
-        std::sort(refs.begin(), refs.end());
-        return (int)(std::unique(refs.begin(), refs.end()) - refs.begin());
-      };
-      // Rank-boundary elements first, as patches of their own: a stage's first launch covers the patches that own a column of a
-      // send slot (split_stage), and with the regular tiling a 4 x 4 patch is such a patch as soon as one of its elements is -- a
-      // quarter of all patches on 8 ranks, for 6 % of the elements.  So up to half a patch of boundary elements is strung together
-      // along the boundary (element by element over the 8-neighbourhood), and the patch is then filled with the elements right
-      // behind them (edge neighbours of its members), as far as the halo ring and the element ring allow: a two-deep band along the
-      // rank boundary, full patches (strips of boundary elements alone left a third of the lanes empty and cost 6 % of a step),
-      // and a first launch of about twice the boundary elements' share.
-      if (strips) {
-        auto try_add = [&](std::vector<int>& cand, int me, int el) {
-          pid[el] = me; cand.push_back(el);
-          if (ring_size(cand, me) <= nrmax && ering_size(cand, me) <= NER) return true;
-          pid[el] = -1; cand.pop_back();
-          return false;
-        };
-        for (int seed = 0; seed < n; seed++) {
-          if (!isb[seed] || pid[seed] >= 0) continue;
-          const int me = (int)patches.size();
-          std::vector<int> cand{seed};
-          pid[seed] = me;
-          bool grew = true;
-          while (grew && (int)cand.size() < PS / 2) {    // the chain of boundary elements
-            grew = false;
-            for (int back = (int)cand.size() - 1; back >= 0 && !grew; back--)
-              for (int d = 0; d < 8 && !grew; d++) {
-                const int nb = nbr[cand[back] * 8 + d];
-                if (nb >= 0 && isb[nb] && pid[nb] < 0) grew = try_add(cand, me, nb);
-              }
-          }
-          grew = true;
-          while (grew && (int)cand.size() < PS) {        // the elements behind it
-            grew = false;
-            for (size_t i = 0; i < cand.size() && !grew; i++)
-              for (int d = 0; d < 4 && !grew; d++) {
-                const int nb = nbr[cand[i] * 8 + d];
-                if (nb >= 0 && pid[nb] < 0) grew = try_add(cand, me, nb);
-              }
-          }
-          patches.push_back(cand);
-        }
-      }
-      for (int seed = 0; seed < n; seed++) {
-        if (pid[seed] >= 0) continue;
-        const int me = (int)patches.size();
-        // fewer rows, then narrower rows, until the halo ring and the element ring fit the tables (one element always does)
-        for (int maxrows = 4, width = 4;; ) {
-          std::vector<int> cand;
-          int rowstart = seed;
-          for (int r = 0; r < maxrows && rowstart >= 0 && pid[rowstart] < 0; r++) {
-            int e = rowstart, cnt = 0;
-            const int first = e;
-            while (e >= 0 && pid[e] < 0 && cnt < width) { pid[e] = me; cand.push_back(e); cnt++; e = nbr[e * 8 + 1]; }   // east
-            rowstart = nbr[first * 8 + 3];                                                                             // north
-          }
-          if ((ring_size(cand, me) <= nrmax && ering_size(cand, me) <= NER) || (maxrows == 1 && width == 1)) { patches.push_back(cand); break; }
-          for (int e : cand) pid[e] = -1;
-          if (maxrows > 1) maxrows--; else width--;
-        }
-      }
-    }
-    // ---- storage
-    c->nslots = (int)patches.size() * PS;
-    std::vector<int> slot_of(n, -1);
-    for (size_t pi = 0; pi < patches.size(); pi++)
-      for (size_t i = 0; i < patches[pi].size(); i++) slot_of[patches[pi][i]] = (int)pi * PS + (int)i;
-    c->cse = (unsigned)(c->nslots + 1) * 16 + (unsigned)std::max(0, c->ncol_recv);
-    // Point order inside every slot (tse_kernels.h: ppos).  An edge of an element is READ FROM OUTSIDE when the neighbour across it
-    // belongs to another patch (that patch's halo ring) or to another rank (the pack kernel); such an edge gets a 128-byte line of
-    // its own, in the order S, N, W, E.  An edge that shares a corner point with an edge placed before it (the corner elements of a
-    // patch export two edges) brings only its remaining points into a fresh line: it then costs its reader two lines.  The points
-    // nobody reads from outside fill what is left.  Slots without an element keep round 2's fixed perimeter-first order (the A/B
-    // of that order for every slot: profiles/r03_ab_halo_ring_bound.txt).
-    std::vector<unsigned long long> pperm((size_t)c->nslots, 0x67895FEA4DCB3210ULL);
-    // lines of a slot that k_lap1<1> must store: 1 + the last line that holds a point some patch's halo ring or a
-    // send column reads -- taken from those tables themselves below, so that it covers corner-only readers and irregular patches too;
-    // the per-slot order packs the exported edges into the first lines, so this is a quarter of the field on average
-    std::vector<unsigned char> pexp((size_t)c->nslots, 0);
-    {
-      static const int edge_dir[4] = {2, 3, 0, 1};   // S, N, W, E as direction indices (west, east, south, north = 0..3)
-      for (int e = 0; e < n; e++) {
-        int pos_of[16]; bool placed[16] = {false};
-        int line = 0;
-        for (int t = 0; t < 4; t++) {
-          const int d = edge_dir[t], nb = nbr[e * 8 + d];
-          const bool outside = nb <= -2 || (nb >= 0 && pid[nb] != pid[e]);
-          if (!outside) continue;
-          int cnt = 0;
-          for (int k = 0; k < 4; k++) { const int pt = edge_point(d, k); if (!placed[pt]) { placed[pt] = true; pos_of[pt] = line * 4 + cnt++; } }
-          if (cnt) line++;
-        }
-        bool used[16] = {false};
-        for (int pt = 0; pt < 16; pt++) if (placed[pt]) used[pos_of[pt]] = true;
-        int f = 0;
-        for (int pt = 0; pt < 16; pt++) if (!placed[pt]) { while (used[f]) f++; pos_of[pt] = f; used[f] = true; }
-        unsigned long long w = 0;
-        for (int pt = 0; pt < 16; pt++) w |= (unsigned long long)pos_of[pt] << (4 * pt);
-        pperm[slot_of[e]] = w;
-      }
-    }
-    // ---- the tables of the kernels
-    {
-      PatchSet& P = c->pset;
-      const std::vector<std::vector<int>>& pt = patches;
-      P.npatch = (int)pt.size();
-      const size_t nts = (size_t)P.npatch * PS;   // table slots
-      std::vector<int> pslots(nts, -1), tslot_of(n, -1);
-      for (int pi = 0; pi < P.npatch; pi++)
-        for (size_t i = 0; i < pt[pi].size(); i++) { pslots[(size_t)pi * PS + i] = pt[pi][i]; tslot_of[pt[pi][i]] = pi * PS + (int)i; }
-      std::vector<unsigned> pring((size_t)P.npatch * nrmax, c->zero0());
-      constexpr int lds_ring = Patch::LDS_RING, lds_zero = Patch::LDS_ZERO;
-      std::vector<unsigned short> plds(nts * 48, (unsigned short)lds_zero);
-      for (int pi = 0; pi < P.npatch; pi++) {
-        std::map<long, int> ring;   // source -> ring entry
-        for (size_t i = 0; i < pt[pi].size(); i++) {
-          const int e = pt[pi][i];
-          for (int k = 0; k < 48; k++) {
-            const int2 t = tab[(size_t)e * 48 + k];
-            unsigned short ent = (unsigned short)lds_zero;
-            if (t.x >= 0 && pid[t.x] == pi) ent = (unsigned short)lds_own_entry(tslot_of[t.x] - pi * PS, t.y);
-            else if (t.x != -1) {
-              const long key = ring_key(t);
-              auto it = ring.find(key);
-              if (it == ring.end()) {
-                if ((int)ring.size() >= nrmax) return fail("tse_init: halo ring of patch %d exceeds %d entries", pi, nrmax);
-                it = ring.emplace(key, (int)ring.size()).first;
-                pring[(size_t)pi * nrmax + it->second] = t.x >= 0 ? (unsigned)slot_of[t.x] * 16 + ppos(pperm[slot_of[t.x]], t.y) : c->halo0() + (unsigned)(-(t.x + 2));
-              }
-              ent = (unsigned short)(lds_ring + it->second);
-            }
-            plds[((size_t)pi * PS + i) * 48 + k] = ent;
-          }
-        }
-      }
-      for (unsigned ent : pring)   // what the halo rings read from the slots
-        if (ent < (unsigned)c->nslots * 16) pexp[ent / 16] = std::max<unsigned char>(pexp[ent / 16], (unsigned char)((ent % 16) / 4 + 1));
-      // element ring and neighbour entries of every patch, for the bounds image of the stage-3 kernel (k_advance<2,3>)
-      std::vector<int> pering((size_t)P.npatch * NER, 0);
-      std::vector<unsigned char> pnb(nts * 8, 255);
-      for (int pi = 0; pi < P.npatch; pi++) {
-        std::map<int, int> ring;   // element (or -(received entry) - 2) -> ring entry
-        for (int r = 0; r < NER; r++) pering[(size_t)pi * NER + r] = pt[pi][0];   // unused entries: any valid element
-        for (size_t i = 0; i < pt[pi].size(); i++) {
-          const int e = pt[pi][i];
-          for (int d = 0; d < 8; d++) {
-            const int nb = nbr[e * 8 + d];
-            if (nb == -1) continue;
-            if (nb >= 0 && pid[nb] == pi) { pnb[((size_t)pi * PS + i) * 8 + d] = (unsigned char)(tslot_of[nb] - pi * PS); continue; }
-            auto it = ring.find(nb);
-            if (it == ring.end()) {
-              if ((int)ring.size() >= NER) return fail("tse_init: patch %d has more than %d elements around it", pi, NER);
-              it = ring.emplace(nb, (int)ring.size()).first;
-              pering[(size_t)pi * NER + it->second] = nb >= 0 ? nb : n + (-(nb + 2));
-            }
-            pnb[((size_t)pi * PS + i) * 8 + d] = (unsigned char)(PS + it->second);
-          }
-        }
-      }
-      // rank-boundary patches first, as the elements above
-      std::vector<int> pb, pin;
-      for (int pi = 0; pi < P.npatch; pi++) {
-        bool b = false;
-        for (int e : pt[pi]) b = b || isb[e];
-        (b ? pb : pin).push_back(pi);
-      }
-      P.np_bnd = (int)pb.size(); P.np_int = (int)pin.size();
-      if (upload(&P.pslots, pslots) || upload(&P.pring, pring) || upload(&P.plds, plds) || upload(&P.pering, pering) || upload(&P.pnb, pnb) ||
-          upload(&P.plist_bnd, pb) || upload(&P.plist_int, pin)) return 1;
-    }
-    std::vector<int2> send_s(send_src);
-    for (int2& t : send_s) { t.x = slot_of[t.x]; t.y = ppos(pperm[t.x], t.y); }   // {slot, position within the slot}
-    for (const int2& t : send_s) pexp[t.x] = std::max<unsigned char>(pexp[t.x], (unsigned char)(t.y / 4 + 1));   // what the pack kernel reads
-    if (upload(&c->slot_of, slot_of) || upload(&c->send_src_s, send_s) || upload(&c->pperm, pperm) || upload(&c->pexp, pexp)) return 1;
-    // the same contributions per ELEMENT as global entries of a chunk, for the remap that assembles the last DSS of a cycle on read
-    std::vector<unsigned> etab((size_t)n * 48);
-    for (size_t i = 0; i < etab.size(); i++) {
-      const int2 t = tab[i];
-      etab[i] = t.x >= 0 ? (unsigned)slot_of[t.x] * 16 + ppos(pperm[slot_of[t.x]], t.y) : t.x == -1 ? c->zero0() : c->halo0() + (unsigned)(-(t.x + 2));
-    }
-    if (upload(&c->etab, etab)) return 1;
-    // the remap's block lists: all / rank-boundary / interior elements in slot order (patch by patch)
-    {
-      std::vector<int> by_slot(n);
-      for (int e = 0; e < n; e++) by_slot[e] = e;
-      std::sort(by_slot.begin(), by_slot.end(), [&](int x, int y) { return slot_of[x] < slot_of[y]; });
-      std::vector<int> rb, ri;
-      for (int e : by_slot) (isb[e] ? rb : ri).push_back(e);
-      if (upload(&c->rl_all, by_slot) || upload(&c->rl_bnd, rb) || upload(&c->rl_int, ri)) return 1;
-    }
+    HostTables t;
+    std::string err;
+    if (build_tables(*a, strips, &t, &err)) return fail("%s", err.c_str());
+    c->ncol_send = t.ncol_send; c->ncol_recv = t.ncol_recv; c->nmm_send = t.nmm_send; c->nmm_recv = t.nmm_recv;
+    c->send_peer = t.send_peer; c->recv_peer = t.recv_peer; c->send_len = t.send_len; c->recv_len = t.recv_len;
+    c->mm_send_len = t.mm_send_len; c->mm_recv_len = t.mm_recv_len;
+    c->n_bnd = t.n_bnd; c->n_int = t.n_int; c->nslots = t.nslots; c->cse = t.cse;
+    PatchSet& P = c->pset;
+    P.npatch = t.npatch; P.np_bnd = t.np_bnd; P.np_int = t.np_int;
+    if (upload(&c->dss_tab, t.dss_tab) || upload(&c->nbr, t.nbr) || upload(&c->send_src, t.send_src) || upload(&c->mm_send_src, t.mm_send_src) ||
+        upload(&c->order, t.order) || upload(&c->ord_bnd, t.ord_bnd) || upload(&c->ord_int, t.ord_int) ||
+        upload(&P.pslots, t.pslots) || upload(&P.pring, t.pring) || upload(&P.plds, t.plds) || upload(&P.pering, t.pering) || upload(&P.pnb, t.pnb) ||
+        upload(&P.plist_bnd, t.plist_bnd) || upload(&P.plist_int, t.plist_int) ||
+        upload(&c->slot_of, t.slot_of) || upload(&c->send_src_s, t.send_src_s) || upload(&c->pperm, t.pperm) || upload(&c->pexp, t.pexp) ||
+        upload(&c->etab, t.etab) || upload(&c->rl_all, t.rl_all) || upload(&c->rl_bnd, t.rl_bnd) || upload(&c->rl_int, t.rl_int)) return 1;
   }
 
   // ---- state -------------------------------------------------------------------------------------
@@ -1836,6 +1489,42 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   if (nbytes) *nbytes = 0;
   return nullptr;
 }
+#ifdef TSE_AB_HOOKS
+// The host tables of tse_init without a device, for the CPU tests (tests/test_tables_cpu.py): tse_test_tables builds them into *h
+// (strips: as TSE_BOUNDARY_STRIPS), tse_test_table hands one out by name -- the vectors of HostTables, and "counts": ncol_send,
+// ncol_recv, nmm_send, nmm_recv, nslots, cse, n_bnd, n_int, npatch, np_bnd, np_int, zero0, halo0 as ints.
+struct TseTestTables { HostTables t; std::vector<int> counts; };
+extern "C" int tse_test_tables(const tse_init_args* a, int strips, void** h) {
+  if (!a || !h) return fail("tse_test_tables: null argument");
+  *h = nullptr;
+  TseTestTables* r = new TseTestTables();
+  std::string err;
+  if (build_tables(*a, strips != 0, &r->t, &err)) { delete r; return fail("%s", err.c_str()); }
+  const HostTables& t = r->t;
+  r->counts = {t.ncol_send, t.ncol_recv, t.nmm_send, t.nmm_recv, t.nslots, (int)t.cse, t.n_bnd, t.n_int, t.npatch, t.np_bnd, t.np_int,
+               (int)t.zero0(), (int)t.halo0()};
+  *h = r;
+  return 0;
+}
+extern "C" int tse_test_table(void* h, const char* name, const void** data, size_t* nbytes) {
+  struct Ent { const char* n; const void* p; size_t b; };
+  if (!h || !name) return fail("tse_test_table: null argument");
+  const TseTestTables& r = *(const TseTestTables*)h;
+  const HostTables& t = r.t;
+  auto ent = [](const char* n, const auto& v) { return Ent{n, v.data(), v.size() * sizeof(v[0])}; };
+  const Ent ents[] = {ent("counts", r.counts), ent("send_peer", t.send_peer), ent("recv_peer", t.recv_peer), ent("send_len", t.send_len),
+                      ent("recv_len", t.recv_len), ent("mm_send_len", t.mm_send_len), ent("mm_recv_len", t.mm_recv_len), ent("send_src", t.send_src),
+                      ent("mm_send_src", t.mm_send_src), ent("dss_tab", t.dss_tab), ent("nbr", t.nbr), ent("order", t.order), ent("ord_bnd", t.ord_bnd),
+                      ent("ord_int", t.ord_int), ent("slot_of", t.slot_of), ent("pperm", t.pperm), ent("pexp", t.pexp), ent("send_src_s", t.send_src_s),
+                      ent("etab", t.etab), ent("rl_all", t.rl_all), ent("rl_bnd", t.rl_bnd), ent("rl_int", t.rl_int), ent("pslots", t.pslots),
+                      ent("pring", t.pring), ent("plds", t.plds), ent("pering", t.pering), ent("pnb", t.pnb), ent("plist_bnd", t.plist_bnd),
+                      ent("plist_int", t.plist_int)};
+  for (const Ent& e : ents)
+    if (!strcmp(e.n, name)) { if (data) *data = e.p; if (nbytes) *nbytes = e.b; return 0; }
+  return fail("tse_test_table: no table named %s", name);
+}
+extern "C" void tse_test_tables_free(void* h) { delete (TseTestTables*)h; }
+#endif
 int tse_timing(tse_ctx* c, int enable) { resolve_timers(c); c->timing = enable != 0; c->timers.clear(); return 0; }
 int tse_kernel_time(tse_ctx* c, const char* name, double* ms, long* launches) {
   resolve_timers(c);

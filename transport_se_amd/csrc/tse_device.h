@@ -7,10 +7,7 @@
 // 16-point reductions of the limiter are quad_perm DPP moves (no LDS, no ds_bpermute): two-stage butterflies over the quad.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#define NP 4
-#define NLEV 72
-#define NLEVP 73
+#include "tse_layout.h"   // NP, NLEV, NLEVP and the layout constants the table builder shares
 
 namespace tse {
 

@@ -4,7 +4,7 @@
 //   tracer fields  Qdp[tl][e][q][k][p]
 //   pre-DSS scratch T, B: tracer-major planes; inside a plane the 72 levels are cut into NCHUNK chunks of CL = 4 levels and
 //                  a chunk holds, level fastest, T[q][kc][slot][pos(p)][kk] (points perimeter first): the element slots (elements regrouped into
-//                  patches of <= 16 neighbouring elements, tse_api.hip), then one all-zero slot (target of empty DSS
+//                  patches of <= 16 neighbouring elements, tse_tables.cpp), then one all-zero slot (target of empty DSS
 //                  contributions), then the received halo columns [col][kk].  Plane stride `tps` doubles, `cse` entries
 //                  (points / halo columns) per chunk.  A plane is < 4 GB, so the DSS-on-read kernels address it with one
 //                  uniform base + 32-bit byte offsets.
@@ -25,44 +25,7 @@ namespace tse {
 // 72-level element is 4.5 waves, so element-sized blocks idle 10% of their lanes and -- worse -- come in units of 5 waves,
 // which leaves SIMD wave slots empty whenever the register budget allows 2 or 3 waves per SIMD (8 or 12 per CU).
 constexpr int FLAT_THREADS = 256;
-// Scratch layout: CL levels per chunk.  The DSS-on-read kernels work on blocks of (patch of 16 element slots) x (one chunk):
-// 16 slots x 4 levels x 4 rows = 256 lanes, and a slot's 16 points x 4 levels are 512 contiguous bytes.
-constexpr int CL = 4;
-constexpr int NCHUNK = NLEV / CL;
-static_assert(NLEV % CL == 0 && CL % 2 == 0, "chunks hold whole level pairs");
-constexpr int PS = 16;        // element slots per patch (4 x 4 elements): slot = patch * PS + position
-// Block shape of the DSS-on-read kernels: a block owns a patch of PS element slots, 256 lanes; its tables (PatchSet, tse_api.hip)
-// name the storage slot of every element and of every halo-ring entry.  (Wider blocks of 6 x 4 and 8 x 4 elements have a shorter
-// ring per element but cost occupancy: 3.4 and 8.5 ms per step more, same bits -- profiles/r03_ab_patch_shapes.txt; retired.)
-struct Patch {
-  static constexpr int THREADS = PS * 16;
-  // halo-ring entries (distinct (element, point) pairs outside the patch: 68 for a full patch; tse_api.hip gives a patch fewer
-  // rows if its ring would not fit); lanes 2r, 2r+1 load entry r
-  static constexpr int NRMAX = 96;
-  // Entries of one LDS buffer (an entry = the CL levels of a point = 32 bytes = 8 of the 64 banks): the own points, the ring, one all-zero
-  // entry.  The own points are SKEWED (lds_own_entry): a slot takes LDS_SLOT = 20 entries instead of 16, and point (j, i) of a slot sits at
-  // position 4j + ((i + j) & 3).  A wave reads, in one ds_read_b64, the same edge of four slots (its rows' neighbour values): in the
-  // natural order an east or west edge is points 3,7,11,15 / 0,4,8,12 -- two bank groups -- and the four slots, 512 bytes apart, fall on
-  // the same two: 8 cycles for the 2 the 512 bytes need.  Skewed, the four points of any edge are in four different groups and slots
-  // s, s+1 in complementary halves of the banks: 2 cycles.  (SQ_LDS_BANK_CONFLICT: more than half of the LDS cycles of the four
-  // gathering kernels before; profiles/r03_ab_lds_skew.txt.)
-  static constexpr int LDS_SLOT = 20;
-  static constexpr int LDS_RING = PS * LDS_SLOT, LDS_ZERO = LDS_RING + NRMAX, LDS_ENT = LDS_ZERO + 1;
-  static_assert(2 * NRMAX <= THREADS, "one 16-byte ring load per lane");
-};
-__host__ __device__ inline int lds_own_entry(int sl, int p) { return sl * Patch::LDS_SLOT + (p & ~3) + (((p & 3) + (p >> 2)) & 3); }
 struct Scr { size_t tps; unsigned cse; };   // plane stride (doubles), entries per chunk
-// Inside a slot the 16 points are stored in a PER-SLOT order (nibble p of the slot's 64-bit word pperm[slot] = position of
-// point p).  The memory system moves whole 128-byte lines (tools/fetch_probe.hip: 32 bytes out of every line cost what the
-// line costs), a position holds the CL = 4 levels of a point = 32 bytes, so a slot is four lines of four points -- and what a
-// neighbouring patch's halo ring reads from a slot is one EDGE of the element (4 points).  tse_init gives every edge that
-// some patch or neighbour rank reads a line of its own (slot_perm, tse_api.hip), so a ring edge is one line instead of the
-// two that three of the four edges straddled with one fixed perimeter-first order.
-__host__ __device__ __forceinline__ int ppos(unsigned long long perm, int p) { return (int)((perm >> (4 * p)) & 15ull); }
-// qmin/qmax(k,q,e) of prim_advection_mod (:459) in the device layout [e][k / CL][q][k % CL]
-// (the tracer count of the bounds layout is rounded up to a multiple of 4: the 4 levels of 4 consecutive tracers are one aligned
-// 128-byte line, so that the kernels that emit bounds can write whole lines)
-__host__ __device__ __forceinline__ int mm_qpad(int qsize) { return (qsize + 3) & ~3; }
 __device__ __forceinline__ size_t mm_idx(int e, int q, int k, int qsize) { return (((size_t)e * NCHUNK + k / CL) * mm_qpad(qsize) + q) * CL + (k % CL); }
 // Blocks are dealt round-robin to the 8 XCDs, so logical block = (blockIdx % 8) * (gridDim/8) + blockIdx / 8 gives every
 // XCD a contiguous range of slabs (and the ranges coincide with the element ranges the DSS kernels walk per XCD).
@@ -362,9 +325,7 @@ __global__ __launch_bounds__(WB * 64) void k_nbr_minmax_patch(int npatch, int qs
 //
 // plist/npwork: the patches this launch walks (nullptr: patches 0..npwork).  A multi-rank step launches every slab kernel
 // twice: first over the patches (plain kernels: elements, order/nwork) that touch another rank, so that their halo can travel
-// while the second launch computes the interior (tse_api.hip).
-constexpr int NER = 48;            // elements around a patch whose bounds the stage-3 kernel reads (a full patch: 20; a two-deep band
-                                   // along a rank boundary: every received (element, direction) pair is an entry of its own, about 40)
+// while the second launch computes the interior (the patch lists: tse_tables.cpp; the two launches: split_stage, tse_api.hip).
 struct GatherArgs {
   Scr S;
   const int* slot_of;              // element -> slot of the scratch layout
@@ -559,7 +520,7 @@ __device__ __forceinline__ void gather_var_plane(RowGather& R, PatchLds& L, cons
 // stores shared with the lane that holds the other level of the pair (even level: points 0,2 for both levels; odd: 1,3),
 // instead of four 8-byte stores.  All lanes must call it (the swizzle needs both lanes of a pair); `live` gates the stores.
 struct RowStore { unsigned o0, o1; bool s0, s1; };   // plane-relative offsets (doubles) of the lane's two stores, and whether each is made
-// pexp (k_lap1<1> only): lines of the slot that hold points some other patch or rank reads (tse_api.hip: slot_perm puts every exported
+// pexp (k_lap1<1> only): lines of the slot that hold points some other patch or rank reads (tse_tables.cpp: slot_point_order puts every exported
 // edge into the slot's first lines); the store of a point beyond them is dropped -- nobody reads the first Laplacian of such a point
 // from memory (k_advance<2,3> forms the Laplacian of its own slots itself), so k_lap1 writes a quarter of the field instead of all of it
 __device__ __forceinline__ RowStore row_store_setup(Scr S, const unsigned long long* __restrict__ pperm, int slot, int j, int k,
@@ -992,7 +953,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
 // Each element adds its neighbours' values in the reference's fixed order (all S, E, N, W, then SW, SE, NE, NW),
 // so results do not depend on how elements are distributed over GPUs.
 //   tab[e][16][3] = {source element (>=0 local, -1 none, <=-2 remote column -(v+2)), source point}  (level fields; the tracer
-//   kernels use the patch tables derived from it: tse_api.hip)
+//   kernels use the patch tables derived from it: tse_tables.cpp)
 // Tracer-field DSS (k_dss_patch): source in the scratch layout written by k_advance/k_lap1, destination in the standard
 // layout dst[e][q][k][p].
 // MODE 0: dst = rspheremp * DSS(src)                                   (prim_advection_mod.F90:929-960)
