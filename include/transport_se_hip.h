@@ -16,7 +16,9 @@
  * Conventions
  *   - All functions return 0 on success, nonzero on error (the Fortran side then calls abortmp, as the
  *     reference does on every failure: parallel_mod.F90:274-287); tse_last_error() gives the message.
- *   - np = 4, nlev = 72 are compile-time constants exactly as in the reference (dimensions_mod.F90:19,27).
+ *   - np = 4 and nlev are compile-time constants exactly as in the reference (dimensions_mod.F90:19,27).  nlev is a build
+ *     setting of the library (-DNLEV=<n>; the multiples of 8 from 16 to 72 compile, 72 and 64 are tested): TSE_NLEV below is the DEFAULT build's value
+ *     (72, libtransport_se_hip.so), and a host must compare tse_nlev() with its own nlev before it passes any field.
  *   - Host arrays are passed as the address of element 1's field plus the byte stride between consecutive
  *     elements (element_t is a fixed-size derived type, element_mod.F90:112-221, so `elem(:)` is strided AoS);
  *     inside one element the reference's own memory order is assumed (i fastest, then j, k, q, time level).
@@ -36,7 +38,7 @@ extern "C" {
 #endif
 
 #define TSE_NP 4
-#define TSE_NLEV 72
+#define TSE_NLEV 72   /* the default build; the library a host loads reports its own with tse_nlev() */
 #define TSE_NLEVP 73
 
 typedef struct tse_ctx tse_ctx;
@@ -87,6 +89,8 @@ typedef struct {
 int  tse_init(tse_ctx **ctx, const tse_init_args *args);
 void tse_finalize(tse_ctx *ctx);
 const char *tse_last_error(void);
+/* the level count (nlev) this library was built for; needs no context.  Every level extent of this interface is this value. */
+int tse_nlev(void);
 int  tse_synchronize(tse_ctx *ctx);
 
 /* ---- bndry_exchangeV inside the library: RCCL neighbour send/recv over xGMI (bndry_mod.F90:74-124) ----

@@ -1,4 +1,7 @@
-"""Loader/builder of libtransport_se_hip.so (in-tree; built by __graft_entry__.build())."""
+"""Loader/builder of libtransport_se_hip.so (in-tree; built by __graft_entry__.build()).
+
+The level count is a build-time setting of the library, as PLEV is of the reference: the default build (NLEV = 72) is
+libtransport_se_hip.so, a build for another level count n is libtransport_se_hip_L<n>.so (build(nlev=n), lib(nlev=n))."""
 import ctypes as C
 import os
 import subprocess
@@ -36,6 +39,15 @@ class InitArgs(C.Structure):
 
 HOOKS_SO = os.path.join(HERE, "libtransport_se_hip_hooks.so")
 HOOKS_FLAGS = ["-DTSE_AB_HOOKS"]
+DEFAULT_NLEV = 72   # the level count of the default build (csrc/tse_layout.h; TSE_NLEV of the header)
+NLEV_BUILDS = (64,)   # the other level counts __graft_entry__.build() ships
+
+
+def so_path(nlev=None):
+    """the product library built for `nlev` levels (None: the default build)"""
+    if nlev is None or nlev == DEFAULT_NLEV:
+        return SO
+    return os.path.join(HERE, "libtransport_se_hip_L%d.so" % int(nlev))
 
 
 def _compile_units(tmp, tag, flags, verbose):
@@ -73,12 +85,22 @@ def _stale(so):
     return not (os.path.exists(so) and os.path.getmtime(so) >= newest)
 
 
-def build(force=False, verbose=False, out=None, flags=(), hooks=True):
+def build(force=False, verbose=False, out=None, flags=(), hooks=True, nlev=None):
     """hipcc --offload-arch=gfx950 (cross-compiles without a GPU).  Builds the product library and, with hooks=True, its twin with
     -DTSE_AB_HOOKS (libtransport_se_hip_hooks.so: the A/B switches and the fault injection the tests use -- none of which the
     product library contains); all translation units compile side by side.
+    nlev: the product library for another level count instead (-DNLEV=<nlev>, so_path(nlev); no hooks twin).  The kernels'
+    static_asserts refuse a level count they cannot serve at compile time.
     out/flags: one A/B variant of the same sources instead (tools/ab_build.sh; always with the hooks)."""
     import tempfile
+    if nlev is not None and nlev != DEFAULT_NLEV:
+        so = so_path(nlev)
+        if force or _stale(so):
+            with tempfile.TemporaryDirectory() as tmp:
+                objs, procs = _compile_units(tmp, "L%d_" % nlev, ["-DNLEV=%d" % nlev], verbose)
+                _finish(procs)
+                _link(so, objs, verbose)
+        return so
     if out is not None:
         with tempfile.TemporaryDirectory() as tmp:
             objs, procs = _compile_units(tmp, "ab_", HOOKS_FLAGS + list(flags), verbose)
@@ -108,7 +130,7 @@ def source_hash():
 _libs = {}
 
 # every symbol include/transport_se_hip.h declares
-SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_synchronize", "tse_copy_qdp_h2d", "tse_copy_qdp_d2h",
+SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchronize", "tse_copy_qdp_h2d", "tse_copy_qdp_d2h",
            "tse_set_derived", "tse_set_divdp", "tse_get_derived", "tse_advec_tracers_remap_rk2", "tse_compute_divdp", "tse_euler_step",
            "tse_qdp_time_avg", "tse_vertical_remap", "tse_get_qminmax", "tse_dcmip_init", "tse_dcmip_set_initial",
            "tse_dcmip_step_inputs", "tse_prim_run_subcycle", "tse_device_ptr", "tse_kernel_time", "tse_timing",
@@ -118,12 +140,19 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_synchronize", "tse
 COMM_ID_BYTES = 128
 
 
-def lib(path=None):
+def lib(path=None, nlev=None):
     """Load the HIP library; raises (never falls back) if it has not been built.  path (or TSE_LIB): another build of the SAME
-    sources -- the -DTSE_AB_HOOKS twin (HOOKS_SO: fault injection for the tests, A/B switches) or a tools/ab variant -- never a fallback."""
-    path = path or os.environ.get("TSE_LIB", SO)
+    sources -- the -DTSE_AB_HOOKS twin (HOOKS_SO: fault injection for the tests, A/B switches) or a tools/ab variant -- never a fallback.
+    nlev: the library must be built for this level count (checked with tse_nlev()); a level count other than the default's loads
+    so_path(nlev) unless a path is given (TSE_LIB names a default-level build and is not used for it)."""
+    if nlev is not None and nlev != DEFAULT_NLEV:
+        path = path or so_path(nlev)
+    else:
+        path = path or os.environ.get("TSE_LIB", SO)
     if path in _libs:
-        return _libs[path]
+        L = _libs[path]
+        _check_nlev(L, path, nlev)
+        return L
     if not os.path.exists(path):
         raise RuntimeError("%s is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(there is no CPU fallback for the product path)" % os.path.basename(path))
@@ -142,6 +171,7 @@ def lib(path=None):
     L.tse_init.argtypes = [C.POINTER(vp), C.POINTER(InitArgs)]
     L.tse_finalize.argtypes = [vp]; L.tse_finalize.restype = None
     L.tse_last_error.restype = C.c_char_p
+    L.tse_nlev.argtypes = []
     L.tse_synchronize.argtypes = [vp]
     L.tse_copy_qdp_h2d.argtypes = [vp, vp, sz, i, i]
     L.tse_copy_qdp_d2h.argtypes = [vp, vp, sz, i, i]
@@ -183,4 +213,10 @@ def lib(path=None):
     L.tse_copy_q_d2h.argtypes = [vp, vp, sz, i]
     L.tse_copy_lnps_d2h.argtypes = [vp, vp, sz]
     _libs[path] = L
+    _check_nlev(L, path, nlev)
     return L
+
+
+def _check_nlev(L, path, nlev):
+    if nlev is not None and L.tse_nlev() != nlev:
+        raise RuntimeError("%s is built for nlev = %d, not %d" % (os.path.basename(path), L.tse_nlev(), nlev))

@@ -143,7 +143,7 @@ struct tse_ctx {
   struct Pending { const char* name; hipEvent_t a, b; };
   std::vector<Pending> pending;       // event pairs recorded on `stream`, resolved lazily (no sync inside the step)
   std::vector<hipEvent_t> free_events;
-  double *sink = nullptr;   // write-only dump of k_remap (run-in levels of its segment tasks, surplus tracer slots): 16 columns x 72 levels, then two bounds areas
+  double *sink = nullptr;   // write-only dump of k_remap (run-in levels of its segment tasks, surplus tracer slots): 16 columns x NLEV levels, then two bounds areas
   double *eta2 = nullptr;   // with lvl_tmp: twin buffers of the level fields (k_dss_lvl writes out of place, then swap)
   bool t_zero_dirty = false;   // the per-stage stage-3 path used T as a plain [e][q][k][p] field (overwrites its zero elements)
   size_t tps = 0;   // plane stride (doubles) of the scratch fields T and B: NCHUNK chunks of (slots, a zero slot, the halo columns)
@@ -164,6 +164,7 @@ struct tse_ctx {
 };
 
 const char* tse_last_error(void) { return g_err; }
+int tse_nlev(void) { return NLEV; }
 
 // the element bounds of Qdp(tl)/dp now sit in qmin2/qmax2 (tl = 0: nothing cached); any halo of older bounds is stale.  Every entry that
 // changes Qdp or ps_v passes here, so the Q / lnps of tse_state_q go stale here too.
@@ -1323,7 +1324,7 @@ int tse_element_mass(tse_ctx* c, int nt, double* out) {
   const size_t n = (size_t)c->nelemd * c->qsize;
   double* d = nullptr;
   if (dalloc(&d, n)) return 1;
-  hipLaunchKernelGGL(k_elem_mass<>, dim3((unsigned)n), dim3(128), 0, c->stream, c->qsize, (const double*)(c->q(nt)),
+  hipLaunchKernelGGL(k_elem_mass<>, dim3((unsigned)n), dim3(ELEM_MASS_THREADS), 0, c->stream, c->qsize, (const double*)(c->q(nt)),
                      (const double*)c->spheremp, d);
   int rc = 0;
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d, n * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -1395,7 +1396,7 @@ int tse_dcmip_init(tse_ctx* c, int test, const double* lat, const double* lon, c
   c->lat = c->lon = c->zm = c->zi = c->pint = c->dph = nullptr;
   if (upload(&c->lat, la) || upload(&c->lon, lo) || upload(&c->zm, zm) || upload(&c->zi, zi) || upload(&c->pint, pint) || upload(&c->dph, dph)) return 1;
   if (!c->dcmip_tab && dalloc(&c->dcmip_tab, 1)) return 1;
-  hipLaunchKernelGGL(k_dcmip_tables<>, dim3(1), dim3(128), 0, c->stream, test, c->zm, c->zi, c->dcmip_tab);   // level-only factors
+  hipLaunchKernelGGL(k_dcmip_tables<>, dim3(1), dim3(DCMIP_TAB_THREADS), 0, c->stream, test, c->zm, c->zi, c->dcmip_tab);   // level-only factors
   LAUNCH_CHECK();
   return 0;
 }

@@ -2,13 +2,13 @@
 //
 // HBM layout (all fp64, point index p = j*4+i fastest):
 //   tracer fields  Qdp[tl][e][q][k][p]
-//   pre-DSS scratch T, B: tracer-major planes; inside a plane the 72 levels are cut into NCHUNK chunks of CL = 4 levels and
+//   pre-DSS scratch T, B: tracer-major planes; inside a plane the NLEV levels are cut into NCHUNK chunks of CL = 4 levels and
 //                  a chunk holds, level fastest, T[q][kc][slot][pos(p)][kk] (points perimeter first): the element slots (elements regrouped into
 //                  patches of <= 16 neighbouring elements, tse_tables.cpp), then one all-zero slot (target of empty DSS
 //                  contributions), then the received halo columns [col][kk].  Plane stride `tps` doubles, `cse` entries
 //                  (points / halo columns) per chunk.  A plane is < 4 GB, so the DSS-on-read kernels address it with one
 //                  uniform base + 32-bit byte offsets.
-//   level fields   dp, divdp, divdp_proj, omega_p, dp3d [e][k][p]; vn0[e][k][c][p]; eta_dot_dpdn[e][73][p]
+//   level fields   dp, divdp, divdp_proj, omega_p, dp3d [e][k][p]; vn0[e][k][c][p]; eta_dot_dpdn[e][NLEVP][p]
 //   bounds         qmin/qmax[e][kc][q (rounded up to a multiple of 4)][kk] (mm_idx): the 4 levels of a chunk fastest, then the tracer, so that the 32 bytes a
 //                  (patch x chunk) block needs per element and tracer share their line with the next three tracers
 //   metric         Dinv[e][p][4], metdet/rmetdet/spheremp/rspheremp[e][p]
@@ -95,10 +95,12 @@ __global__ __launch_bounds__(256) void k_elem_op(int nelemd, Dvv_t D, GeoPtrs G,
 
 // Per-element tracer mass sum_k sum_p spheremp(p) * Qdp(p,k,q) -- the element's share of global_integral behind the "Q, Q diss"
 // diagnostics (global_norms_mod.F90:39-86, prim_state_mod.F90:352-385) -- in a FIXED order (points 0..15 inside a level, then
-// levels 0..71), so that an element's partial does not depend on which rank or block computed it; the cross-element sum is
+// levels 0..NLEV-1), so that an element's partial does not depend on which rank or block computed it; the cross-element sum is
 // done by the caller with an exact (order-independent) summation.  block = (element, tracer), thread = level.
+constexpr int ELEM_MASS_THREADS = 128;   // k_elem_mass: one thread per level
+static_assert(NLEV <= ELEM_MASS_THREADS, "k_elem_mass: one thread per level: NLEV <= 128");
 template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
-__global__ __launch_bounds__(128) void k_elem_mass(int qsize, const double* __restrict__ Q, const double* __restrict__ spheremp, double* __restrict__ out) {
+__global__ __launch_bounds__(ELEM_MASS_THREADS) void k_elem_mass(int qsize, const double* __restrict__ Q, const double* __restrict__ spheremp, double* __restrict__ out) {
   __shared__ double lev[NLEV];
   const int e = blockIdx.x / qsize, q = blockIdx.x - e * qsize, k = threadIdx.x;
   if (k < NLEV) {
@@ -1056,7 +1058,8 @@ __global__ __launch_bounds__(Patch::THREADS) void k_dss_patch(int qsize, const d
 // (prim_advection_mod.F90:911-919,943-957), out of place (the neighbours read src).  src/dst carry src_lev/dst_lev levels per
 // element (eta_dot_dpdn: nlev+1; the extra level is copied through), so no staging copies are needed and the caller just
 // swaps the two buffers.  Lanes flattened over (element slot, level pair, row); all gathers issued before any use.
-constexpr int LVL_UNITS = (NLEV / 2) * 4;   // lanes per element: 36 level pairs (k, k+36) x 4 rows
+constexpr int LVL_UNITS = (NLEV / 2) * 4;   // lanes per element: NLEV/2 level pairs (k, k+NLEV/2) x 4 rows (72 levels: 144 lanes, 64: 128)
+static_assert(NLEV % 2 == 0, "k_dss_lvl: a lane does the level pair (k, k + NLEV/2): NLEV must be even");
 template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
 __global__ __launch_bounds__(DSS_FLAT_THREADS) void k_dss_lvl(int nelemd, const int2* __restrict__ tab, const double* __restrict__ rspheremp,
                                                               const double* __restrict__ spheremp, const double* __restrict__ src, int src_lev,
@@ -1191,7 +1194,8 @@ __global__ void k_time_avg(size_t n, int rkstage, const double* __restrict__ Qn0
 // issue of the column loop (two waves per SIMD in both forms), not by the phases following one another.
 constexpr int REMAP_THREADS = 256;   // 4 waves: one per SIMD and element
 constexpr int REMAP_PF = 8;   // column loads kept in flight per thread = levels per unrolled block = levels per segment task
-static_assert(NLEV % REMAP_PF == 0, "whole blocks");
+static_assert(NLEV % REMAP_PF == 0, "whole blocks: NLEV must be a multiple of 8 (REMAP_PF)");
+static_assert(NLEV >= 2 * REMAP_PF, "the first block's prefetch and one segment task after it: NLEV >= 16");
 static_assert(REMAP_PF % CL == 0, "a block of REMAP_PF levels holds whole chunks of the bounds layout");
 constexpr int REMAP_SEG_MAX = 3;   // at most this many tracers of an element go through segment tasks (LDS for their mass prefixes)
 // tracers left over after whole rounds of `slots` tracer slots; more than REMAP_SEG_MAX of them take one more (partly idle) round
@@ -1214,7 +1218,9 @@ struct RemapLds {
   __device__ double* dB() { return &ca[0][0][0] + NLEV; }                                     // hybi(k+1)-hybi(k)
 };
 static_assert(2 * NLEV <= (NLEV + 1) * 3 * 16, "phase-1 scratch fits the coefficient arrays");
-static_assert(2 * sizeof(RemapLds) <= 160 * 1024, "two elements per CU");
+static_assert(2 * sizeof(RemapLds) <= 160 * 1024, "two elements per CU (160 KB of LDS): NLEV <= 72");
+static_assert(NLEV <= REMAP_THREADS, "one thread per level forms the hybrid-coefficient differences: NLEV <= 256");
+static_assert(NLEV + 1 <= 255, "kid(k) is a byte: NLEV <= 254");
 // The column arithmetic below is compiled WITHOUT implicit FMA contraction and spells its fused operations out: what the
 // compiler fuses on its own depends on which multiplies it happens to see in the same basic block -- in an unrolled block of
 // levels the product a = m/dp of the previous level, across a block boundary not -- so the rounding of a level would depend
@@ -1782,8 +1788,8 @@ __global__ __launch_bounds__(REMAP_THREADS / NT, NT == 1 ? 2 : 1 /* <= 256 regis
     // pressure pio(nlev+1) (:142-144: the same terms added in the same order from 0), so it is not summed a second time; the
     // hybrid coefficient differences of the target grid (:1316-1317) wait in LDS instead of behind one scalar load per level.
     const int p = tid;
-    constexpr int SB = 12;
-    static_assert(NLEV % SB == 0, "scan batches");
+    constexpr int SB = NLEV % 16 == 0 ? 16 : NLEV % 12 == 0 ? 12 : 8;   // 12 at 72 levels, 16 at 64
+    static_assert(NLEV % SB == 0, "scan batches: NLEV must be a multiple of 8");
     double run = 0.0;
     pio[0][p] = 0.0;
     for (int kb = 0; kb < NLEV; kb += SB) {
@@ -1957,13 +1963,15 @@ __device__ inline DcmipPt dcmip_point(int test, double time, double lon, double 
 }
 
 // per-step inputs: derived%dp, vn0 = u(t_wind)*dp, eta_dot_dpdn(t_now), omega_p = 0
-// zm[72], zi[73], pint[73] are per-level constants prepared on the host (dcmip_wrapper_mod.F90:68-89,183).
+// zm[NLEV], zi[NLEVP], pint[NLEVP] are per-level constants prepared on the host (dcmip_wrapper_mod.F90:68-89,183).
 // The prescribed fields factor into (level-only) x (column-only) x (time-only) terms; evaluating dcmip_point per grid point
-// spends ~15 transcendental calls on every one of the 73 levels of a column.  k_dcmip_tables evaluates the level-only
+// spends ~15 transcendental calls on every one of the NLEVP levels of a column.  k_dcmip_tables evaluates the level-only
 // factors once (same device libm, same expression trees as dcmip_point, cut exactly where the left-to-right product order
 // allows it, so the values are identical), k_dcmip_step evaluates the column-only factors once per column and step and
 // then only multiplies.
 struct DcmipTab { double m1[NLEV], m2[NLEV], i1[NLEVP], i2[NLEVP], i3[NLEVP]; };
+constexpr int DCMIP_TAB_THREADS = 128;   // k_dcmip_tables: one block, one thread per interface
+static_assert(NLEVP <= DCMIP_TAB_THREADS, "k_dcmip_tables: one thread per interface: NLEV <= 127");
 template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
 __global__ void k_dcmip_tables(int test, const double* __restrict__ zm, const double* __restrict__ zi, DcmipTab* __restrict__ T) {
   const int k = threadIdx.x;

@@ -10,8 +10,17 @@
 #endif
 
 #define NP 4
+// The level count is a build-time setting, as the reference's PLEV (dimensions_mod.F90:27): a build may pass -DNLEV=<n>
+// (NLEVP follows).  The default is 72.  The static_asserts of the kernels name the rules, which together allow the multiples of
+// 8 from 16 to 72 (tse_kernels.h: the remap's blocks of 8 levels and its two elements per CU); anything else fails to compile.
+// Those values compile; 72 and 64 are the ones built and tested.
+#ifndef NLEV
 #define NLEV 72
-#define NLEVP 73
+#endif
+#ifndef NLEVP
+#define NLEVP (NLEV + 1)
+#endif
+static_assert(NLEVP == NLEV + 1, "NLEVP = NLEV + 1");
 
 namespace tse {
 
@@ -19,7 +28,7 @@ namespace tse {
 // 16 slots x 4 levels x 4 rows = 256 lanes, and a slot's 16 points x 4 levels are 512 contiguous bytes.
 constexpr int CL = 4;
 constexpr int NCHUNK = NLEV / CL;
-static_assert(NLEV % CL == 0 && CL % 2 == 0, "chunks hold whole level pairs");
+static_assert(NLEV % CL == 0 && CL % 2 == 0, "chunks hold whole level pairs: NLEV must be a multiple of 4");
 constexpr int PS = 16;        // element slots per patch (4 x 4 elements): slot = patch * PS + position
 // Block shape of the DSS-on-read kernels: a block owns a patch of PS element slots, 256 lanes; its tables (PatchSet, tse_tables.cpp)
 // name the storage slot of every element and of every halo-ring entry.  (Wider blocks of 6 x 4 and 8 x 4 elements have a shorter

@@ -113,14 +113,17 @@ def check_schedules_match(sched, minmax_len, rank, dist_mod):
 
 class PrimRun:
     def __init__(self, ne, qsize, test_case=1, nu_q=None, tstep=None, rsplit=3, rank=0, world=1, device=0,
-                 dist_mod=None, torch_mod=None, exchange="rccl", vert_remap_q_alg=0, limiter_option=8):
+                 dist_mod=None, torch_mod=None, exchange="rccl", vert_remap_q_alg=0, limiter_option=8, hvcoord=None):
         """exchange (world > 1): "rccl" = in-library RCCL send/recv (production), "torch" = torch.distributed P2P ops in the
         exchange callback, "staged" = callback with host-staged slots over a CPU backend (ranks may share a GPU).
-        limiter_option: 8 (optimization-based limiter) or 0 (no limiter), as control_mod's."""
+        limiter_option: 8 (optimization-based limiter) or 0 (no limiter), as control_mod's.
+        hvcoord: the vertical coordinate (an HvCoord; default: the shipped acme-72 grid); its level count selects the library
+        (_lib.lib(nlev=)) and every level extent below."""
         self.ne, self.qsize, self.rsplit, self.test_case = ne, qsize, rsplit, test_case
         self.nu_q = NU_Q.get(ne, 1e15 * (30.0 / ne) ** 3.2) if nu_q is None else nu_q
         self.tstep = TSTEP.get(ne, 300.0 * 30.0 / ne) if tstep is None else tstep
-        self.hv = HvCoord()
+        self.hv = hvcoord if hvcoord is not None else HvCoord()
+        self.nlev = self.hv.nlev
         topo = cm.topology(ne)
         geo = cm.geometry(ne, topo)
         self.nelem = 6 * ne * ne
@@ -216,7 +219,7 @@ class PrimRun:
         """order-independent checksum of Qdp(:,:,:,:,tl) on this rank: the wrap-around int64 sum of the bit patterns
         (summing it over ranks gives a number that is identical for every partition iff the fields are bit-for-bit equal)"""
         ptr, nbytes = self.hip.device_ptr("qdp%d" % tl)
-        n = self.mine.size * self.qsize * 72 * 16
+        n = self.mine.size * self.qsize * self.nlev * 16
         self.hip.synchronize()
         iface = {"shape": (n,), "typestr": "<i8", "data": (int(ptr), False), "version": 2}
         holder = type("DevArr", (), {"__cuda_array_interface__": iface})()
@@ -225,13 +228,13 @@ class PrimRun:
 
     def fetch_qdp(self, tl):
         n, q = self.mine.size, self.qsize
-        return self.hip.fetch("qdp%d" % tl, (n, q, 72, 4, 4))   # (one time level: the two are separate allocations)
+        return self.hip.fetch("qdp%d" % tl, (n, q, self.nlev, 4, 4))   # (one time level: the two are separate allocations)
 
     def fetch_q(self, tl):
         """(Q, lnps) of this rank's elements, formed on the device from Qdp(tl) and the current ps_v (what prim_run_subcycle leaves in
         elem%state%Q and elem%state%lnps(:,:,np1)): Q[ie][q][k][j][i], lnps[ie][j][i]"""
         n = self.mine.size
-        out = dict(Q=np.empty((n, self.qsize, 72, 4, 4)), lnps=np.empty((n, 4, 4)))
+        out = dict(Q=np.empty((n, self.qsize, self.nlev, 4, 4)), lnps=np.empty((n, 4, 4)))
         self.hip.state_q(tl)
         self.hip.copy_q_d2h(out); self.hip.copy_lnps_d2h(out)
         return out["Q"], out["lnps"]

@@ -112,6 +112,9 @@ module cuda_mod
      function tse_last_error() bind(C, name='tse_last_error') result(p)
        import; type(c_ptr) :: p
      end function
+     integer(c_int) function tse_nlev() bind(C, name='tse_nlev')
+       import
+     end function
      integer(c_int) function tse_halo_layout(ctx, ns, nr) bind(C, name='tse_halo_layout')
        import; type(c_ptr), value :: ctx; integer(c_int), intent(out) :: ns, nr
      end function
@@ -183,6 +186,17 @@ contains
     call abortmp(text)
   end subroutine seam_abort
 
+  ! The library is built for one level count (tse_nlev(); include/transport_se_hip.h): a host built with another PLEV must not
+  ! drive it -- every level extent it passes would be read with the library's.
+  subroutine check_nlev(where)
+    character(len=*), intent(in) :: where
+    character(len=200) :: text
+    if (tse_nlev() == nlev) return
+    write(text, '(a,a,i0,a,i0,a)') where, ': the HIP library is built for nlev = ', tse_nlev(), ', this host for nlev = ', nlev, &
+         ' (PLEV): link the library built with -DNLEV=<PLEV>'
+    call seam_abort(trim(text))
+  end subroutine check_nlev
+
   subroutine tic()
     call system_clock(t_c0)
   end subroutine tic
@@ -228,6 +242,7 @@ contains
     if (hypervis_subcycle_q /= 1) call seam_abort('cuda_mod_init(hip): hypervis_subcycle_q must be 1')
     if (hypervis_power /= 0 .or. hypervis_scaling /= 0) call seam_abort('cuda_mod_init(hip): hypervis_power and hypervis_scaling must be 0')
     if (vert_remap_q_alg < 0 .or. vert_remap_q_alg > 2) call seam_abort('cuda_mod_init(hip): vert_remap_q_alg must be 0, 1 or 2')
+    call check_nlev('cuda_mod_init(hip)')
     allocate(putm(8,nelemd), getm(8,nelemd), revm(8,nelemd))
     do ie = 1, nelemd
        putm(:,ie) = elem(ie)%desc%putmapP(1:8)
@@ -520,6 +535,7 @@ contains
     integer :: ie, i, j
     !$OMP BARRIER
     !$OMP MASTER
+    call check_nlev('dcmip_init_hip')
     call tic_res()
     allocate(lat(np,np,nelemd), lon(np,np,nelemd), hyam(nlev), hybm(nlev))
     do ie = 1, nelemd

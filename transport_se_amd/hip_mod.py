@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 
-NP, NLEV, NLEVP = 4, 72, 73
+NP, NLEV, NLEVP = 4, 72, 73   # the default build of the library (_lib.DEFAULT_NLEV); a HipMod's own level count is self.nlev
 DSSeta, DSSomega, DSSdiv_vdp_ave = 1, 2, 3  # prim_advection_mod.F90:454-456
 
 
@@ -32,11 +32,17 @@ def _vp(a):
 
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
-                 schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None):
+                 schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
         """cuda_mod_init.  hvcoord = (hyai, hybi, ps0).  schedule = dict(send=[(peer, ptrP, lengthP)...],
         recv=[...]) as in Schedule(1)%SendCycle/RecvCycle; exchange(sendbuf_ptr, recvbuf_ptr, nlyr, kind) -> 0.
-        lib_path: another build of the same sources (_lib.HOOKS_SO: the tests' fault injection) instead of the product library."""
-        L = _lib.lib(lib_path)
+        lib_path: another build of the same sources (_lib.HOOKS_SO: the tests' fault injection) instead of the product library.
+        nlev: the level count (default: that of hvcoord, len(hyai) - 1); the library built for it is loaded (_lib.lib(nlev=))."""
+        hyai, hybi, ps0 = hvcoord
+        self.nlev = int(nlev) if nlev is not None else len(hyai) - 1
+        if len(hyai) != self.nlev + 1 or len(hybi) != self.nlev + 1:
+            raise TseError("hvcoord has %d interfaces, nlev = %d needs %d" % (len(hyai), self.nlev, self.nlev + 1))
+        self.nlevp = self.nlev + 1
+        L = _lib.lib(lib_path, nlev=self.nlev)
         self.L = L
         self.qsize = int(qsize)
         self.nelemd = int(elem["metdet"].shape[0])
@@ -48,7 +54,6 @@ class HipMod:
 
         def keep(x, dtype):
             x = np.ascontiguousarray(x, dtype=dtype); self._keep.append(x); return x
-        hyai, hybi, ps0 = hvcoord
         a.Dvv = _vp(keep(deriv_Dvv, np.float64)); a.hyai = _vp(keep(hyai, np.float64)); a.hybi = _vp(keep(hybi, np.float64))
         a.ps0 = float(ps0)
         for name, cnt in (("Dinv", 64), ("metdet", 16), ("rmetdet", 16), ("spheremp", 16), ("rspheremp", 16)):
@@ -242,9 +247,9 @@ class HipMod:
 
     def remap_q_ppm(self, qdp, dp1, dp2):
         """remap_Q_ppm(Qdp,np,qsize,dp1,dp2) (prim_advection_mod.F90:98): qdp[ie][q][k][np][np], dp1/dp2[ie][k][np][np] -> new qdp"""
-        q = np.ascontiguousarray(qdp, np.float64).copy(); assert q.shape == (self.nelemd, self.qsize, NLEV, NP, NP)
+        q = np.ascontiguousarray(qdp, np.float64).copy(); assert q.shape == (self.nelemd, self.qsize, self.nlev, NP, NP)
         d1 = np.ascontiguousarray(dp1, np.float64); d2 = np.ascontiguousarray(dp2, np.float64)
-        assert d1.shape == d2.shape == (self.nelemd, NLEV, NP, NP)
+        assert d1.shape == d2.shape == (self.nelemd, self.nlev, NP, NP)
         self._chk(self.L.tse_remap_q_ppm(self.h, _vp(q), _vp(d1), _vp(d2)))
         return q
 
@@ -262,7 +267,7 @@ class HipMod:
         return tuple(out)
 
     def get_qminmax(self):
-        qmin = np.empty((self.nelemd, self.qsize, NLEV)); qmax = np.empty_like(qmin)
+        qmin = np.empty((self.nelemd, self.qsize, self.nlev)); qmax = np.empty_like(qmin)
         self._chk(self.L.tse_get_qminmax(self.h, _vp(qmin), _vp(qmax)))
         return qmin, qmax
 

@@ -1,6 +1,9 @@
 """hvcoord_t / hvcoord_init (reference src/share/hybvcoord_mod.F90:18-171): hybrid vertical coordinate read from the
 ascii files the reference's namelists name (test/dcmip1-1/dcmip1-1.nl: vcoord/acme-72{m,i}.ascii).  The two data
-files are shipped as data under transport_se_amd/data/vcoord/."""
+files are shipped as data under transport_se_amd/data/vcoord/.  Any level count is read (the reference's plev is a build setting:
+dimensions_mod.F90:27); the library that runs it must be built for the same count (_lib.lib(nlev=...), tse_nlev()).
+The reference's other grids (test/dcmip1-1/dcmip1-1.nl: vcoord/12k_top-64{m,i}.ascii) are not shipped: a namelist names the
+user's own copy."""
 import os
 
 import numpy as np
@@ -10,13 +13,20 @@ P0 = 100000.0  # physical_constants.F90:26
 
 
 class HvCoord:
-    def __init__(self, vfile_mid=None, vfile_int=None):
+    def __init__(self, vfile_mid=None, vfile_int=None, nlev=None):
+        """nlev: the level count the caller is built for (the reference's plev); None: whatever the mid-level file holds.
+        The interface file must then hold nlev + 1 levels (plevp)."""
         vfile_mid = vfile_mid or os.path.join(DATA, "acme-72m.ascii")
         vfile_int = vfile_int or os.path.join(DATA, "acme-72i.ascii")
         self.hyai, self.hybi = self._read(vfile_int)
         self.hyam, self.hybm = self._read(vfile_mid)
-        if self.hyai.size != 73 or self.hyam.size != 72:
-            raise ValueError("hyai input file and plevp do not match")  # hybvcoord_mod.F90:79-82
+        plev = int(nlev) if nlev is not None else self.hyam.size
+        # the reference's checks and messages (hybvcoord_mod.F90:76-102), first failure reported
+        for name, arr, want, what in (("hyai", self.hyai, plev + 1, "plevp"), ("hybi", self.hybi, plev + 1, "plevp"),
+                                      ("hyam", self.hyam, plev, "plev"), ("hybm", self.hybm, plev, "plev")):
+            if arr.size != want:
+                raise ValueError("Error: %s input file and HOMME %s do not match %d %d" % (name, what, want, arr.size))
+        self.nlev, self.nlevp = plev, plev + 1
         self.ps0 = P0
         self.etam = self.hyam + self.hybm   # :170-171
         self.etai = self.hyai + self.hybi

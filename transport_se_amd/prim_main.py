@@ -113,6 +113,35 @@ def settings(groups):
     return s
 
 
+SHIPPED_VCOORD = {"vfile_mid": "acme-72m.ascii", "vfile_int": "acme-72i.ascii"}   # transport_se_amd/data/vcoord
+
+
+def vertical_coordinate(s):
+    """hvcoord_init(vfile_mid, vfile_int) as prim_main calls it (prim_main.F90:94-97): the files are opened by the names the
+    namelist gives, relative to the working directory, as the reference's open() does (hybvcoord_mod.F90:61-71).  A name that is
+    not there is served from the shipped copy only when it is one of the shipped acme-72 files (the reference's own namelists name
+    vcoord/acme-72{m,i}.ascii), so that every such namelist runs as it always has; an empty name means the shipped grid.  Any other
+    missing file ends the run with the reference's messages.  The level count is the files' (HvCoord checks that they agree)."""
+    from .hybvcoord import DATA, HvCoord
+    files = {}
+    for key, line in (("vfile_int", 63), ("vfile_mid", 70)):
+        name = str(s.get(key) or "").strip()
+        if not name:
+            files[key] = os.path.join(DATA, SHIPPED_VCOORD[key])
+        elif os.path.isfile(name):
+            files[key] = name
+        elif os.path.basename(name) in SHIPPED_VCOORD.values():
+            files[key] = os.path.join(DATA, os.path.basename(name))
+        else:
+            print(" open() error: hybvcoord_mod.F90 %d %s" % (line, name), flush=True)
+            raise SystemExit("prim_main: error in hvcoord_init (%s = %r: no such file)" % (key, name))
+    try:
+        return HvCoord(files["vfile_mid"], files["vfile_int"])
+    except ValueError as ex:
+        print(" %s" % ex, flush=True)
+        raise SystemExit("prim_main: error in hvcoord_init (%s)" % ex)
+
+
 def _fortran_e(x, w, d):
     """Fortran Ew.d: 0.dddE+ee (the mantissa is below 1, unlike C's %E)"""
     if x == 0 or not np.isfinite(x):
@@ -229,6 +258,7 @@ def main(argv=None):
     if world > 1:
         dist.broadcast_object_list(box, src=0)
     s = settings(parse_namelists(box[0]))
+    hv = vertical_coordinate(s)
 
     from . import cube_mesh as cm
     from .driver import PrimRun
@@ -245,7 +275,7 @@ def main(argv=None):
         os._exit(2)
     run = PrimRun(s["ne"], s["qsize"], test_case=s["test"], nu_q=s["nu_q"], tstep=s["tstep"], rsplit=s["rsplit"], rank=rank, world=world,
                   device=local, dist_mod=dist, torch_mod=torch, exchange=exchange, vert_remap_q_alg=s["vert_remap_q_alg"],
-                  limiter_option=s["limiter_option"])
+                  limiter_option=s["limiter_option"], hvcoord=hv)
     hip, gid, nelem = run.hip, run.mine, run.nelem
     say = print if rank == 0 else (lambda *x, **k: None)
 
@@ -344,7 +374,7 @@ def main(argv=None):
         print("DCMIP 1-%d: L1=%8.6f L2=%8.6f Linf=%8.6f q_max=%8.6f q_min=%14.6e" % (s["test"], nrm["L1"], nrm["L2"], nrm["Linf"], nrm["q_max"], nrm["q_min"]))
         for t in range(s["qsize"]):
             print("Q%d mass: %22.14E -> %22.14E (relative change %10.3e)" % (t + 1, m0[t], m1[t], (m1[t] - m0[t]) / max(abs(m0[t]), 1e-300)))
-        print("prim_run wall %.3f s: %.4e tracer-DOF-steps/s on %d rank(s)" % (float(stack[:, 0].max()), nelem * 16 * 72 * s["qsize"] * nsteps / float(stack[:, 0].max()), world))
+        print("prim_run wall %.3f s: %.4e tracer-DOF-steps/s on %d rank(s)" % (float(stack[:, 0].max()), nelem * 16 * run.nlev * s["qsize"] * nsteps / float(stack[:, 0].max()), world))
     run.close()
     if world > 1:
         watchdog.kick("the final barrier")   # (still armed: a peer that died leaves this rank in the barrier)
