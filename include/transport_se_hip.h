@@ -225,9 +225,28 @@ int tse_copy_lnps_d2h(tse_ctx *ctx, double *lnps_elem1, size_t elem_stride);
  * (both null before the first tse_state_q) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
- * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq" */
+ * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq",
+ * and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
-int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing */
+int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
+/* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call
+ * alone; tse_timing neither turns them on nor clears them):
+ *   "comm_pack_q", "comm_pack_mm"          pack launches of the tracer halo (kind 0) / of the element bounds (kind 1), on the stream
+ *                                          they run on
+ *   "comm_exchange_q", "comm_exchange_mm"  the whole exchange of that kind: ncclGroupStart .. ncclGroupEnd, or the callback (with the
+ *                                          host's wait for the packs before it)
+ *   "comm_unpack_q", "comm_unpack_mm"      unpack launches
+ *   "comm_wait"                            the exposed wait: the time the compute stream could not go on because communication was not
+ *                                          done.  Where the exchange runs on the communication stream (the whole-step call and
+ *                                          tse_prim_run_subcycle on several ranks), one event pair on the compute stream brackets each
+ *                                          of its waits for that stream (after every split stage; at the first stage's bounds).  Where
+ *                                          the exchange runs on the compute stream itself (tse_euler_step, and the whole-step call with
+ *                                          TSE_DSS_ON_READ=0), all of it is exposed: the pair brackets the pack -> exchange -> unpack
+ *                                          sequence, so its time is their sum (with the launch gaps between them).
+ * "comm" gives the total of all seven, "comm_exchange" both kinds.  Off by default; while off no event is created or recorded and the
+ * launches and stream dependencies are those of a context without it.  A context without neighbour ranks records nothing: 0 ms and 0
+ * launches for every comm_* name.  The events resolve when they are read (the read waits for the compute and communication streams). */
+int tse_comm_timing(tse_ctx *ctx, int enable);
 /* where the five tracer-sized fields were placed (device memory is not uniform for writes and the rate is a property of the
  * allocation: tse_init tries field-sized chunks -- up to TSE_PLACEMENT, default 20, in all, up to 8 held at a time, the slowest given
  * back and the next one allocated behind a small pad -- until three of them take a streaming write at TSE_PLACEMENT_GOOD, default

@@ -8,7 +8,11 @@ the work is the real thing: boundary-first split launches, pack / unpack, ncclSe
 communication stream (device-local copies instead of xGMI transfers), event hand-over, interior overlap.  ms/step here against
 (1-GPU ms/step) / W is the part of the strong-scaling loss that does not depend on link bandwidth.
 
-    python tools/rank_rehearsal.py --ne 120 --qsize 35 --world 8 [--rank 3] [--cycles 2]
+    python tools/rank_rehearsal.py --ne 120 --qsize 35 --world 8 [--rank 3] [--cycles 2] [--comm-timing]
+
+--comm-timing: the timed cycles run with tse_comm_timing on (so ms_per_step includes the cost of its events), and the JSON line gets
+"comm_ms_per_step" / "comm_launches_per_step": the seven comm_* groups per tracer step.  In loopback the exchange groups time
+device-local copies, not xGMI transfers.
 """
 import argparse
 import json
@@ -24,11 +28,12 @@ def main():
     ap.add_argument("--ne", type=int, default=120); ap.add_argument("--qsize", type=int, default=35)
     ap.add_argument("--world", type=int, default=8); ap.add_argument("--rank", type=int, default=-1)
     ap.add_argument("--cycles", type=int, default=2)
+    ap.add_argument("--comm-timing", action="store_true", help="time the halo exchange (tse_comm_timing) in the timed cycles")
     ap.add_argument("--verify", action="store_true", help="also compare one DSS-on-read step with the one-DSS-pass-per-stage route on the device")
     a = ap.parse_args()
     from transport_se_amd import cube_mesh as cm
     from transport_se_amd.driver import NU_Q, TSTEP, partition
-    from transport_se_amd.hip_mod import HipMod
+    from transport_se_amd.hip_mod import COMM_GROUPS, HipMod
     from transport_se_amd.hybvcoord import HvCoord
     hv = HvCoord()
     topo = cm.topology(a.ne); geo = cm.geometry(a.ne, topo)
@@ -48,10 +53,17 @@ def main():
         h.dcmip_set_initial()
         n = h.prim_run_subcycle(tstep, 1, 0)          # warm-up: one rsplit cycle
         h.synchronize()
+        if a.comm_timing:
+            h.comm_timing(True)
         t0 = time.perf_counter()
         n = h.prim_run_subcycle(tstep, a.cycles, n)
         h.synchronize()
         ms = 1e3 * (time.perf_counter() - t0) / (3 * a.cycles)
+        if a.comm_timing:
+            ct = {k: h.kernel_time(k) for k in COMM_GROUPS}
+            comm = {"comm_ms_per_step": {k: round(v[0] / (3 * a.cycles), 4) for k, v in ct.items()},
+                    "comm_launches_per_step": {k: round(v[1] / (3 * a.cycles), 3) for k, v in ct.items()}}
+            h.comm_timing(False)
         h.timing(True)
         n = h.prim_run_subcycle(tstep, 1, n)
         h.synchronize()
@@ -67,6 +79,8 @@ def main():
         import torch   # (already in the process: _lib loads it first) -- device memory in use with every field of the rank allocated
         free, total = torch.cuda.mem_get_info(0)
         out["device_memory_used_GB"] = round((total - free) / 1e9, 2)
+        if a.comm_timing:
+            out.update(comm)
         if a.verify:
             # one tracer step from the initial state, DSS on read against one DSS pass per stage (same loopback halo in both):
             # the two routes must agree to the step tolerance at this shape, too

@@ -133,7 +133,7 @@ _libs = {}
 SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchronize", "tse_copy_qdp_h2d", "tse_copy_qdp_d2h",
            "tse_set_derived", "tse_set_divdp", "tse_get_derived", "tse_advec_tracers_remap_rk2", "tse_compute_divdp", "tse_euler_step",
            "tse_qdp_time_avg", "tse_vertical_remap", "tse_get_qminmax", "tse_dcmip_init", "tse_dcmip_set_initial",
-           "tse_dcmip_step_inputs", "tse_prim_run_subcycle", "tse_device_ptr", "tse_kernel_time", "tse_timing",
+           "tse_dcmip_step_inputs", "tse_prim_run_subcycle", "tse_device_ptr", "tse_kernel_time", "tse_timing", "tse_comm_timing",
            "tse_halo_layout", "tse_halo_minmax_layout", "tse_comm_unique_id", "tse_comm_init", "tse_comm_precheck", "tse_comm_version", "tse_comm_info", "tse_comm_abort",
            "tse_boundary_layout", "tse_patch_layout", "tse_placement", "tse_invalidate_cache", "tse_divergence_sphere", "tse_laplace_sphere_wk", "tse_remap_q_ppm", "tse_host_register", "tse_element_mass", "tse_element_qdiag",
            "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h"]
@@ -191,6 +191,7 @@ def lib(path=None, nlev=None):
     L.tse_device_ptr.argtypes = [vp, C.c_char_p, C.POINTER(sz)]; L.tse_device_ptr.restype = vp
     L.tse_kernel_time.argtypes = [vp, C.c_char_p, C.POINTER(d), C.POINTER(C.c_long)]
     L.tse_timing.argtypes = [vp, i]
+    L.tse_comm_timing.argtypes = [vp, i]
     L.tse_halo_layout.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
     L.tse_halo_minmax_layout.argtypes = [vp, vp, vp]
     L.tse_comm_unique_id.argtypes = [vp]

@@ -139,9 +139,13 @@ struct tse_ctx {
   double* stage[2] = {nullptr, nullptr};       // page-locked staging buffers for every other host pointer
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   bool timing = false;
+  // tse_comm_timing: the comm_* groups (pack / exchange / unpack of both halo kinds, the compute stream's exposed wait); their events
+  // sit on the communication stream too, and a prefetched exchange may still be in flight there when they are read (comm_pending)
+  bool comm_timing = false, comm_pending = false;
   std::map<std::string, KTimer> timers;
   struct Pending { const char* name; hipEvent_t a, b; };
-  std::vector<Pending> pending;       // event pairs recorded on `stream`, resolved lazily (no sync inside the step)
+  std::vector<Pending> pending;       // event pairs, each on one stream, resolved lazily (no sync inside the step)
+  size_t drain_at = 0;                // pending.size() at which the completed pairs are taken in (drain_timers)
   std::vector<hipEvent_t> free_events;
   double *sink = nullptr;   // write-only dump of k_remap (run-in levels of its segment tasks, surplus tracer slots): 16 columns x NLEV levels, then two bounds areas
   double *eta2 = nullptr;   // with lvl_tmp: twin buffers of the level fields (k_dss_lvl writes out of place, then swap)
@@ -189,24 +193,47 @@ static hipEvent_t get_event(tse_ctx* c) {
   if (!c->free_events.empty()) { hipEvent_t e = c->free_events.back(); c->free_events.pop_back(); return e; }
   hipEvent_t e = nullptr; (void)hipEventCreate(&e); return e;
 }
+static void take_pending(tse_ctx* c, const tse_ctx::Pending& p) {
+  float ms = 0; (void)hipEventElapsedTime(&ms, p.a, p.b);
+  KTimer& t = c->timers[p.name]; t.ms += ms; t.n += 1;
+  c->free_events.push_back(p.a); c->free_events.push_back(p.b);
+}
+// A long run whose timers nobody reads would hold two events per group and launch for ever: past PENDING_DRAIN pairs, the pairs whose
+// second event has completed (both events of a pair are on one stream) are taken into the timers and their events recycled, and the next
+// drain waits until twice as many pairs as are still in flight have piled up.  Only hipEventQuery: the host never waits here.
+static const size_t PENDING_DRAIN = 1024;
+static void drain_timers(tse_ctx* c) {
+  size_t k = 0;
+  for (size_t i = 0; i < c->pending.size(); i++) {
+    if (hipEventQuery(c->pending[i].b) == hipSuccess) take_pending(c, c->pending[i]);
+    else c->pending[k++] = c->pending[i];
+  }
+  c->pending.resize(k);
+  c->drain_at = std::max(PENDING_DRAIN, 2 * k);
+  (void)hipGetLastError();   // (hipErrorNotReady of the pairs still in flight)
+}
 struct Scope {
   tse_ctx* c; const char* name; hipEvent_t a = nullptr; hipStream_t st;
-  Scope(tse_ctx* c_, const char* n, hipStream_t st_ = nullptr) : c(c_), name(n), st(st_ ? st_ : c_->stream) { if (c->timing) { a = get_event(c); (void)hipEventRecord(a, st); } }
+  Scope(tse_ctx* c_, const char* n, hipStream_t st_ = nullptr) : Scope(c_, n, st_, c_->timing) {}
+  Scope(tse_ctx* c_, const char* n, hipStream_t st_, bool on) : c(c_), name(n), st(st_ ? st_ : c_->stream) { if (on) { a = get_event(c); (void)hipEventRecord(a, st); } }
   ~Scope() {
     if (!a) return;
     hipEvent_t b = get_event(c);
     (void)hipEventRecord(b, st);
     c->pending.push_back({name, a, b});
+    if (c->pending.size() >= std::max(PENDING_DRAIN, c->drain_at)) drain_timers(c);
   }
+};
+// a comm_* group (tse_comm_timing): only on a context with a halo, and nothing at all while comm timing is off
+struct CommScope : Scope {
+  CommScope(tse_ctx* c_, const char* n, hipStream_t st_) : Scope(c_, n, st_, c_->comm_timing && c_->halo()) { if (a) c->comm_pending = true; }
 };
 static void resolve_timers(tse_ctx* c) {
   if (c->pending.empty()) return;
   (void)hipStreamSynchronize(c->stream);
-  for (auto& p : c->pending) {
-    float ms = 0; (void)hipEventElapsedTime(&ms, p.a, p.b);
-    KTimer& t = c->timers[p.name]; t.ms += ms; t.n += 1;
-    c->free_events.push_back(p.a); c->free_events.push_back(p.b);
-  }
+  if (c->comm_pending && c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);   // (a prefetched bounds exchange may be in flight)
+  c->comm_pending = false;
+  for (auto& p : c->pending) take_pending(c, p);
   c->pending.clear();
 }
 
@@ -741,6 +768,7 @@ int tse_compute_divdp(tse_ctx* c) {
 // (bndry_mod.F90:74-112 posts all sends and receives, then waits).  Otherwise the host's callback, after `st` has drained.
 static int halo_exchange(tse_ctx* c, int nlyr, int kind, hipStream_t st) {
   if (!c->halo()) return 0;
+  CommScope s(c, kind ? "comm_exchange_mm" : "comm_exchange_q", st);
   double* sb = kind ? c->sendbuf_mm : c->sendbuf;
   double* rb = kind ? c->recvbuf_mm : c->recvbuf;
   if (c->comm) {
@@ -778,6 +806,7 @@ static int halo_items(size_t tot, unsigned* blocks) {
 static int pack_tracers(tse_ctx* c, hipStream_t st, const double* scratch, int nlyr_halo, int nlyr = 0) {
   const int nq = nlyr ? nlyr : c->qsize * NLEV;
   if (!c->ncol_send) return 0;
+  CommScope s(c, "comm_pack_q", st);
   unsigned nb;
   if (halo_items((size_t)c->ncol_send * (nq / CL), &nb)) return 1;
   hipLaunchKernelGGL(k_pack_scratch<>, dim3(nb), dim3(256), 0, st, c->ncol_send, nq / CL, c->send_src_s, scratch, c->sendbuf, nlyr_halo, c->scr());
@@ -788,6 +817,7 @@ static int pack_tracers(tse_ctx* c, hipStream_t st, const double* scratch, int n
 static int pack_var(tse_ctx* c, hipStream_t st, const double* var, int var_levels) {
   const int nq = c->qsize * NLEV;
   if (!c->ncol_send || !var) return 0;
+  CommScope s(c, "comm_pack_q", st);
   unsigned nb;
   if (halo_items((size_t)c->ncol_send * NLEV, &nb)) return 1;
   hipLaunchKernelGGL(k_pack<>, dim3(nb), dim3(256), 0, st, c->ncol_send, NLEV, c->send_src, var, c->spheremp, c->sendbuf, nq + NLEV, nq, var_levels);
@@ -797,6 +827,7 @@ static int pack_var(tse_ctx* c, hipStream_t st, const double* var, int var_level
 static int pack_minmax(tse_ctx* c, hipStream_t st, const double* qmin = nullptr, const double* qmax = nullptr) {
   const int m = c->mm_m();
   if (!c->nmm_send) return 0;
+  CommScope s(c, "comm_pack_mm", st);
   unsigned nb;
   if (halo_items((size_t)c->nmm_send * (m / 2), &nb)) return 1;
   hipLaunchKernelGGL(k_pack_minmax<>, dim3(nb), dim3(256), 0, st, c->nmm_send, m, c->mm_send_src,
@@ -807,6 +838,7 @@ static int pack_minmax(tse_ctx* c, hipStream_t st, const double* qmin = nullptr,
 // DSS on read: copy the received tracer halo behind the planes of the scratch field the next slab kernel gathers from
 static int unpack_halo(tse_ctx* c, hipStream_t st, double* field, int nlyr_halo, int nlyr = 0) {
   if (!c->ncol_recv) return 0;
+  CommScope s(c, "comm_unpack_q", st);
   const int nq = nlyr ? nlyr : c->qsize * NLEV;   // layers to copy: the tracer planes, or also the extra variable's plane
   unsigned nb;
   if (halo_items((size_t)c->ncol_recv * (nq / CL), &nb)) return 1;
@@ -819,6 +851,7 @@ static int unpack_halo(tse_ctx* c, hipStream_t st, double* field, int nlyr_halo,
 static int unpack_minmax(tse_ctx* c, hipStream_t st) {
   const int m = c->mm_m();
   if (!c->nmm_recv) return 0;
+  CommScope s(c, "comm_unpack_mm", st);
   unsigned nb;
   if (halo_items((size_t)c->nmm_recv * (m / 2), &nb)) return 1;
   hipLaunchKernelGGL(k_unpack_minmax<>, dim3(nb), dim3(256), 0, st, c->nmm_recv, m, (const double*)c->recvbuf_mm, c->qmin + (size_t)c->nelemd * m,
@@ -841,8 +874,11 @@ static int nbr_minmax_kernel(tse_ctx* c) {
 }
 // neighbor_minmax (viscosity_mod.F90:748-816), everything on the compute stream (per-stage API)
 static int neighbor_minmax(tse_ctx* c) {
-  if (pack_minmax(c, c->stream)) return 1;
-  if (halo_exchange(c, 2 * c->mm_m(), 1, c->stream)) return 1;
+  {
+    CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
+    if (pack_minmax(c, c->stream)) return 1;
+    if (halo_exchange(c, 2 * c->mm_m(), 1, c->stream)) return 1;
+  }
   return nbr_minmax_kernel(c);
 }
 
@@ -936,9 +972,12 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
     }
     // biharmonic_wk_scalar_minmax: DSS(lap1) (+ min/max exchange) -> T = rspheremp*DSS(lap1).  The reference's message is
     // (lap, Qmin, Qmax) = 3*qsize*nlev layers (viscosity_mod.F90:389-391); here the Laplacian and the bounds travel separately.
-    if (pack_tracers(c, c->stream, c->B, nq)) return 1;
-    if (halo_exchange(c, nq, 0, c->stream)) return 1;
-    if (unpack_halo(c, c->stream, c->B, nq)) return 1;
+    {
+      CommScope w(c, "comm_wait", c->stream);
+      if (pack_tracers(c, c->stream, c->B, nq)) return 1;
+      if (halo_exchange(c, nq, 0, c->stream)) return 1;
+      if (unpack_halo(c, c->stream, c->B, nq)) return 1;
+    }
     if (dss_tracer_pass(c, c->B, c->T, nullptr)) return 1;
     if (c->lim && neighbor_minmax(c)) return 1;
     Scope s(c, "advance2");
@@ -953,10 +992,13 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
   double* pre = rhs == 2 ? c->B : c->T;
   const double* avg = fuse_avg ? c->q(avg_n0) : nullptr;
   // edgeVpack(Qdp) + edgeVpack(spheremp*DSSvar) -> bndry_exchangeV -> edgeVunpack + rspheremp  (:911-960)
-  if (pack_tracers(c, c->stream, pre, nq + NLEV)) return 1;
-  if (var && pack_var(c, c->stream, *var, var_levels)) return 1;
-  if (halo_exchange(c, nq + NLEV, 0, c->stream)) return 1;
-  if (unpack_halo(c, c->stream, pre, nq + NLEV)) return 1;
+  {
+    CommScope w(c, "comm_wait", c->stream);
+    if (pack_tracers(c, c->stream, pre, nq + NLEV)) return 1;
+    if (var && pack_var(c, c->stream, *var, var_levels)) return 1;
+    if (halo_exchange(c, nq + NLEV, 0, c->stream)) return 1;
+    if (unpack_halo(c, c->stream, pre, nq + NLEV)) return 1;
+  }
   if (dss_tracer_pass(c, pre, Qnp1, avg)) return 1;
   return dss_level_var(c, var, var_levels);
 }
@@ -1035,7 +1077,7 @@ static int split_stage(tse_ctx* c, const char* timer, Launch launch /* (Work) */
   } else if (launch(work_of(c, 2))) return 1;
   if (!c->comm) { if (comm_work()) return 1; HIPCHK(hipEventRecord(evC, c->comm_stream)); }
   if (done_out) *done_out = evC;
-  else HIPCHK(hipStreamWaitEvent(c->stream, evC, 0));
+  else { CommScope w(c, "comm_wait", c->stream); HIPCHK(hipStreamWaitEvent(c->stream, evC, 0)); }   // (the comm_wait pair brackets the wait)
   return 0;
 }
 
@@ -1077,6 +1119,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
       LAUNCH_CHECK();
     }
     if (halo_ready) {
+      CommScope w(c, "comm_wait", c->stream);
       HIPCHK(hipStreamWaitEvent(c->stream, c->ev_mm, 0));
     } else if (c->halo()) {
       hipEvent_t ev0 = next_sync_event(c), evM = next_sync_event(c);
@@ -1084,6 +1127,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
       HIPCHK(hipStreamWaitEvent(cs, ev0, 0));
       if (pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs)) return 1;
       HIPCHK(hipEventRecord(evM, cs));
+      CommScope w(c, "comm_wait", c->stream);
       HIPCHK(hipStreamWaitEvent(c->stream, evM, 0));
     }
     if (nbr_minmax_kernel(c)) return 1;
@@ -1526,7 +1570,13 @@ extern "C" int tse_test_table(void* h, const char* name, const void** data, size
 }
 extern "C" void tse_test_tables_free(void* h) { delete (TseTestTables*)h; }
 #endif
-int tse_timing(tse_ctx* c, int enable) { resolve_timers(c); c->timing = enable != 0; c->timers.clear(); return 0; }
+// the two switches reset their own groups only: the comm_* groups (tse_comm_timing) and all the others (tse_timing)
+static void reset_timers(tse_ctx* c, bool comm) {
+  for (auto it = c->timers.begin(); it != c->timers.end();)
+    if ((it->first.compare(0, 5, "comm_") == 0) == comm) it = c->timers.erase(it); else ++it;
+}
+int tse_timing(tse_ctx* c, int enable) { resolve_timers(c); c->timing = enable != 0; reset_timers(c, false); return 0; }
+int tse_comm_timing(tse_ctx* c, int enable) { resolve_timers(c); c->comm_timing = enable != 0; reset_timers(c, true); return 0; }
 int tse_kernel_time(tse_ctx* c, const char* name, double* ms, long* launches) {
   resolve_timers(c);
   double t = 0; long n = 0;

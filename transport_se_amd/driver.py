@@ -147,6 +147,7 @@ class PrimRun:
         self.exchange_note = None
         self.hip_device = device
         self.rank, self.world = rank, world
+        self._dist = dist_mod
         self.hip = HipMod(self.elem, cm.dvv(), (self.hv.hyai, self.hv.hybi, self.hv.ps0), qsize, self.nu_q,
                           rsplit=rsplit, device=device, schedule=dict(send=desc["send"], recv=desc["recv"]), exchange=callback,
                           vert_remap_q_alg=vert_remap_q_alg, limiter_option=limiter_option)
@@ -214,6 +215,22 @@ class PrimRun:
         for _ in range(nsteps):
             np1 = self.step()
         return np1
+
+    def comm_stats(self):
+        """{name: (ms, launches)} of this rank's halo-exchange timers (HipMod.comm_times: the seven comm_* groups and their totals) since
+        hip.comm_timing(True).  Several ranks: a collective call over the control plane; on rank 0 the dict also holds "max" = {name:
+        (max ms, max launches) over the ranks} and "ranks" = every rank's dict, in rank order."""
+        mine = self.hip.comm_times()
+        if self.world == 1:
+            return mine
+        everyone = [None] * self.world
+        self._dist.all_gather_object(everyone, mine)
+        if self.rank != 0:
+            return mine
+        out = dict(mine)
+        out["max"] = {k: (max(r[k][0] for r in everyone), max(r[k][1] for r in everyone)) for k in mine}
+        out["ranks"] = everyone
+        return out
 
     def state_checksum(self, tl, torch_mod):
         """order-independent checksum of Qdp(:,:,:,:,tl) on this rank: the wrap-around int64 sum of the bit patterns

@@ -22,6 +22,12 @@ NP, NLEV, NLEVP = 4, 72, 73   # the default build of the library (_lib.DEFAULT_N
 DSSeta, DSSomega, DSSdiv_vdp_ave = 1, 2, 3  # prim_advection_mod.F90:454-456
 
 
+# the halo-exchange timers of tse_comm_timing, and the prefixes that sum them: "comm" = all seven, "comm_pack" / "comm_exchange" /
+# "comm_unpack" = both kinds
+COMM_GROUPS = ("comm_pack_q", "comm_pack_mm", "comm_exchange_q", "comm_exchange_mm", "comm_unpack_q", "comm_unpack_mm", "comm_wait")
+COMM_TOTALS = ("comm", "comm_pack", "comm_exchange", "comm_unpack")
+
+
 class TseError(RuntimeError):
     """what the Fortran side turns into abortmp(msg) (parallel_mod.F90:274-287)"""
 
@@ -306,10 +312,18 @@ class HipMod:
     def timing(self, enable=True):
         self.L.tse_timing(self.h, int(enable))
 
+    def comm_timing(self, enable=True):
+        """enable/disable + reset the comm_* timers (COMM_GROUPS; tse_comm_timing): separate from timing(), which leaves them alone"""
+        self.L.tse_comm_timing(self.h, int(enable))
+
     def kernel_time(self, name):
         ms = C.c_double(); n = C.c_long()
         self.L.tse_kernel_time(self.h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+    def comm_times(self):
+        """{name: (ms, launches)} of the seven comm_* groups and of their totals (COMM_TOTALS) since the last comm_timing()"""
+        return {k: self.kernel_time(k) for k in COMM_GROUPS + COMM_TOTALS}
 
     def halo_layout(self):
         a, b = C.c_int(), C.c_int()

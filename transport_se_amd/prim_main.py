@@ -7,7 +7,9 @@
 Reads the reference's Fortran namelists from stdin the way prim_main/readnl do (src/prim_main.F90:47,
 src/share/namelist_mod.F90:159-351: rank 0 reads, everybody gets a copy), runs the device-resident prim_run loop and leaves
 a `HommeTime_stats` file with the four timer names the reference's perf scripts grep (test/run_ne120_perf.sh:140-144:
-prim_run, prim_advance_exp, prim_advec_tracers_remap_rk2, vertical_remap; wallmax = maximum over the ranks).  Only the ~12
+prim_run, prim_advance_exp, prim_advec_tracers_remap_rk2, vertical_remap; wallmax = maximum over the ranks), and on several ranks
+two more rows behind them: bndry_exchange (pack + exchange + unpack of the halo) and bndry_exchange_wait (the part of it the
+compute stream waited for; tse_comm_timing).  Only the ~12
 ctl_nl/vert_nl keys the tracer path reads are honoured; output (analysis_nl), restart and threading keys are accepted and
 ignored.  At the end it prints the error-norm line the reference's NCL script prints and the tracer-mass lines; both are
 computed reproducibly (diagnostics.py), so the same run prints the same digits on 1, 2, 4 or 8 GPUs.
@@ -161,6 +163,20 @@ def write_hommetime(path, timers, nranks=1):
             f.write("%-40s %9d %8d %10d %12.6f %12.6f %12.6f\n" % (name, nranks, 1, count * nranks, tot, mx, mn))
 
 
+HOMMETIME_ROWS = ("prim_run", "prim_advance_exp", "prim_advec_tracers_remap_rk2", "vertical_remap")
+# several ranks: the halo exchange as the reference's bndry_exchange timer reports it (bndry_mod.F90:234-245) -- pack + exchange + unpack
+# of both kinds (tse_comm_timing's comm_pack, comm_exchange, comm_unpack) -- and the compute stream's exposed wait for it (comm_wait)
+COMM_ROWS = ("bndry_exchange", "bndry_exchange_wait")
+
+
+def hommetime_timers(stack, counts):
+    """{row: (count, walltotal, wallmax, wallmin)} of HommeTime_stats from stack[rank][column] (seconds; column i = row i): the four rows
+    the perf scripts grep, in their order, then COMM_ROWS for the columns beyond the fourth"""
+    names = HOMMETIME_ROWS + COMM_ROWS[:stack.shape[1] - len(HOMMETIME_ROWS)]
+    assert len(names) == stack.shape[1] == len(counts), (names, stack.shape, counts)
+    return {nm: (int(cnt), float(stack[:, i].sum()), float(stack[:, i].max()), float(stack[:, i].min())) for i, (nm, cnt) in enumerate(zip(names, counts))}
+
+
 def _rank_world():
     env = os.environ
     for r, w in (("RANK", "WORLD_SIZE"), ("PMI_RANK", "PMI_SIZE"), ("OMPI_COMM_WORLD_RANK", "OMPI_COMM_WORLD_SIZE"), ("SLURM_PROCID", "SLURM_NTASKS")):
@@ -295,6 +311,8 @@ def main(argv=None):
         v = hip.comm_version()
         say(" RCCL runtime %s (%s), library built with the headers of %s" % (v["runtime"], v["path"], v["built"]))
     hip.timing(True)
+    if world > 1:
+        hip.comm_timing(True)   # (the COMM_ROWS of HommeTime_stats)
     hip.synchronize()
     if world > 1:
         dist.barrier()
@@ -351,6 +369,11 @@ def main(argv=None):
     wall = time.perf_counter() - t0
     groups = {k: hip.kernel_time(k)[0] / 1e3 for k in ("advance", "dss", "lap", "minmax", "level", "remap", "dcmip")}
     mine = np.array([wall, groups["dcmip"], sum(groups[k] for k in ("advance", "dss", "lap", "minmax", "level")), groups["remap"]])
+    counts = [nsteps // s["rsplit"], nsteps, nsteps, nsteps // s["rsplit"]]
+    if world > 1:
+        ct = hip.comm_times()
+        mine = np.append(mine, [sum(ct[k][0] for k in ("comm_pack", "comm_exchange", "comm_unpack")) / 1e3, ct["comm_wait"][0] / 1e3])
+        counts += [ct["comm_exchange"][1], ct["comm_wait"][1]]   # (the same on every rank: one schedule)
     if world > 1:
         ranks_t = [None] * world if rank == 0 else None
         dist.gather_object(mine, ranks_t, dst=0)
@@ -358,10 +381,7 @@ def main(argv=None):
     else:
         stack = mine[None]
     if rank == 0:
-        names = ("prim_run", "prim_advance_exp", "prim_advec_tracers_remap_rk2", "vertical_remap")
-        counts = (nsteps // s["rsplit"], nsteps, nsteps, nsteps // s["rsplit"])
-        write_hommetime("HommeTime_stats", {nm: (cnt, float(stack[:, i].sum()), float(stack[:, i].max()), float(stack[:, i].min()))
-                                            for i, (nm, cnt) in enumerate(zip(names, counts))}, world)
+        write_hommetime("HommeTime_stats", hommetime_timers(stack, counts), world)
     # error norms on the unique-column grid (dcmip1-*_error_norm_ng.ncl:39-77) and tracer mass ("Q, Q diss")
     q1 = gather(run.fetch_qdp(np1)[:, tr].copy())
     ps_v = gather(hip.fetch("ps_v", (gid.size, 4, 4)))
