@@ -166,7 +166,13 @@ int tse_invalidate_cache(tse_ctx *ctx);
  *   remap_Q_ppm(Qdp,np,qsize,dp1,dp2)      prim_advection_mod.F90:98-214  Qdp[ie][qsize][nlev][np*np] in place,
  *                                                                          dp1, dp2[ie][nlev][np*np]
  * They run the same device routines as the fused kernels (operator-level parity checks; not used by the time loop;
- * tse_remap_q_ppm overwrites time level 1 of the device tracer state and the dp/divdp_proj/dp3d level fields). */
+ * tse_remap_q_ppm overwrites time level 1 of the device tracer state and the dp/divdp_proj/dp3d level fields).
+ * Precondition of tse_remap_q_ppm, checked on the host before anything is uploaded or launched (nonzero return, and
+ * tse_last_error() names the first offending element, column and level, counted from 0): every dp1 is a finite positive number,
+ * every dp2 is finite and not negative, and in every column the serial fp64 partial sums of dp2 above the last level stay below
+ * sum(dp1) + 1 -- the sentinel on which remap_Q_ppm's bracket search ends (prim_advection_mod.F90:142-172; the reference assumes
+ * this silently).  The last level's own sum of dp2 is not used: pin(nlev+1) is set to pio(nlev+1) = sum(dp1), and its search ends on
+ * the sentinel too, so sum(dp1) + 1 must exceed sum(dp1) in fp64: a column with sum(dp1) >= 2^53 is refused as well. */
 int tse_divergence_sphere(tse_ctx *ctx, const double *v, double *div);
 int tse_laplace_sphere_wk(tse_ctx *ctx, const double *s, double *lap);
 int tse_remap_q_ppm(tse_ctx *ctx, double *Qdp, const double *dp1, const double *dp2);

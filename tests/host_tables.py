@@ -60,3 +60,16 @@ def host_tables(desc, strips=False):
         return out
     finally:
         L.tse_test_tables_free(h)
+
+
+def check_remap_grids(dp1, dp2):
+    """check_remap_grids (csrc/tse_tables.cpp; what tse_remap_q_ppm runs before any upload or launch) on dp1, dp2[E][nlev][4][4]:
+    None for a good pair, else ((element, column, level), message) of the first offender"""
+    L = _hooks()
+    L.tse_test_remap_grids.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    d1, d2 = np.ascontiguousarray(dp1, dtype=np.float64), np.ascontiguousarray(dp2, dtype=np.float64)
+    assert d1.shape == d2.shape and d1.shape[2:] == (4, 4)
+    where = (C.c_int * 3)(-1, -1, -1)
+    if L.tse_test_remap_grids(d1.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p), d1.shape[0], d1.shape[1], where):
+        return tuple(where), L.tse_last_error().decode()
+    return None

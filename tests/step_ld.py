@@ -112,6 +112,20 @@ def mul(a, b):
     return T(a.v * b.v, a.A * b.A, a.m + b.m + 1)
 
 
+def mul_tight(a, b):
+    """a*b where |v| may lie far below A (a difference that cancelled, and its powers): the same count as mul, and the magnitude
+    taken from the absolute errors E = gamma_m * A of the factors instead of A_a * A_b:
+      |fl(a~ b~) - a b| <= |a| E_b + |b| E_a + E_a E_b + u (|a| + E_a)(|b| + E_b) =: err,   A = max(|v|, err / gamma_m), m = m_a + m_b + 1.
+    err <= gamma_m * A_a * A_b, so this is never looser than mul; the longdouble evaluation's own error obeys the same formula with
+    u = 2^-64, which bound() adds as gamma_m(2^-64) * A."""
+    m = a.m + b.m + 1
+    u = 2.0 ** -53
+    av, bv = np.abs(a.v), np.abs(b.v)
+    Ea, Eb = LD(gamma(a.m)) * a.A, LD(gamma(b.m)) * b.A
+    err = av * Eb + bv * Ea + Ea * Eb + LD(u) * (av + Ea) * (bv + Eb)
+    return T(a.v * b.v, np.maximum(av * bv, err / LD(gamma(m))), m)
+
+
 def part(a):
     """a quantity as one term of a sum: (v, A, count of the term, number of terms)"""
     return a.v, a.A, a.m, 1
@@ -125,6 +139,41 @@ def sum_parts(*parts):
 
 def add(*ts):
     return sum_parts(*[part(t) for t in ts])
+
+
+# ---- continuous, piecewise operations (the PPM remap, tests/remap_ld.py): no decision is taken on any of them ----
+def absval(a):
+    """|a|: exact on the value, the error is that of a"""
+    return T(np.abs(a.v), a.A, a.m)
+
+
+def minimum(*ts):
+    """min(a, b, ...).  min is 1-Lipschitz in the max norm, so |min(a,b)_fl - min(a,b)| <= max(err_a, err_b) whichever operand either
+    side picks; (A, m) = (max A_i, max m_i) gives gamma_m * A >= gamma_{m_i} * A_i for every i, and A >= |v|."""
+    v, A = ts[0].v, ts[0].A
+    for t in ts[1:]:
+        v, A = np.minimum(v, t.v), np.maximum(A, t.A)
+    return T(v, A, max(t.m for t in ts))
+
+
+def copysign_le(mag, da):
+    """copysign(mag, da) for a mag that is min(|da|, ...) on BOTH sides, so 0 <= mag <= |da| in exact arithmetic and in every fp64
+    evaluation.  Continuous through da = 0.  Same sign of da on both sides: the error is err_mag.  Opposite signs (or one side 0):
+    |r_fl - r| = mag_fl + mag <= |da_fl| + |da| = |da_fl - da| = err_da, because da_fl and da then lie on opposite sides of 0.
+    So |r_fl - r| <= max(err_mag, err_da): (A, m) = (max(A_mag, A_da), max(m_mag, m_da))."""
+    return T(np.where(np.signbit(da.v), -mag.v, mag.v), np.maximum(mag.A, da.A), max(mag.m, da.m))
+
+
+def select(cond, a, b):
+    """where(cond, a, b) of a decision taken elsewhere (the caller answers for the decision): value and magnitude of the chosen operand,
+    the larger count"""
+    return T(np.where(cond, a.v, b.v), np.where(cond, a.A, b.A), max(a.m, b.m))
+
+
+def cancel(t, where):
+    """t with T(0, 0, .) at the points `where`: a difference of a quantity and a copy of its own bits (a ghost cell and the cell it
+    mirrors, the two interface values of a flattened cell) is exactly 0 on both sides"""
+    return T(np.where(where, LD(0), t.v), np.where(where, LD(0), t.A), t.m)
 
 
 def contract(spec, C, t):

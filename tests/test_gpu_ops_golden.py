@@ -3,7 +3,9 @@ divergence_sphere, laplace_sphere_wk -- derivative_mod.F90:2364,2418 -- and rema
 called by oracle/ref/ref_harness.F90 on LCG inputs), with the reference's own metric terms (ref_ne2_static.npz).
 Tolerances (fp64): the device routines contract a*b+c into FMAs and re-associate the metric products of the Laplacian
 (tse_device.h), so agreement is to a few ulp of the slab's largest term: 1e-14 (divergence), 5e-14 (Laplacian) relative to
-the slab maximum; remap: TOL_STEP = 5e-13 of the field maximum, column mass to 1e-13."""
+the slab maximum; remap: TOL_STEP = 5e-13 of the field maximum, column mass to 1e-13.
+The remap checks here are norms of one reference-generated field: a thin top level may be wrong by hundreds of times what a thick one
+is allowed.  What a single level of a single column may be off by is asserted in test_gpu_remap_pointwise.py (tests/remap_ld.py)."""
 import numpy as np
 import pytest
 

@@ -307,6 +307,8 @@ def test_remap_column_loop_variants(ctx5, monkeypatch, nt, generic, squeeze):
         elem["divdp"][...] = o.divdp; elem["divdp_proj"][...] = o.divdp_proj
         hip.set_divdp(elem)
     o.vertical_remap(dt, 2)
+    hip.copy_qdp_d2h(elem, 2)
+    before = elem["Qdp"][:, 1].copy()
     hip.vertical_remap(dt, 2)
     hip.copy_qdp_d2h(elem, 2); hip.get_derived(elem)
     assert relerr(elem["dp3d"], o.dp3d) < 1e-15 and relerr(elem["ps_v"], o.ps_v) < 1e-15
@@ -314,6 +316,18 @@ def test_remap_column_loop_variants(ctx5, monkeypatch, nt, generic, squeeze):
         assert relerr(elem["Qdp"][:, 1, q], o.qdp[1][:, q]) < 4 * TOL_STEP, q
     mass_h = np.einsum("eji,eqkji->q", o.spheremp, elem["Qdp"][:, 1, :5]); mass_o = np.einsum("eji,eqkji->q", o.spheremp, o.qdp[1])
     assert np.all(np.abs(mass_h - mass_o) <= 1e-13 * np.abs(mass_o))
+    if nt == 2:
+        # every level is one fixed sequence of roundings "whatever loop produces it" (tse_kernels.h): two tracers per thread leave the
+        # bits of one tracer per thread, on the lockstep grid, through the generic loop and on the squeezed grid -- which ties NT = 2 to
+        # the route tests/test_gpu_remap_pointwise.py holds to the longdouble bound
+        two = elem["Qdp"][:, 1].copy()
+        elem["Qdp"][:, 1] = before
+        hip.copy_qdp_h2d(elem, 2)
+        monkeypatch.setenv("TSE_REMAP_NT", "1")
+        hip.vertical_remap(dt, 2)
+        hip.copy_qdp_d2h(elem, 2)
+        assert not np.array_equal(two, before)
+        assert np.array_equal(elem["Qdp"][:, 1].view(np.uint64), two.view(np.uint64)), "TSE_REMAP_NT=2 moved bits"
 
 
 def test_limiter_edge_cases_through_the_step(ctx5):

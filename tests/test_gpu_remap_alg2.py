@@ -2,7 +2,9 @@
 either end of a column are piecewise constant (prim_advection_mod.F90:230-250,283-341).  Checked against the reference's own
 outputs with that namelist value (tests/golden/ref_ne2_alg2.npz: oracle/ref/make_golden.py --alg2 = the reference harness run with
 TSE_NL_VERT_REMAP_Q_ALG=2), through the single operator call, the device-resident time loop, every column-loop variant of
-k_remap, and the Fortran seam.  Tolerance: 5e-13 of the field maximum per call / tracer step, as for the default algorithm."""
+k_remap, and the Fortran seam.  Tolerance: 5e-13 of the field maximum per call / tracer step, as for the default algorithm.
+These are field-maximum norms; the per-level, per-column claim for alg 2 (which cells are piecewise constant, and how far any single
+output may be off) is asserted against longdouble in test_gpu_remap_pointwise.py (tests/remap_ld.py)."""
 import json
 import os
 import subprocess

@@ -152,3 +152,84 @@ def test_host_tables(ne, world, strips):
     for rank in range(world):
         desc = cm.edge_descriptors(topo, owner, rank)
         check(desc, host_tables(desc, strips))
+
+
+# ---- the guard of tse_remap_q_ppm: check_remap_grids (csrc/tse_tables.cpp) ----
+def _grids(nlev=72, nelem=3, seed=3):
+    rng = np.random.default_rng(seed)
+    dp1 = 1000.0 * (1 + 0.2 * rng.random((nelem, nlev, 4, 4)))
+    dp2 = dp1 * (1 + 0.05 * (rng.random(dp1.shape) - 0.5))
+    dp2 *= dp1.sum(1, keepdims=True) / dp2.sum(1, keepdims=True)
+    return dp1, dp2
+
+
+def _serial_sum(x):
+    run = np.zeros_like(x[0])
+    for k in range(x.shape[0]):
+        run = run + x[k]
+    return run
+
+
+@pytest.mark.parametrize("nlev", [72, 64, 16])
+def test_remap_grid_guard_accepts_a_good_grid(nlev):
+    from host_tables import check_remap_grids
+    dp1, dp2 = _grids(nlev)
+    assert check_remap_grids(dp1, dp2) is None
+    assert check_remap_grids(dp1, dp1) is None                     # every interface a tie
+    z = dp2.copy(); z[1, 5, 2, 3] = 0.0                            # an empty target layer is a grid the search ends on
+    assert check_remap_grids(dp1, z) is None
+
+
+@pytest.mark.parametrize("kind", ["dp1 zero", "dp1 negative", "dp1 nan", "dp2 negative", "dp2 nan", "dp2 inf", "dp2 too long"])
+def test_remap_grid_guard_names_the_first_offender(kind):
+    """element, column (4*j + i) and level of the first bad entry in scan order, all counted from 0, in the message as well"""
+    from host_tables import check_remap_grids
+    dp1, dp2 = _grids()
+    e, k, j, i = 1, 40, 2, 1
+    if kind.startswith("dp1"):
+        dp1[e, k, j, i] = {"dp1 zero": 0.0, "dp1 negative": -3.0, "dp1 nan": np.nan}[kind]
+        dp1[2, 3, 0, 0] = -1.0                                     # a later offender is not the one reported
+    elif kind == "dp2 too long":
+        dp2[e, k, j, i] += dp2[e, k + 1:, j, i].sum() + 2.0        # the partial sum at level k reaches sum(dp1) + 1
+        dp2[e, 50, j, i] = -1.0                                    # (later in the same column)
+    else:
+        dp2[e, k, j, i] = {"dp2 negative": -1e-300, "dp2 nan": np.nan, "dp2 inf": np.inf}[kind]
+    where, msg = check_remap_grids(dp1, dp2)
+    assert where == (e, 4 * j + i, k), (where, msg)
+    assert "element %d, column %d, level %d" % (e, 4 * j + i, k) in msg and kind.split()[0] in msg, msg
+
+
+def test_remap_grid_guard_at_the_exact_boundary():
+    """a partial sum of dp2 below the last level is refused from sum(dp1) + 1 on (both in fp64, serial order), not before"""
+    from host_tables import check_remap_grids
+    nlev = 72
+    dp1 = np.full((1, nlev, 4, 4), 1024.0)                         # sums exact in fp64: sum(dp1) + 1 = 73729
+    end = float(_serial_sum(dp1[0])[0, 0]) + 1.0
+    assert end == 73729.0
+    dp2 = dp1.copy()
+    dp2[0, 10, 1, 1] = end - 10 * 1024.0                           # pin(12) == sum(dp1) + 1 exactly
+    where, msg = check_remap_grids(dp1, dp2)
+    assert where == (0, 5, 10) and "73729" in msg, (where, msg)
+    dp2[0, 10, 1, 1] = np.nextafter(end, 0.0) - 10 * 1024.0        # pin(12) one ulp below it: the search ends (at pio(nlev+2))
+    assert float(_serial_sum(dp2[0, :11])[1, 1]) == np.nextafter(end, 0.0)
+    dp2[0, 11:, 1, 1] = 0.0
+    assert check_remap_grids(dp1, dp2) is None
+    dp2[0, nlev - 1, 1, 1] = 1e9                                   # the last level's sum is replaced by pio(nlev+1): never compared
+    assert check_remap_grids(dp1, dp2) is None
+
+
+def test_remap_grid_guard_refuses_a_column_whose_sentinel_is_absorbed():
+    """from sum(dp1) = 2^53 on, sum(dp1) + 1 == sum(dp1): the last level searches for an entry above pin(nlev+1) = pio(nlev+1) and
+    pio(nlev+2) is not one.  Refused with the column named, whatever dp2 is; one ulp-step below 2^53 the sentinel holds"""
+    from host_tables import check_remap_grids
+    nlev = 72
+    dp1 = np.ones((2, nlev, 4, 4)); dp2 = np.ones((2, nlev, 4, 4))
+    dp1[1, 0, 3, 2] = 2.0 ** 54; dp2[1, 0, 3, 2] = 2.0 ** 53
+    where, msg = check_remap_grids(dp1, dp2)
+    assert where == (1, 14, nlev - 1) and "element 1, column 14" in msg and "sum(dp1)" in msg, (where, msg)
+    assert check_remap_grids(dp1, dp1)[0] == (1, 14, nlev - 1)
+    dp1[1, 0, 3, 2] = 2.0 ** 53 - (nlev - 1)                      # sum(dp1) == 2^53 exactly: still absorbed
+    assert float(_serial_sum(dp1[1])[3, 2]) == 2.0 ** 53
+    assert check_remap_grids(dp1, dp1)[0] == (1, 14, nlev - 1)
+    dp1[1, 0, 3, 2] = 2.0 ** 53 - nlev                            # sum(dp1) == 2^53 - 1: + 1 is exact and larger
+    assert check_remap_grids(dp1, dp1) is None

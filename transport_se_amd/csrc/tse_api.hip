@@ -1337,6 +1337,8 @@ int tse_laplace_sphere_wk(tse_ctx* c, const double* s, double* lap) { return ele
 // level fields dp/divdp_proj/dp3d as work space (a test/utility call, not part of the time loop).
 int tse_remap_q_ppm(tse_ctx* c, double* Qdp, const double* dp1, const double* dp2) {
   if (!Qdp || !dp1 || !dp2) return fail("tse_remap_q_ppm: null argument");
+  // before any upload or launch: a target grid the kernel's bracket search cannot end on never reaches the device (tse_tables.h)
+  { std::string err; if (check_remap_grids(dp1, dp2, c->nelemd, NLEV, nullptr, &err)) return fail("tse_remap_q_ppm: %s", err.c_str()); }
   set_bounds_cache(c, 0);
   c->dcmip_static = false;   // dp is overwritten below: the next tse_dcmip_step_inputs must write the prescribed values again
   const size_t lev = c->lev();
@@ -1352,7 +1354,7 @@ int tse_remap_q_ppm(tse_ctx* c, double* Qdp, const double* dp1, const double* dp
                          c->dp, c->divdp_proj, c->dp3d, c->ps_v, c->q(1), c->bad, (double*)nullptr, (double*)nullptr, generic, c->sink, (const double*)d2,
                          (const int*)nullptr, c->nelemd, c->lvl_tmp, RemapFuse{});
     };
-    if (c->remap_alg2) go(k_remap<1, true>); else go(k_remap<1, false>);
+    { Scope s(c, "remap_q_ppm"); if (c->remap_alg2) go(k_remap<1, true>); else go(k_remap<1, false>); }   // (tse_kernel_time("remap") counts it)
     if (hipGetLastError() != hipSuccess) { rc = fail("tse_remap_q_ppm: kernel launch failed"); break; }
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(Qdp, c->q(1), c->trc() * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail("tse_remap_q_ppm: download failed"); break; }
     rc = remap_check(c);
@@ -1569,6 +1571,12 @@ extern "C" int tse_test_table(void* h, const char* name, const void** data, size
   return fail("tse_test_table: no table named %s", name);
 }
 extern "C" void tse_test_tables_free(void* h) { delete (TseTestTables*)h; }
+// check_remap_grids (tse_tables.h) without a device: 0, or 1 with the offender in where[3] and the message in tse_last_error()
+extern "C" int tse_test_remap_grids(const double* dp1, const double* dp2, int nelem, int nlev, int* where) {
+  std::string err;
+  if (check_remap_grids(dp1, dp2, nelem, nlev, where, &err)) return fail("%s", err.c_str());
+  return 0;
+}
 #endif
 // the two switches reset their own groups only: the comm_* groups (tse_comm_timing) and all the others (tse_timing)
 static void reset_timers(tse_ctx* c, bool comm) {

@@ -52,4 +52,14 @@ struct HostTables {
 // strips: TSE_BOUNDARY_STRIPS (rank-boundary elements in patches of their own).  Returns 0, or 1 with the reason in *err.
 int build_tables(const tse_init_args& a, bool strips, HostTables* out, std::string* err);
 
+// The precondition of remap_Q_ppm's bracket search (k_remap: `while (pio(kk) <= pin(k+1)) kk++`), checked on the host before anything
+// reaches the device.  dp1, dp2: [e][nlev][16].  Per column, in the kernel's serial order, pio(k+1) = pio(k) + dp1(k) and
+// pin(k+1) = pin(k) + dp2(k) from 0; the search of level k < nlev ends only at pio(nlev+2) = pio(nlev+1) + 1, so it needs
+// pin(k+1) < pio(nlev+1) + 1; the last level uses pin(nlev+1) = pio(nlev+1) itself, so it needs pio(nlev+1) + 1 > pio(nlev+1) in
+// fp64, i.e. sum(dp1) < 2^53.  Refused: a dp1 that is not a finite positive number, a column whose sum(dp1) + 1 does not exceed
+// sum(dp1), a dp2 that is negative or not finite, a partial sum of dp2 below the last level that is >= sum(dp1) + 1 (both in fp64).
+// Returns 0, or 1 with the first offender in scan order (element, then column, then level; all counted from 0) in where[3] (if
+// given) and in *err.
+int check_remap_grids(const double* dp1, const double* dp2, int nelem, int nlev, int* where, std::string* err);
+
 }  // namespace tse
