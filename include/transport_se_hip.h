@@ -17,7 +17,7 @@
  *   - All functions return 0 on success, nonzero on error (the Fortran side then calls abortmp, as the
  *     reference does on every failure: parallel_mod.F90:274-287); tse_last_error() gives the message.
  *   - np = 4 and nlev are compile-time constants exactly as in the reference (dimensions_mod.F90:19,27).  nlev is a build
- *     setting of the library (-DNLEV=<n>; the multiples of 8 from 16 to 72 compile, 72 and 64 are tested): TSE_NLEV below is the DEFAULT build's value
+ *     setting of the library (-DNLEV=<n>; the multiples of 8 from 16 to 72 and 80 compile; 72, 64 and 80 are tested): TSE_NLEV below is the DEFAULT build's value
  *     (72, libtransport_se_hip.so), and a host must compare tse_nlev() with its own nlev before it passes any field.
  *   - Host arrays are passed as the address of element 1's field plus the byte stride between consecutive
  *     elements (element_t is a fixed-size derived type, element_mod.F90:112-221, so `elem(:)` is strided AoS);

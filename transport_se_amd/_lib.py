@@ -1,7 +1,9 @@
 """Loader/builder of libtransport_se_hip.so (in-tree; built by __graft_entry__.build()).
 
 The level count is a build-time setting of the library, as PLEV is of the reference: the default build (NLEV = 72) is
-libtransport_se_hip.so, a build for another level count n is libtransport_se_hip_L<n>.so (build(nlev=n), lib(nlev=n))."""
+libtransport_se_hip.so, a build for another level count n is libtransport_se_hip_L<n>.so (build(nlev=n), lib(nlev=n)).  The
+multiples of 8 from 16 to 72 and 80 compile (csrc/tse_kernels.h names the rules); NLEV_BUILDS are the ones built and tested beside the
+default: 64 (the reference's 12k_top-64 grid) and 80 (one remap element per CU; nothing above 80 builds)."""
 import ctypes as C
 import os
 import subprocess
@@ -40,7 +42,7 @@ class InitArgs(C.Structure):
 HOOKS_SO = os.path.join(HERE, "libtransport_se_hip_hooks.so")
 HOOKS_FLAGS = ["-DTSE_AB_HOOKS"]
 DEFAULT_NLEV = 72   # the level count of the default build (csrc/tse_layout.h; TSE_NLEV of the header)
-NLEV_BUILDS = (64,)   # the other level counts __graft_entry__.build() ships
+NLEV_BUILDS = (64, 80)   # the other level counts __graft_entry__.build() ships
 
 
 def so_path(nlev=None):

@@ -1058,7 +1058,7 @@ __global__ __launch_bounds__(Patch::THREADS) void k_dss_patch(int qsize, const d
 // (prim_advection_mod.F90:911-919,943-957), out of place (the neighbours read src).  src/dst carry src_lev/dst_lev levels per
 // element (eta_dot_dpdn: nlev+1; the extra level is copied through), so no staging copies are needed and the caller just
 // swaps the two buffers.  Lanes flattened over (element slot, level pair, row); all gathers issued before any use.
-constexpr int LVL_UNITS = (NLEV / 2) * 4;   // lanes per element: NLEV/2 level pairs (k, k+NLEV/2) x 4 rows (72 levels: 144 lanes, 64: 128)
+constexpr int LVL_UNITS = (NLEV / 2) * 4;   // lanes per element: NLEV/2 level pairs (k, k+NLEV/2) x 4 rows (72 levels: 144 lanes, 64: 128, 80: 160)
 static_assert(NLEV % 2 == 0, "k_dss_lvl: a lane does the level pair (k, k + NLEV/2): NLEV must be even");
 template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
 __global__ __launch_bounds__(DSS_FLAT_THREADS) void k_dss_lvl(int nelemd, const int2* __restrict__ tab, const double* __restrict__ rspheremp,
@@ -1174,7 +1174,8 @@ __global__ void k_time_avg(size_t n, int rkstage, const double* __restrict__ Qn0
 }
 
 // ---------------------------------------------------------------------------------------------------
-// vertical_remap + remap_Q_ppm (prim_advection_mod.F90:1242-1330, 98-356).  Block = element, 4 waves; TWO blocks share a CU.
+// vertical_remap + remap_Q_ppm (prim_advection_mod.F90:1242-1330, 98-356).  Block = element, 4 waves; TWO blocks share a CU
+// (up to 72 levels; the 80-level build holds one: REMAP_PER_CU below).
 // Phase 1 (grid part, once per column): dp3d, ps_v, target dp, interface sums, bracket search kid/z2, the PPM grid
 // coefficients per level -> LDS.  Phase 2: thread = (tracer q, column p) streams down the column keeping a 5-cell window of
 // cell means in registers (kid(k) >= k-1 by construction of the search, :160-166, so the in-place update never overtakes
@@ -1218,7 +1219,13 @@ struct RemapLds {
   __device__ double* dB() { return &ca[0][0][0] + NLEV; }                                     // hybi(k+1)-hybi(k)
 };
 static_assert(2 * NLEV <= (NLEV + 1) * 3 * 16, "phase-1 scratch fits the coefficient arrays");
-static_assert(2 * sizeof(RemapLds) <= 160 * 1024, "two elements per CU (160 KB of LDS): NLEV <= 72");
+// 80 levels (88.6 KB) are admitted with ONE element per CU: the grid phase of an element then runs beside no other element's
+// column loop, and the CU holds one wave per SIMD.  Nothing else depends on the co-residency -- the XCD dealing of k_remap
+// goes by block index, no grid size is derived from an occupancy, and the DSS on read gathers neighbour entries that the
+// tracer step wrote before the launch.  No other count above 72 is built or tested, so none compiles.
+constexpr int REMAP_PER_CU = 2 * sizeof(RemapLds) <= 160 * 1024 ? 2 : 1;   // resident blocks (elements) per CU
+static_assert(REMAP_PER_CU == 2 || (NLEV == 80 && sizeof(RemapLds) <= 160 * 1024),
+              "two elements per CU (160 KB of LDS): NLEV <= 72; 80 runs one element per CU");
 static_assert(NLEV <= REMAP_THREADS, "one thread per level forms the hybrid-coefficient differences: NLEV <= 256");
 static_assert(NLEV + 1 <= 255, "kid(k) is a byte: NLEV <= 254");
 // The column arithmetic below is compiled WITHOUT implicit FMA contraction and spells its fused operations out: what the
@@ -1742,7 +1749,7 @@ __device__ __forceinline__ void remap_columns_fast(const RemapLds& S, double* __
 #pragma clang fp contract(fast)   // (the default of the rest of the file)
 
 template <int NT, bool ALG2 = false, bool FUSED = false>
-__global__ __launch_bounds__(REMAP_THREADS / NT, NT == 1 ? 2 : 1 /* <= 256 registers: two blocks per CU */) void k_remap(
+__global__ __launch_bounds__(REMAP_THREADS / NT, NT == 1 ? REMAP_PER_CU : 1 /* <= 256 registers: two blocks per CU (80 levels: one) */) void k_remap(
     int qsize, double dt, double ps0, const double* __restrict__ hyai, const double* __restrict__ hybi, const double* __restrict__ dp,
     const double* __restrict__ divdp_proj, double* __restrict__ dp3d, double* __restrict__ ps_v, double* __restrict__ Q, int* __restrict__ bad,
     double* __restrict__ mn_out, double* __restrict__ mx_out, int force_generic, double* __restrict__ sink,
@@ -1788,7 +1795,7 @@ __global__ __launch_bounds__(REMAP_THREADS / NT, NT == 1 ? 2 : 1 /* <= 256 regis
     // pressure pio(nlev+1) (:142-144: the same terms added in the same order from 0), so it is not summed a second time; the
     // hybrid coefficient differences of the target grid (:1316-1317) wait in LDS instead of behind one scalar load per level.
     const int p = tid;
-    constexpr int SB = NLEV % 16 == 0 ? 16 : NLEV % 12 == 0 ? 12 : 8;   // 12 at 72 levels, 16 at 64
+    constexpr int SB = NLEV % 16 == 0 ? 16 : NLEV % 12 == 0 ? 12 : 8;   // 12 at 72 levels, 16 at 64 and 80
     static_assert(NLEV % SB == 0, "scan batches: NLEV must be a multiple of 8");
     double run = 0.0;
     pio[0][p] = 0.0;

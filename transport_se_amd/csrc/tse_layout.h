@@ -12,8 +12,8 @@
 #define NP 4
 // The level count is a build-time setting, as the reference's PLEV (dimensions_mod.F90:27): a build may pass -DNLEV=<n>
 // (NLEVP follows).  The default is 72.  The static_asserts of the kernels name the rules, which together allow the multiples of
-// 8 from 16 to 72 (tse_kernels.h: the remap's blocks of 8 levels and its two elements per CU); anything else fails to compile.
-// Those values compile; 72 and 64 are the ones built and tested.
+// 8 from 16 to 72 and 80 (tse_kernels.h: the remap's blocks of 8 levels and its two elements per CU -- one at 80); anything else
+// fails to compile.  Those values compile; 72, 64 and 80 are the ones built and tested.
 #ifndef NLEV
 #define NLEV 72
 #endif

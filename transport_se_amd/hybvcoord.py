@@ -3,7 +3,7 @@ ascii files the reference's namelists name (test/dcmip1-1/dcmip1-1.nl: vcoord/ac
 files are shipped as data under transport_se_amd/data/vcoord/.  Any level count is read (the reference's plev is a build setting:
 dimensions_mod.F90:27); the library that runs it must be built for the same count (_lib.lib(nlev=...), tse_nlev()).
 The reference's other grids (test/dcmip1-1/dcmip1-1.nl: vcoord/12k_top-64{m,i}.ascii) are not shipped: a namelist names the
-user's own copy."""
+user's own copy (tests/golden/vcoord holds the 64-level pair and an 80-level pair made by the same rule)."""
 import os
 
 import numpy as np
