@@ -63,8 +63,10 @@ typedef struct {
   int qsize;           /* active tracers */
   int device;          /* HIP device ordinal, -1 = current */
   double nu_q;         /* control_mod nu_q */
-  int limiter_option;  /* 8: the optimization-based limiter (prim_advection_mod.F90:858,880); 0: no limiter (control_mod's default).
-                          Every other value is refused.  With 0 no tracer bounds are kept: tse_get_qminmax fails. */
+  int limiter_option;  /* 8: the optimization-based limiter (prim_advection_mod.F90:858,880); 9: the clip-and-sum limiter (the same bounds as
+                          8: one clip to them, the clipped mass redistributed in proportion to the room left; qmin is not clamped
+                          at 0); 0: no limiter (control_mod's default).  Every other value is refused.  With 0 no tracer bounds are
+                          kept: tse_get_qminmax fails. */
   int rsplit;          /* control_mod rsplit (vertical remap frequency), informational */
   const double *Dvv;   /* deriv%Dvv(np,np), Fortran order */
   const double *hyai;  /* hvcoord%hyai(nlevp) */

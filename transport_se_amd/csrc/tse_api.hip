@@ -30,7 +30,7 @@ using namespace tse;
 namespace tse {   // tse_stage3.hip: k_advance<2,3> lives in a translation unit of its own (another scheduler strategy)
 void launch_advance23(unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
                       const double* B, const double* lapT, double* C, const double* vn0, const double* dp, const double* divdp,
-                      const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga, bool lim);
+                      const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga, int limiter_option);
 }
 
 // TSE_DSS_ON_READ=0 falls back to one DSS pass per stage in the whole-step call (the per-stage API always does that)
@@ -69,9 +69,12 @@ struct PatchSet {
 struct tse_ctx {
   int nelemd = 0, qsize = 0, device = 0, rsplit = 3;
   bool remap_alg2 = false;   // control_mod vert_remap_q_alg == 2: piecewise-constant boundary cells in the PPM remap
-  // control_mod limiter_option: 8 (true) or 0 (false).  Unlimited, no kernel reads or writes qmin/qmax(2): the kernels without the
+  // control_mod limiter_option: 8 or 9 (true) or 0 (false).  Unlimited, no kernel reads or writes qmin/qmax(2): the kernels without the
   // limiter (LIM = false) run, and no element bounds are formed, exchanged or reduced over neighbours (prim_advection_mod.F90:858,880).
+  // limiter_option itself picks what a limited k_advance does inside a slab (8: limiter8_quad, 9: limiter9_quad, clip-and-sum); the
+  // bounds work is the same for both.
   bool lim = true;
+  int limiter_option = 8;
   double nu_q = 0, ps0 = 0;
   Dvv_t D;
   hipStream_t stream = nullptr;
@@ -333,7 +336,8 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
   c->nelemd = a->nelemd; c->qsize = a->qsize; c->nu_q = a->nu_q; c->ps0 = a->ps0; c->rsplit = a->rsplit;
   c->exchange = a->exchange; c->exchange_user = a->exchange_user;
   c->remap_alg2 = a->vert_remap_q_alg == 2;
-  c->lim = a->limiter_option == 8;
+  c->lim = a->limiter_option == 8 || a->limiter_option == 9;
+  c->limiter_option = a->limiter_option;
   memcpy(c->D.d, a->Dvv, sizeof c->D.d);
   { std::vector<double> dv(a->Dvv, a->Dvv + 16); if (upload(&c->dvv_d, dv)) return 1; }
   HIPCHK(hipStreamCreate(&c->stream));   // blocking w.r.t. the legacy default stream: see the note above split_stage
@@ -432,8 +436,9 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
 int tse_init(tse_ctx** out, const tse_init_args* a) {
   if (!out || !a) return fail("tse_init: null argument");
   *out = nullptr;
-  if (a->limiter_option != 8 && a->limiter_option != 0)
-    return fail("tse_init: limiter_option=%d (supported: limiter_option=8, the optimization-based limiter, and 0, no limiter)", a->limiter_option);
+  if (a->limiter_option != 8 && a->limiter_option != 9 && a->limiter_option != 0)
+    return fail("tse_init: limiter_option=%d (supported: limiter_option=8, the optimization-based limiter, 9, the clip-and-sum limiter, and 0, no limiter)",
+                a->limiter_option);
   if (a->nelemd <= 0 || a->qsize <= 0) return fail("tse_init: nelemd=%d qsize=%d", a->nelemd, a->qsize);
   if (a->vert_remap_q_alg < 0 || a->vert_remap_q_alg > 2)
     return fail("tse_init: vert_remap_q_alg=%d (0|1: mirrored ghost cells, 2: piecewise-constant boundary cells; control_mod.F90:61-66)", a->vert_remap_q_alg);
@@ -951,13 +956,21 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
     set_bounds_cache(c, 0);
     if (neighbor_minmax(c)) return 1;
     Scope s(c, "advance0");
-    hipLaunchKernelGGL(k_advance<0>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr, c->T, c->vn0,
-                       c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    if (c->limiter_option == 9)
+      hipLaunchKernelGGL((k_advance<0, 0, false, true, 9>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
+                         c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    else
+      hipLaunchKernelGGL(k_advance<0>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr, c->T, c->vn0,
+                         c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
     LAUNCH_CHECK();
   } else if (rhs == 1) {
     Scope s(c, "advance1");
-    hipLaunchKernelGGL(k_advance<1>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr, c->T, c->vn0,
-                       c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    if (c->limiter_option == 9)
+      hipLaunchKernelGGL((k_advance<1, 0, false, true, 9>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
+                         c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    else
+      hipLaunchKernelGGL(k_advance<1>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr, c->T, c->vn0,
+                         c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
     LAUNCH_CHECK();
   } else {
     c->t_zero_dirty = true;   // below, T receives rspheremp*DSS(lap) in the plain tracer layout
@@ -981,7 +994,10 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
     if (dss_tracer_pass(c, c->B, c->T, nullptr)) return 1;
     if (c->lim && neighbor_minmax(c)) return 1;
     Scope s(c, "advance2");
-    if (c->lim)
+    if (c->limiter_option == 9)
+      hipLaunchKernelGGL((k_advance<2, 0, false, true, 9>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0, c->dp,
+                         c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    else if (c->lim)
       hipLaunchKernelGGL(k_advance<2>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0, c->dp, c->divdp,
                          c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
     else
@@ -1140,7 +1156,10 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
           if (!w.nwork) return 0;
           GatherArgs ga = gargs(w, c->divdp_proj, NLEV);
           ga.divdp_out = c->divdp;
-          if (c->lim)
+          if (c->limiter_option == 9)
+            hipLaunchKernelGGL((k_advance<0, 0, false, true, 9>), dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q,
+                               (const double*)Qn0, (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, ga);
+          else if (c->lim)
             hipLaunchKernelGGL(k_advance<0>, dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, (const double*)Qn0,
                                (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, ga);
           else
@@ -1154,7 +1173,11 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   if (split_stage(c, "advance1",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
-          if (c->lim)
+          if (c->limiter_option == 9)
+            hipLaunchKernelGGL((k_advance<1, 1, true, true, 9>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(),
+                               c->qsize, dts, c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin,
+                               c->qmax, c->dp0, gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
+          else if (c->lim)
             hipLaunchKernelGGL((k_advance<1, 1, true>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts,
                                c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0,
                                gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
@@ -1188,7 +1211,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
         [&](Work w) -> int {
           if (!w.npwork) return 0;
           launch_advance23(patch_blocks(w.npwork), c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, c->B, c->T, c->C, c->vn0, c->dp,
-                           c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, gargs(w, c->omega_p, NLEV), c->lim);   // (tse_stage3.hip)
+                           c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, gargs(w, c->omega_p, NLEV), c->limiter_option);   // (tse_stage3.hip)
           LAUNCH_CHECK(); return 0; },
         [&]() -> int { return pack_tracers(c, cs, c->C, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->C, nqv, nqv); })) return 1;
   if (defer_dss) {   // C (halo columns filled: the stage's exchange is ordered before the next launch on the compute stream) waits for the remap

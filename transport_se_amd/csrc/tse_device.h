@@ -228,4 +228,41 @@ __device__ __forceinline__ bool limiter8_quad(double x[4], const double c[4], do
   return lo | hi;
 }
 
+// The clip-and-sum limiter (limiter_option = 9) on one slab spread over a quad; arguments and return value as limiter8_quad's.
+// The bounds are relaxed as limiter 8 relaxes them; then one clip to [minp,maxp] and one redistribution of the clipped mass in
+// proportion to the room each point has left towards the bound the mass moves to (v = maxp - x going up, x - minp going down):
+// no iteration and no wave-wide vote.  1/sumc does not depend on the tracer, so after inlining it is formed once per slab and the
+// relaxed bound costs a product; the one division per tracer is addmass/den.  den <= 0 (every point pinned, e.g. minp == maxp, or
+// nothing clipped on a flat slab): nothing is added -- an infinite or NaN quotient must not reach x, as for w <= 0 in limiter 8.
+// No implicit contraction: the kernels that inline this (and the two copies of the loop body in the double-buffered ones) must give
+// a slab the same bits.
+__device__ __forceinline__ bool limiter9_quad(double x[4], const double c[4], double sumc, double& minp, double& maxp) {
+#pragma clang fp contract(off)
+  if (!(sumc > 0.0)) return false;  // whole quad takes the same branch
+  const double mass = quad_sum(((c[0] * x[0] + c[1] * x[1]) + c[2] * x[2]) + c[3] * x[3]);
+  const bool lo = mass < minp * sumc, hi = mass > maxp * sumc;
+  const double r = mass * (1.0 / sumc);
+  minp = lo ? r : minp;
+  maxp = hi ? r : maxp;
+  double xc[4], addmass = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    xc[i] = fmin(fmax(x[i], minp), maxp);
+    addmass = addmass + (x[i] - xc[i]) * c[i];
+  }
+  addmass = quad_sum(addmass);
+  const bool up = addmass > 0.0;
+  double v[4], den = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    v[i] = up ? maxp - xc[i] : xc[i] - minp;
+    den = den + v[i] * c[i];
+  }
+  den = quad_sum(den);
+  const double inc = den > 0.0 ? addmass / den : 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) x[i] = fma(inc, v[i], xc[i]);
+  return lo | hi;
+}
+
 }  // namespace tse

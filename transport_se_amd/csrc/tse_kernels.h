@@ -582,6 +582,8 @@ __global__ void k_zero_slot(int qsize, double* __restrict__ dst, Scr S, unsigned
 //   Vstar = vn0/dp, dp_star = dp - dt*divdp, Qtens = Qdp - dt*div(Vstar*Qdp) [+ biharmonic], limiter8, *spheremp.
 // LIM = false (limiter_option = 0): Qtens = Qdp - dt*div(Vstar*Qdp) [+ biharmonic], *spheremp -- no dp_star, no bounds read,
 // formed or written, no limiter (:858,880 apply limiter_optim_iter_full only under limiter_option == 8).
+// LOPT (with LIM only): the limiter applied to the slab -- 8: limiter8_quad, 9: limiter9_quad (clip-and-sum).  Bounds, dp_star and the
+// write-back of relaxed bounds are the same for both.
 // RHS = rhs_multiplier.  RHS==1 folds in the local min/max update (:781-793).  RHS==2 folds in the second
 // Laplacian of the biharmonic and its scaling (viscosity_mod.F90:419-423 + prim_advection_mod.F90:813-826);
 // `lap` then holds rspheremp*DSS(laplace_sphere_wk(Q)).
@@ -591,7 +593,7 @@ __global__ void k_zero_slot(int qsize, double* __restrict__ dst, Scr S, unsigned
 // (the exported lines k_lap1<1> stored) -- and so are the element bounds.  Stage 3 never needs the DSS'd stage-2 tracers in memory.
 // Register tiers (512 VGPRs per SIMD lane): 128 -> 4 waves, 168 -> 3, 256 -> 2.  Forcing the stage-2 DSS-on-read kernel
 // (170) into the 3-wave tier with amdgpu_waves_per_eu costs 2 spills and gains nothing measurable.
-template <int RHS, int GIN = 0, bool DB = (GIN != 0), bool LIM = true>
+template <int RHS, int GIN = 0, bool DB = (GIN != 0), bool LIM = true, int LOPT = 8>
 __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_advance(int nelemd, Dvv_t D, GeoPtrs G, int qsize, double dt, double nu_q,
                                                           const double* __restrict__ Qn0, const double* __restrict__ lap,
                                                           double* __restrict__ Tout, const double* __restrict__ vn0,
@@ -599,6 +601,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
                                                           const double* __restrict__ divdp_proj, double* __restrict__ qmin,
                                                           double* __restrict__ qmax, const double* __restrict__ dp0, GatherArgs GA) {
   static_assert(GIN == 0 || GIN == 1 || (GIN == 3 && RHS == 2), "plain inputs, gathered tracers, or gathered tracers and Laplacian");
+  static_assert(LOPT == 8 || (LOPT == 9 && LIM), "limiter 8, or clip-and-sum with the bounds work on");
   __shared__ PatchLds lds_[GIN == 3 ? 2 : 1];   // (unused and removed by the compiler when GIN == 0)
   __shared__ BoundsLds bnd_;                    // (GIN == 3 with LIM only)
   // Stage 3 forms the first Laplacian and the element bounds of its patch's OWN slots itself (OWNLAP; below): k_lap1 only has to
@@ -835,7 +838,8 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
     if (LIM) {
 #pragma unroll
       for (int i = 0; i < 4; i++) x[i] = x[i] * rdps[i];
-      changed |= limiter8_quad(x, c, sumc, minp, maxp);
+      if (LOPT == 9) changed |= limiter9_quad(x, c, sumc, minp, maxp);
+      else changed |= limiter8_quad(x, c, sumc, minp, maxp);
 #pragma unroll
       for (int i = 0; i < 4; i++) cur.x[i] = c[i] * x[i];   // spheremp * (x*dp_star)
       cur.mn = minp; cur.mx = maxp; cur.ch = changed;   // unchanged bounds are not written back (3.5 GB per launch)

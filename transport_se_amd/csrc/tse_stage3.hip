@@ -11,14 +11,18 @@
 
 namespace tse {
 
-// launch k_advance<2,3,true> over `blocks` (patch, chunk) blocks; the arguments are the kernel's.  lim = false: the kernel without the
-// limiter (k_advance<2,3,true,false>: no bounds image, no dp_star, qmin/qmax not touched)
+// launch k_advance<2,3,true> over `blocks` (patch, chunk) blocks; the arguments are the kernel's.  limiter_option 8: limiter 8;
+// 9: clip-and-sum (k_advance<2,3,true,true,9>); 0: the kernel without the limiter (k_advance<2,3,true,false>: no bounds image, no
+// dp_star, qmin/qmax not touched)
 void launch_advance23(unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
                       const double* B, const double* lapT, double* C, const double* vn0, const double* dp, const double* divdp,
-                      const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga, bool lim) {
-  if (lim)
+                      const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga, int limiter_option) {
+  if (limiter_option == 8)
     hipLaunchKernelGGL((k_advance<2, 3, true>), dim3(blocks), dim3(Patch::THREADS), 0, stream, nelemd, D, G, qsize, dt, nu_q, B, lapT, C, vn0, dp, divdp,
                        divdp_proj, qmin, qmax, dp0, ga);
+  else if (limiter_option == 9)
+    hipLaunchKernelGGL((k_advance<2, 3, true, true, 9>), dim3(blocks), dim3(Patch::THREADS), 0, stream, nelemd, D, G, qsize, dt, nu_q, B, lapT, C, vn0, dp,
+                       divdp, divdp_proj, qmin, qmax, dp0, ga);
   else
     hipLaunchKernelGGL((k_advance<2, 3, true, false>), dim3(blocks), dim3(Patch::THREADS), 0, stream, nelemd, D, G, qsize, dt, nu_q, B, lapT, C, vn0, dp,
                        divdp, divdp_proj, (double*)nullptr, (double*)nullptr, dp0, ga);

@@ -116,7 +116,7 @@ class PrimRun:
                  dist_mod=None, torch_mod=None, exchange="rccl", vert_remap_q_alg=0, limiter_option=8, hvcoord=None):
         """exchange (world > 1): "rccl" = in-library RCCL send/recv (production), "torch" = torch.distributed P2P ops in the
         exchange callback, "staged" = callback with host-staged slots over a CPU backend (ranks may share a GPU).
-        limiter_option: 8 (optimization-based limiter) or 0 (no limiter), as control_mod's.
+        limiter_option: 8 (optimization-based limiter), 9 (clip-and-sum limiter) or 0 (no limiter), as control_mod's.
         hvcoord: the vertical coordinate (an HvCoord; default: the shipped acme-72 grid); its level count selects the library
         (_lib.lib(nlev=)) and every level extent below."""
         self.ne, self.qsize, self.rsplit, self.test_case = ne, qsize, rsplit, test_case

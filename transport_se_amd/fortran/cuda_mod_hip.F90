@@ -237,7 +237,8 @@ contains
     ! replaced by the default behaviour: the tracer time levels assume qsplit = 1 (TimeLevel_Qdp, time_mod.F90:85-109), the
     ! hyperviscosity is the single constant-coefficient application of euler_step (prim_advection_mod.F90:796-826; no tracer
     ! subcycling, no variable / tensor coefficient: derivative_mod.F90:2438-2445), the remap is remap_Q_ppm with ghost-cell
-    ! variant 0|1 or 2 (prim_advection_mod.F90:230-341).
+    ! variant 0|1 or 2 (prim_advection_mod.F90:230-341).  limiter_option needs no check here: control_mod's value goes into
+    ! tse_init_args below, and tse_init takes 8 (optimization-based), 9 (clip-and-sum) and 0 (none) and refuses every other value.
     if (qsplit /= 1) call seam_abort('cuda_mod_init(hip): qsplit must be 1')
     if (hypervis_subcycle_q /= 1) call seam_abort('cuda_mod_init(hip): hypervis_subcycle_q must be 1')
     if (hypervis_power /= 0 .or. hypervis_scaling /= 0) call seam_abort('cuda_mod_init(hip): hypervis_power and hypervis_scaling must be 0')

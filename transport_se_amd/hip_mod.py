@@ -39,7 +39,7 @@ def _vp(a):
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
-        """cuda_mod_init.  hvcoord = (hyai, hybi, ps0).  schedule = dict(send=[(peer, ptrP, lengthP)...],
+        """cuda_mod_init.  hvcoord = (hyai, hybi, ps0).  limiter_option: 8, 9 (clip-and-sum) or 0 (none); tse_init refuses any other.  schedule = dict(send=[(peer, ptrP, lengthP)...],
         recv=[...]) as in Schedule(1)%SendCycle/RecvCycle; exchange(sendbuf_ptr, recvbuf_ptr, nlyr, kind) -> 0.
         lib_path: another build of the same sources (_lib.HOOKS_SO: the tests' fault injection) instead of the product library.
         nlev: the level count (default: that of hvcoord, len(hyai) - 1); the library built for it is loaded (_lib.lib(nlev=))."""

@@ -97,8 +97,9 @@ def settings(groups):
         s["nmax"] = int(s["ndays"] * 86400 / s["tstep"])       # namelist_mod.F90:347-351
     if s["nu_q"] < 0:
         s["nu_q"] = s["nu"]                                    # :700
-    if s["limiter_option"] not in (0, 8):   # 0 (control_mod's default) runs unlimited; any other value would too in the reference
-        raise SystemExit("prim_main: limiter_option = %r is not supported (8: the optimization-based limiter, 0: no limiter)" % (s["limiter_option"],))
+    if s["limiter_option"] not in (0, 8, 9):   # 0 (control_mod's default) runs unlimited; any other value would too in the reference
+        raise SystemExit("prim_main: limiter_option = %r is not supported (8: the optimization-based limiter, 9: the clip-and-sum limiter, "
+                         "0: no limiter)" % (s["limiter_option"],))
     if s["rsplit"] <= 0 or s["qsplit"] != 1:
         raise SystemExit("prim_main: needs rsplit > 0 (vertically lagrangian) and qsplit = 1")
     # what the device path does not implement is refused, never silently replaced (the Fortran seam aborts on the same keys)
