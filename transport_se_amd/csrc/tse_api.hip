@@ -1600,6 +1600,57 @@ extern "C" int tse_test_remap_grids(const double* dp1, const double* dp2, int ne
   if (check_remap_grids(dp1, dp2, nelem, nlev, where, &err)) return fail("%s", err.c_str());
   return 0;
 }
+// The slab limiters alone (tests/test_gpu_limiter_slab.py): limiter8_quad / limiter9_quad called as k_advance calls them.  One wave per
+// block; lane l owns row l & 3 of slab l >> 2 of its wave, so slab s of the batch sits in wave s / 16 and the caller chooses its
+// wave-mates.  sumc is formed as k_advance forms it.  x comes back as the limiter leaves it (not x * dp), the bounds in place, the
+// return value in changed.  The arrays hold whole waves (tse_test_limiter pads them).
+template <int LOPT>
+__global__ __launch_bounds__(64) void k_test_limiter(double* __restrict__ x, const double* __restrict__ c, double* __restrict__ minp,
+                                                     double* __restrict__ maxp, int* __restrict__ changed) {
+  const int s = blockIdx.x * 16 + (threadIdx.x >> 2), j = threadIdx.x & 3;
+  double xr[4], cr[4];
+  load4(x + (size_t)s * 16 + j * 4, xr);
+  load4(c + (size_t)s * 16 + j * 4, cr);
+  double mn = minp[s], mx = maxp[s];
+  const double sumc = quad_sum(((cr[0] + cr[1]) + cr[2]) + cr[3]);
+  const bool ch = LOPT == 9 ? limiter9_quad(xr, cr, sumc, mn, mx) : limiter8_quad(xr, cr, sumc, mn, mx);
+  store4(x + (size_t)s * 16 + j * 4, xr);
+  if (j == 0) { minp[s] = mn; maxp[s] = mx; changed[s] = ch; }
+}
+// option: 8 | 9.  x, c: [nslab][4][4] (x in/out); minp, maxp: [nslab] (in/out); changed: [nslab].  Needs no tse_ctx: it allocates, copies,
+// launches and frees on the current device.  nslab is padded to whole waves with copies of the last slab.
+extern "C" int tse_test_limiter(int option, int nslab, double* x, const double* c, double* minp, double* maxp, int* changed) {
+  if (option != 8 && option != 9) return fail("tse_test_limiter: option %d (8 or 9)", option);
+  if (nslab <= 0 || !x || !c || !minp || !maxp || !changed) return fail("tse_test_limiter: no slabs or a null argument");
+  const size_t n = (size_t)nslab, npad = (n + 15) / 16 * 16;
+  std::vector<double> h(npad * 34);   // x, c, minp, maxp
+  double *hx = h.data(), *hc = hx + npad * 16, *hmn = hc + npad * 16, *hmx = hmn + npad;
+  for (size_t s = 0; s < npad; s++) {
+    const size_t f = std::min(s, n - 1);
+    memcpy(hx + s * 16, x + f * 16, 128); memcpy(hc + s * 16, c + f * 16, 128);
+    hmn[s] = minp[f]; hmx[s] = maxp[f];
+  }
+  double* d = nullptr; int* dch = nullptr;
+  std::vector<int> hch(npad);
+  int rc = 0;
+  do {
+    if (hipMalloc((void**)&d, npad * 34 * 8) != hipSuccess || hipMalloc((void**)&dch, npad * 4) != hipSuccess) { rc = fail("tse_test_limiter: cannot allocate"); break; }
+    if (hipMemcpy(d, hx, npad * 34 * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("tse_test_limiter: upload failed"); break; }
+    double *dx = d, *dc = dx + npad * 16, *dmn = dc + npad * 16, *dmx = dmn + npad;
+    if (option == 9) hipLaunchKernelGGL(k_test_limiter<9>, dim3((unsigned)(npad / 16)), dim3(64), 0, 0, dx, dc, dmn, dmx, dch);
+    else hipLaunchKernelGGL(k_test_limiter<8>, dim3((unsigned)(npad / 16)), dim3(64), 0, 0, dx, dc, dmn, dmx, dch);
+    if (hipGetLastError() != hipSuccess) { rc = fail("tse_test_limiter: kernel launch failed"); break; }
+    if (hipDeviceSynchronize() != hipSuccess) { rc = fail("tse_test_limiter: the kernel failed"); break; }
+    if (hipMemcpy(hx, d, npad * 34 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hch.data(), dch, npad * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+      rc = fail("tse_test_limiter: download failed"); break;
+    }
+    memcpy(x, hx, n * 128);
+    for (size_t s = 0; s < n; s++) { minp[s] = hmn[s]; maxp[s] = hmx[s]; changed[s] = hch[s]; }
+  } while (0);
+  if (rc) (void)hipGetLastError();
+  (void)hipFree(d); (void)hipFree(dch);
+  return rc;
+}
 #endif
 // the two switches reset their own groups only: the comm_* groups (tse_comm_timing) and all the others (tse_timing)
 static void reset_timers(tse_ctx* c, bool comm) {
