@@ -227,14 +227,34 @@ int tse_copy_q_d2h(tse_ctx *ctx, double *q_elem1, size_t elem_stride, int qsize_
 /* elem(ie)%state%lnps(:,:,np1) <- device lnps; lnps_elem1 = address of elem(1)%state%lnps(1,1,np1) */
 int tse_copy_lnps_d2h(tse_ctx *ctx, double *lnps_elem1, size_t elem_stride);
 
+/* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
+ * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
+ * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
+ * adds the shares exactly (math.fsum, repro_sum) and gets the same bits on any number of ranks.  No tracer field crosses to the host.
+ * tse_norm_setup:
+ *   owner[nelemd][16]: 1 where this element's point is the owner of its GLL column (dof_mod.F90:43-57), else 0;
+ *   colw[nelemd][16]: horizontal weight of the column (the NCL script's R cos(lat) dlon * R dlat), read only where owner = 1;
+ *   dh[nlev]: layer depths of the script's "2*(h-base)" recursion.  Copied to the device; may be called again. */
+int tse_norm_setup(tse_ctx *ctx, const int *owner, const double *colw, const double *dh);
+/* snapshot Q0 = Qdp(nt)[tracer q]/dp as the reference field (one tracer-slot field, allocated by the first call; stays valid through
+ * every later state change; a second call overwrites it) and return sum0[nelemd] = sum over owned points and levels of Q0 (unweighted).
+ * q counts from 0.  Q is formed as tse_state_q forms it (dp from the current ps_v, a true division): bit for bit the host's Qdp/dp. */
+int tse_norm_reference(tse_ctx *ctx, int nt, int q, double *sum0);
+/* out[nelemd][8] for Qf = Qdp(nt)[q]/dp(current ps_v), dq = Qf - Q0, dev = |Q0 - avg|, dV = colw*dh(k), owned points only:
+ *   0 sum |dq| dV   1 sum dev dV   2 sum dq*dq dV   3 sum dev*dev dV   4 max |dq| dV   5 max dev dV   6 max Qf   7 min Qf
+ * Every term is the host expression's in every bit (no contraction); only the order of addition is the device's.  An element without an
+ * owned point gives 0 for entries 0 to 5 and -inf / +inf for entries 6 and 7.  All three calls return nonzero (and launch nothing) when
+ * tse_norm_setup has not been called, tse_norm_partials also before the first tse_norm_reference, for q outside 0..qsize-1 and nt outside 1|2. */
+int tse_norm_partials(tse_ctx *ctx, int nt, int q, double avg, double *out);
+
 /* ---- introspection for tests and the benchmark harness ---- */
 /* device pointers of internal fields: "qdp1", "qdp2" [nelemd][qsize][nlev][16] (the two time levels are two allocations), "vn0", "dp", "divdp", "divdp_proj",
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
- * (both null before the first tse_state_q) */
+ * (both null before the first tse_state_q), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
- * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq",
- * and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
+ * (tse_norm_reference and tse_norm_partials), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

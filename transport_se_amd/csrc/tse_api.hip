@@ -96,6 +96,11 @@ struct tse_ctx {
   // until the next change of Qdp or ps_v (set_bounds_cache)
   double *qmix = nullptr, *lnps = nullptr;
   bool qmix_valid = false;
+  // the error norms (tse_norm_*): owner mask, column weights and layer depths of tse_norm_setup; the reference field Q0 of
+  // tse_norm_reference (one tracer slot, allocated by its first call; a snapshot: no state change makes it stale)
+  int* norm_owner = nullptr;
+  double *norm_colw = nullptr, *norm_dh = nullptr, *qref = nullptr;
+  bool norm_ready = false, qref_set = false;
   int* bad = nullptr;
   int* bad_host = nullptr; hipEvent_t bad_ev[2] = {nullptr, nullptr};   // page-locked copies of `bad`, one per cycle in flight (tse_prim_run_subcycle)
   int mm_valid = 0;   // time level (1|2) whose element min/max of Q sit in qmin2/qmax2 (emitted by the previous step), 0 = none
@@ -468,7 +473,7 @@ void tse_finalize(tse_ctx* c) {
   for (int i = 0; i < 2; i++) { if (c->stage[i]) (void)hipHostFree(c->stage[i]); if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]); }
   void* ptrs[] = {c->dcmip_tab, c->dvv_d, c->Dinv, c->metdet, c->rmetdet, c->spheremp, c->rspheremp, c->hyai, c->hybi, c->dp0, c->dss_tab, c->send_src,
                   c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
-                  c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
+                  c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->norm_owner, c->norm_colw, c->norm_dh, c->qref, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
                   c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (double* p : {c->T, c->B, c->C}) if (p) (void)hipFree(p);
@@ -1445,6 +1450,76 @@ int tse_state_q(tse_ctx* c, int nt) {
   return 0;
 }
 
+// ---- the DCMIP error norms from element partials (k_norm_reference / k_norm_partials, tse_kernels.h) ----
+// owner[nelemd][16], colw[nelemd][16], dh[nlev] -> device (allocated once; a later call overwrites them)
+int tse_norm_setup(tse_ctx* c, const int* owner, const double* colw, const double* dh) {
+  if (!owner || !colw || !dh) return fail("tse_norm_setup: null argument");
+  const size_t n = (size_t)c->nelemd * 16;
+  if (!c->norm_owner && dalloc(&c->norm_owner, n)) return 1;
+  if (!c->norm_colw && dalloc(&c->norm_colw, n)) return 1;
+  if (!c->norm_dh && dalloc(&c->norm_dh, (size_t)NLEV)) return 1;
+  c->norm_ready = false;
+  HIPCHK(hipStreamSynchronize(c->stream));   // (a norm kernel still running reads the old tables)
+  HIPCHK(hipMemcpy(c->norm_owner, owner, n * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->norm_colw, colw, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->norm_dh, dh, (size_t)NLEV * 8, hipMemcpyHostToDevice));
+  c->norm_ready = true;
+  return 0;
+}
+static int norm_args(tse_ctx* c, const char* who, int nt, int q, const void* out) {
+  if (!c->norm_ready) return fail("%s: call tse_norm_setup first", who);
+  if (nt < 1 || nt > 2) return fail("%s: nt=%d", who, nt);
+  if (q < 0 || q >= c->qsize) return fail("%s: tracer q=%d outside 0..%d", who, q, c->qsize - 1);
+  if (!out) return fail("%s: null argument", who);
+  return 0;
+}
+// d[n] on the device -> host out, behind everything on the stream; frees d
+static int norm_fetch(tse_ctx* c, const char* who, double* d, double* out, size_t n, bool launched) {
+  int rc = !launched || hipMemcpyAsync(out, d, n * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess;
+  if (rc) rc = fail("%s: launch or copy failed", who);
+  (void)hipFree(d);
+  return rc;
+}
+int tse_norm_reference(tse_ctx* c, int nt, int q, double* sum0) {
+  if (norm_args(c, "tse_norm_reference", nt, q, sum0)) return 1;
+  if (!c->qref) {
+    // (TSE_TEST_FAIL_NORM_ALLOC, hooks twin only: the allocation fails on request, for the test of this message)
+    const hipError_t e = hook_env("TSE_TEST_FAIL_NORM_ALLOC") ? hipErrorOutOfMemory : hipMalloc((void**)&c->qref, c->lev() * 8);
+    if (e != hipSuccess) {
+      (void)hipGetLastError(); c->qref = nullptr;
+      return fail("tse_norm_reference: cannot allocate the reference field (%.3f GB of device memory): %s", c->lev() * 8 / 1e9, hipGetErrorString(e));
+    }
+  }
+  double* d = nullptr;
+  if (dalloc(&d, (size_t)c->nelemd)) return 1;
+  c->qref_set = false;
+  bool ok;
+  {
+    Scope s(c, "norms");
+    hipLaunchKernelGGL(k_norm_reference<>, dim3((unsigned)c->nelemd), dim3(NORM_THREADS), 0, c->stream, c->qsize, q, (const double*)c->q(nt), (const double*)c->ps_v,
+                       (const double*)c->hyai, (const double*)c->hybi, c->ps0, (const int*)c->norm_owner, c->qref, d);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  if (norm_fetch(c, "tse_norm_reference", d, sum0, (size_t)c->nelemd, ok)) return 1;
+  c->qref_set = true;
+  return 0;
+}
+int tse_norm_partials(tse_ctx* c, int nt, int q, double avg, double* out) {
+  if (norm_args(c, "tse_norm_partials", nt, q, out)) return 1;
+  if (!c->qref_set) return fail("tse_norm_partials: call tse_norm_reference first");
+  double* d = nullptr;
+  if (dalloc(&d, (size_t)c->nelemd * 8)) return 1;
+  bool ok;
+  {
+    Scope s(c, "norms");
+    hipLaunchKernelGGL(k_norm_partials<>, dim3((unsigned)c->nelemd), dim3(NORM_THREADS), 0, c->stream, c->qsize, q, (const double*)c->q(nt), (const double*)c->ps_v,
+                       (const double*)c->hyai, (const double*)c->hybi, c->ps0, (const int*)c->norm_owner, (const double*)c->norm_colw, (const double*)c->norm_dh,
+                       (const double*)c->qref, avg, d);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  return norm_fetch(c, "tse_norm_partials", d, out, (size_t)c->nelemd * 8, ok);
+}
+
 // ---- prescribed fields + device-resident driver ---------------------------------------------------
 int tse_dcmip_init(tse_ctx* c, int test, const double* lat, const double* lon, const double* hyam, const double* hybm) {
   if (test != 1 && test != 2) return fail("tse_dcmip_init: test_case=%d", test);
@@ -1551,7 +1626,7 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   const size_t m2 = (size_t)2 * c->mm_m() * 8;
   Ent ents[] = {{"qdp1", c->q(1), trc}, {"qdp2", c->q(2), trc}, {"T", c->T, scr + c->tps * 8}, {"B", c->B, scr + c->tps * 8}, {"C", c->C, scr + c->tps * 8}, {"vn0", c->vn0, 2 * lev}, {"dp", c->dp, lev},
                 {"divdp", c->divdp, lev}, {"divdp_proj", c->divdp_proj, lev}, {"eta_dot_dpdn", c->eta, (size_t)c->nelemd * NLEVP * 16 * 8},
-                {"omega_p", c->omega_p, lev}, {"dp3d", c->dp3d, lev}, {"ps_v", c->ps_v, (size_t)c->nelemd * 16 * 8}, {"q", c->qmix, trc}, {"lnps", c->lnps, (size_t)c->nelemd * 16 * 8}, {"qmin", c->qmin, mm},
+                {"omega_p", c->omega_p, lev}, {"dp3d", c->dp3d, lev}, {"ps_v", c->ps_v, (size_t)c->nelemd * 16 * 8}, {"q", c->qmix, trc}, {"lnps", c->lnps, (size_t)c->nelemd * 16 * 8}, {"qref", c->qref, lev}, {"qmin", c->qmin, mm},
                 {"qmax", c->qmax, mm}, {"sendbuf", c->sendbuf, (size_t)c->ncol_send * c->nlyr_halo * 8},
                 {"recvbuf", c->recvbuf, (size_t)c->ncol_recv * c->nlyr_halo * 8}, {"sendbuf_mm", c->sendbuf_mm, (size_t)c->nmm_send * m2},
                 {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}};

@@ -193,6 +193,93 @@ __global__ __launch_bounds__(STATEQ_THREADS) void k_state_q(int nelemd, int qsiz
   }
 }
 
+// The element shares of the DCMIP error norms (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77): the norm line L1 L2 Linf q_max q_min is
+// made of four sums and four extrema over the unique GLL columns and the levels; an element contributes the points it OWNS (owner[e][p] = 1:
+// the first of the sharers of a node in (element, j, i) order, dof_mod.F90:43-57).  Q is formed as k_state_q / k_elem_qdiag form it
+// (level_dp, mixing_ratio), every term with contraction off, so each term is the host's (diagnostics.dcmip_norms) in every bit and only the
+// order of addition is the device's own.
+//
+// THE ORDER (tests/norm_model.py adds in the same one).  block = element; lane t = (point p = t & 15, level group g = t >> 4); the NLEV
+// levels are cut into NORM_LG = 4 groups of NORM_LPG = NLEV/4 consecutive levels.
+//   1. lane (p, g): s = 0; for k = g*NORM_LPG .. (g+1)*NORM_LPG - 1 ascending: s = s + term(p, k)
+//   2. column p:    c(p) = ((s(p,0) + s(p,1)) + s(p,2)) + s(p,3)
+//   3. element:     S = 0; for p = 0 .. 15 ascending, owned points only: S = S + c(p)
+// Maxima and minima take the same route (they do not depend on it).  All of it is a function of the element's own 16 x NLEV values, colw and
+// owner rows and of dh and avg: not of the block index, of the other elements, or of how the elements are dealt to ranks -- so the host's
+// exact sum of the element shares (math.fsum) has the same bits on any number of ranks.
+constexpr int NORM_THREADS = 64, NORM_LG = 4, NORM_LPG = NLEV / NORM_LG;
+static_assert(NLEV % NORM_LG == 0, "k_norm_*: four level groups of equal length");
+
+// Q0 = Qdp(nt)[q]/dp(ps_v) -> qref[e][k][16] (all 16 points of every element), sum0[e] = the unweighted sum of Q0 over owned points and
+// levels in THE ORDER: the element's share of avg(q0) (the script's avg() over (lev, ncol)).
+template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
+__global__ __launch_bounds__(NORM_THREADS) void k_norm_reference(int qsize, int q, const double* __restrict__ Qdp, const double* __restrict__ ps_v,
+                                                                 const double* __restrict__ hyai, const double* __restrict__ hybi, double ps0,
+                                                                 const int* __restrict__ owner, double* __restrict__ qref, double* __restrict__ sum0) {
+#pragma clang fp contract(off)
+  __shared__ double hs[NORM_THREADS];
+  const int e = blockIdx.x, t = threadIdx.x, p = t & 15, g = t >> 4;
+  const double* x = Qdp + ((size_t)e * qsize + q) * NLEV * 16 + p;
+  double* r = qref + (size_t)e * NLEV * 16 + p;
+  const double ps = ps_v[(size_t)e * 16 + p];
+  double s = 0.0;
+  for (int k = g * NORM_LPG; k < (g + 1) * NORM_LPG; k++) {
+    const double q0 = mixing_ratio(x[(size_t)k * 16], level_dp(hyai, hybi, ps0, k, ps));
+    r[(size_t)k * 16] = q0;
+    s = s + q0;
+  }
+  hs[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    const int* own = owner + (size_t)e * 16;
+    double tot = 0.0;
+    for (int i = 0; i < 16; i++)
+      if (own[i]) tot = tot + (((hs[i] + hs[16 + i]) + hs[32 + i]) + hs[48 + i]);
+    sum0[e] = tot;
+  }
+}
+
+// out[e][8], Qf = Qdp(nt)[q]/dp(ps_v), dq = Qf - Q0, dev = |Q0 - avg|, dV = colw[e][p]*dh[k], owned points only:
+//   0 sum |dq| dV   1 sum dev dV   2 sum (dq*dq) dV   3 sum (dev*dev) dV   4 max |dq| dV   5 max dev dV   6 max Qf   7 min Qf
+// sums in THE ORDER; an element without an owned point gives 0 0 0 0 0 0 -inf +inf.  (Every term is >= 0, so the maxima start at 0.)
+template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
+__global__ __launch_bounds__(NORM_THREADS) void k_norm_partials(int qsize, int q, const double* __restrict__ Qdp, const double* __restrict__ ps_v,
+                                                                const double* __restrict__ hyai, const double* __restrict__ hybi, double ps0,
+                                                                const int* __restrict__ owner, const double* __restrict__ colw, const double* __restrict__ dh,
+                                                                const double* __restrict__ qref, double avg, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double h[8][NORM_THREADS];
+  const int e = blockIdx.x, t = threadIdx.x, p = t & 15, g = t >> 4;
+  const double* x = Qdp + ((size_t)e * qsize + q) * NLEV * 16 + p;
+  const double* r = qref + (size_t)e * NLEV * 16 + p;
+  const double ps = ps_v[(size_t)e * 16 + p], w = colw[(size_t)e * 16 + p];
+  const double inf = __builtin_huge_val();
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, m4 = 0.0, m5 = 0.0, m6 = -inf, m7 = inf;
+  for (int k = g * NORM_LPG; k < (g + 1) * NORM_LPG; k++) {
+    const double qf = mixing_ratio(x[(size_t)k * 16], level_dp(hyai, hybi, ps0, k, ps));
+    const double q0 = r[(size_t)k * 16];
+    const double dV = w * dh[k];
+    const double dq = qf - q0, adq = fabs(dq), dev = fabs(q0 - avg);
+    const double t0 = adq * dV, t1 = dev * dV, t2 = (dq * dq) * dV, t3 = (dev * dev) * dV;
+    s0 = s0 + t0; s1 = s1 + t1; s2 = s2 + t2; s3 = s3 + t3;
+    m4 = fmax(m4, t0); m5 = fmax(m5, t1); m6 = fmax(m6, qf); m7 = fmin(m7, qf);
+  }
+  h[0][t] = s0; h[1][t] = s1; h[2][t] = s2; h[3][t] = s3; h[4][t] = m4; h[5][t] = m5; h[6][t] = m6; h[7][t] = m7;
+  __syncthreads();
+  if (t < 8) {   // lane t combines entry t
+    const int* own = owner + (size_t)e * 16;
+    const double* v = h[t];
+    double a = t < 6 ? 0.0 : (t == 6 ? -inf : inf);
+    for (int i = 0; i < 16; i++) {
+      if (!own[i]) continue;
+      if (t < 4) a = a + (((v[i] + v[16 + i]) + v[32 + i]) + v[48 + i]);
+      else if (t == 7) a = fmin(a, fmin(fmin(v[i], v[16 + i]), fmin(v[32 + i], v[48 + i])));
+      else a = fmax(a, fmax(fmax(v[i], v[16 + i]), fmax(v[32 + i], v[48 + i])));
+    }
+    out[(size_t)e * 8 + t] = a;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // element min/max of Q = Qdp/dp, dp = derived%dp - rhs_multiplier*dt*divdp_proj  (prim_advection_mod.F90:750-775)
 template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)

@@ -3,6 +3,8 @@
 * `dcmip_norms`: L1/L2/Linf/q_max/q_min exactly as test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77 (and the dcmip1-2 twin)
   computes them from the history file: unique-column native grid, dV = R cos(lat) dlon * R dlat * dh(lev) with dh rebuilt
   from the level heights by the "2*(h-base)" recursion, relative to (q0 - avg(q0)).
+* `column_weights` / `norms_from_partials`: the same norm line without the field on the host -- the device forms every element's share
+  over the columns it owns (tse_norm_partials), rank 0 adds the shares exactly.
 * `tracer_mass`: the conserved integral behind the "Q,Q diss" line (prim_state_mod.F90:352-385 through
   global_integral, global_norms_mod.F90:39-86).
 * `printstate_lines`: the `qv=  min max sum` lines of prim_printstate (prim_state_mod.F90:341-347).
@@ -10,9 +12,8 @@
   count with a fixed-point reproducible sum (repro_sum_mod.F90:216-632; "independent of thread count and task count",
   global_norms_mod.F90:66-68).  Here every ELEMENT's partial sum is formed in a fixed order (on the device:
   tse_element_mass), the partials travel to rank 0, and rank 0 adds them with math.fsum -- the correctly rounded exact sum,
-  which does not depend on the order, hence not on how the elements were distributed.  Fields needed whole (the norm
-  calculator works on the unique-column grid) are reassembled on rank 0 in global element order, after which every number
-  is computed exactly as on one rank.
+  which does not depend on the order, hence not on how the elements were distributed.  The error norms go the same way
+  (tse_norm_partials -> norms_from_partials).  `gather_by_gid` reassembles per-element rows on rank 0 in global element order.
 """
 import math
 
@@ -44,27 +45,67 @@ def hybrid_dp(hyai, hybi, ps_v):
     return da[None, :, None, None] + db[None, :, None, None] * np.asarray(ps_v)[:, None, :, :]
 
 
-def dcmip_norms(ne, lat, lon, q_i, q_f, zm):
-    nlev = q_i.shape[1]
-    cols = unique_columns(lat, lon)
-    if cols.size != 6 * ne * ne * 9 + 2:
-        raise ValueError("expected %d unique columns, found %d" % (6 * ne * ne * 9 + 2, cols.size))
-    qi = np.moveaxis(q_i, 1, 0).reshape(nlev, -1)[:, cols]
-    qf = np.moveaxis(q_f, 1, 0).reshape(nlev, -1)[:, cols]
-    latc = np.asarray(lat).reshape(-1)[cols]
+R_EARTH = 6.37122e6
+
+
+def layer_depths(zm):
+    """dh(lev) of the norm script: rebuilt from the mid-level heights by its "2*(h-base)" recursion, from the surface up"""
+    nlev = len(zm)
     dh = np.zeros(nlev); base = 0.0
     for i in range(1, nlev + 1):
         dh[nlev - i] = 2.0 * (zm[nlev - i] - base)
         base = base + dh[nlev - i]
-    R = 6.37122e6
+    return dh
+
+
+def _norm_columns(ne, lat, lon):
+    """(cols, colw): the unique columns (flat point indices, ascending) and the horizontal weight of each, the script's
+    R cos(lat) dlon * R dlat with dlon = dlat = the mean node spacing; both norm routes take their weights from here"""
+    cols = unique_columns(lat, lon)
+    if cols.size != 6 * ne * ne * 9 + 2:
+        raise ValueError("expected %d unique columns, found %d" % (6 * ne * ne * 9 + 2, cols.size))
+    latc = np.asarray(lat).reshape(-1)[cols]
+    R = R_EARTH
     dlat = 0.5 * np.pi / (ne * 3)
-    dV = (R * np.cos(latc) * dlat)[None, :] * (R * dlat) * dh[:, None]
+    return cols, (R * np.cos(latc) * dlat) * (R * dlat)
+
+
+def column_weights(ne, lat, lon, zm):
+    """(owner, colw, dh) of tse_norm_setup for the WHOLE mesh (lat, lon [nelem][4][4]; a rank passes on the rows of its elements):
+    owner[nelem][4][4] = 1 where the element's point is the owner of its GLL column (unique_columns), colw[nelem][4][4] = that column's
+    horizontal weight (0 where owner = 0: never read), dh[nlev] = layer_depths(zm) -- the very numbers dcmip_norms multiplies"""
+    cols, w = _norm_columns(ne, lat, lon)
+    shape = np.asarray(lat).shape
+    owner = np.zeros(np.asarray(lat).size, dtype=np.int32); colw = np.zeros(owner.size)
+    owner[cols] = 1; colw[cols] = w
+    return owner.reshape(shape), colw.reshape(shape), layer_depths(zm)
+
+
+def dcmip_norms(ne, lat, lon, q_i, q_f, zm):
+    nlev = q_i.shape[1]
+    cols, colw = _norm_columns(ne, lat, lon)
+    qi = np.moveaxis(q_i, 1, 0).reshape(nlev, -1)[:, cols]
+    qf = np.moveaxis(q_f, 1, 0).reshape(nlev, -1)[:, cols]
+    dh = layer_depths(zm)
+    dV = colw[None, :] * dh[:, None]
     dq = qf - qi
     dev = np.abs(qi - qi.mean())
     return dict(L1=float((np.abs(dq) * dV).sum() / (dev * dV).sum()),
                 L2=float(np.sqrt((dq * dq * dV).sum()) / np.sqrt((dev * dev * dV).sum())),
                 Linf=float((np.abs(dq) * dV).max() / (dev * dV).max()),
                 q_max=float(qf.max()), q_min=float(qf.min()))
+
+
+def norms_from_partials(partials, gid, nelem, dist_mod=None, rank=0, world=1):
+    """partials[n_local][8] (tse_norm_partials: one row per local element) -> the norm line's dict on rank 0 (None elsewhere): entries 0
+    to 3 added exactly over all elements (math.fsum: no order, hence no dependence on the partition), entries 4 to 7 reduced by max / min;
+    L1 = s0/s1, L2 = sqrt(s2)/sqrt(s3), Linf = m4/m5."""
+    full = gather_by_gid(np.asarray(partials, dtype=np.float64), gid, nelem, dist_mod, rank, world)
+    if full is None:
+        return None
+    s = [math.fsum(full[:, j].tolist()) for j in range(4)]
+    return dict(L1=float(s[0] / s[1]), L2=float(np.sqrt(s[2]) / np.sqrt(s[3])), Linf=float(full[:, 4].max() / full[:, 5].max()),
+                q_max=float(full[:, 6].max()), q_min=float(full[:, 7].min()))
 
 
 def tracer_mass(spheremp, qdp):

@@ -135,6 +135,8 @@ class PrimRun:
                          spheremp=geo["spheremp"][mine], rspheremp=geo["rspheremp"][mine],
                          putmapP=desc["putmapP"], getmapP=desc["getmapP"], reverse=desc["reverse"])
         self.lat, self.lon = geo["lat"][mine], geo["lon"][mine]
+        self._mesh_latlon = (geo["lat"], geo["lon"])   # the whole mesh: which point owns a GLL column is a global question (norm_reference)
+        self._norm = None
         callback = None
         if world > 1:
             if exchange not in ("rccl", "torch", "staged"):
@@ -255,6 +257,36 @@ class PrimRun:
         self.hip.state_q(tl)
         self.hip.copy_q_d2h(out); self.hip.copy_lnps_d2h(out)
         return out["Q"], out["lnps"]
+
+    def norm_reference(self, tl=1, tracer=None):
+        """collective: take Q(tl) of the norm script's tracer (tracer counts from 0; default: tracer 1 for DCMIP 1-1, tracer 2 = Q2 for 1-2)
+        as the reference field of the error norms, on the device.  Sets up this rank's owner mask and column weights, snapshots Q0 there and
+        forms avg(Q0) = (exact sum of the element sums) / (nlev * ncol) on rank 0; that one double is broadcast, so that every rank's
+        partials are taken against the same bits."""
+        from . import diagnostics as dg
+        import math
+        if tracer is None:
+            tracer = 0 if self.test_case == 1 else 1
+        lat, lon = self._mesh_latlon
+        owner, colw, dh = dg.column_weights(self.ne, lat, lon, dg.level_heights(self.hv.hyam, self.hv.hybm))
+        self.hip.norm_setup(owner[self.mine], colw[self.mine], dh)
+        sum0 = self.hip.norm_reference(tl, tracer)
+        full = dg.gather_by_gid(sum0, self.mine, self.nelem, self._dist, self.rank, self.world)
+        box = [math.fsum(full.tolist()) / (self.nlev * int(owner.sum())) if self.rank == 0 else None]
+        if self.world > 1:
+            self._dist.broadcast_object_list(box, src=0)
+        self._norm = (tracer, box[0])
+        return box[0]
+
+    def norms(self, tl):
+        """collective: dict(L1, L2, Linf, q_max, q_min) of Q(tl) against the snapshot of norm_reference, as dcmip1-*_error_norm_ng.ncl
+        prints them, on rank 0 (None elsewhere): element partials from the device, added exactly on rank 0 (diagnostics.norms_from_partials)
+        -- the same digits on any number of ranks, and no field on the host"""
+        from . import diagnostics as dg
+        if self._norm is None:
+            raise RuntimeError("PrimRun.norms: call norm_reference first")
+        tracer, avg = self._norm
+        return dg.norms_from_partials(self.hip.norm_partials(tl, tracer, avg), self.mine, self.nelem, self._dist, self.rank, self.world)
 
     def close(self):
         self.hip.close()

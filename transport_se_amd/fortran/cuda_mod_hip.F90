@@ -40,6 +40,9 @@ module cuda_mod
   ! not in the reference's list either: the device-resident prim_run loop (INTEGRATION.md section 2b) -- prescribed DCMIP fields on the
   ! device, nsub whole prim_run_subcycle calls in one device call, and the download of what prim_run_subcycle leaves in elem
   public :: dcmip_init_hip, prim_run_subcycle_hip, copy_state_d2h_hip, hip_resident_report
+  ! the DCMIP error norms from element partials (INTEGRATION.md section 2c): the device forms every element's share of the norm line's
+  ! sums and extrema, the host reduces them over elements and ranks (repro_sum for the sums)
+  public :: norm_setup_hip, norm_reference_hip, norm_partials_hip
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
   integer(c_int), save :: res_nstep = 0   ! the library's step count after the last prim_run_subcycle_hip
   integer(kind=8), save :: t_c0
@@ -139,6 +142,15 @@ module cuda_mod
      end function
      integer(c_int) function tse_copy_lnps_d2h(ctx, lnps, stride) bind(C, name='tse_copy_lnps_d2h')
        import; type(c_ptr), value :: ctx, lnps; integer(c_size_t), value :: stride
+     end function
+     integer(c_int) function tse_norm_setup(ctx, owner, colw, dh) bind(C, name='tse_norm_setup')
+       import; type(c_ptr), value :: ctx, owner, colw, dh
+     end function
+     integer(c_int) function tse_norm_reference(ctx, nt, q, sum0) bind(C, name='tse_norm_reference')
+       import; type(c_ptr), value :: ctx, sum0; integer(c_int), value :: nt, q
+     end function
+     integer(c_int) function tse_norm_partials(ctx, nt, q, avg, out) bind(C, name='tse_norm_partials')
+       import; type(c_ptr), value :: ctx, out; integer(c_int), value :: nt, q; real(c_double), value :: avg
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -640,5 +652,45 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine copy_state_d2h_hip
+
+  ! ---- the DCMIP error norms from element partials (tse_norm_*, include/transport_se_hip.h) ----
+  ! owner(np,np,nelemd) = 1 where this element's point owns its GLL column (the smallest global dof among the sharers, dof_mod.F90:43-57),
+  ! colw(np,np,nelemd) = the column's horizontal weight (read where owner = 1), dh(nlev) = the layer depths.  May be called again.
+  subroutine norm_setup_hip(owner, colw, dh)
+    integer(c_int), intent(in), target :: owner(np,np,nelemd)
+    real(c_double), intent(in), target :: colw(np,np,nelemd), dh(nlev)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check_nlev('norm_setup_hip')
+    call check(tse_norm_setup(ctx, c_loc(owner), c_loc(colw), c_loc(dh)), 'norm_setup_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine norm_setup_hip
+
+  ! snapshot Q0 = Qdp(:,:,:,q,nt)/dp on the device as the reference field (q counts from 1 here, as Fortran's tracer index does);
+  ! sum0(ie) = the element's unweighted sum of Q0 over its owned points and levels: avg = repro_sum(sum0) / (nlev * ncol)
+  subroutine norm_reference_hip(nt, q, sum0)
+    integer,        intent(in)          :: nt, q
+    real(c_double), intent(out), target :: sum0(nelemd)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_norm_reference(ctx, int(nt,c_int), int(q-1,c_int), c_loc(sum0)), 'norm_reference_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine norm_reference_hip
+
+  ! out(1:8,ie): sum |dq| dV, sum dev dV, sum dq*dq dV, sum dev*dev dV, max |dq| dV, max dev dV, max Qf, min Qf over the element's owned
+  ! points, Qf = Qdp(:,:,:,q,nt)/dp(ps_v), dq = Qf - Q0, dev = |Q0 - avg|.  The host adds rows 1:4 over elements and ranks with repro_sum
+  ! and reduces rows 5:8 with max / min: L1 = s1/s2, L2 = sqrt(s3)/sqrt(s4), Linf = m5/m6, q_max = m7, q_min = m8.
+  subroutine norm_partials_hip(nt, q, avg, out)
+    integer,        intent(in)          :: nt, q
+    real(c_double), intent(in)          :: avg
+    real(c_double), intent(out), target :: out(8,nelemd)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_norm_partials(ctx, int(nt,c_int), int(q-1,c_int), avg, c_loc(out)), 'norm_partials_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine norm_partials_hip
 
 end module cuda_mod

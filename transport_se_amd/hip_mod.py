@@ -272,6 +272,27 @@ class HipMod:
         self._chk(self.L.tse_element_qdiag(self.h, int(nt), *[_vp(x) for x in out]))
         return tuple(out)
 
+    # ---- the DCMIP error norms from element partials (tse_norm_*; diagnostics.column_weights / norms_from_partials) ----
+    def norm_setup(self, owner, colw, dh):
+        """owner[nelemd][4][4] (1: this element's point owns its GLL column), colw[nelemd][4][4] (the column's horizontal weight),
+        dh[nlev] (layer depths) -> device"""
+        owner = np.ascontiguousarray(owner, np.int32); colw = np.ascontiguousarray(colw, np.float64); dh = np.ascontiguousarray(dh, np.float64)
+        if owner.size != self.nelemd * 16 or colw.size != self.nelemd * 16 or dh.size != self.nlev:
+            raise TseError("norm_setup: owner %s, colw %s, dh %s for %d elements and %d levels" % (owner.shape, colw.shape, dh.shape, self.nelemd, self.nlev))
+        self._chk(self.L.tse_norm_setup(self.h, _vp(owner), _vp(colw), _vp(dh)))
+
+    def norm_reference(self, nt, q):
+        """snapshot Q0 = Qdp(nt)[q]/dp on the device (q from 0); returns sum0[nelemd], each element's unweighted sum of Q0 over its owned points"""
+        out = np.empty(self.nelemd)
+        self._chk(self.L.tse_norm_reference(self.h, int(nt), int(q), _vp(out)))
+        return out
+
+    def norm_partials(self, nt, q, avg):
+        """[nelemd][8]: the element shares of the norm line against the snapshot (include/transport_se_hip.h: tse_norm_partials)"""
+        out = np.empty((self.nelemd, 8))
+        self._chk(self.L.tse_norm_partials(self.h, int(nt), int(q), float(avg), _vp(out)))
+        return out
+
     def get_qminmax(self):
         qmin = np.empty((self.nelemd, self.qsize, self.nlev)); qmax = np.empty_like(qmin)
         self._chk(self.L.tse_get_qminmax(self.h, _vp(qmin), _vp(qmax)))

@@ -277,7 +277,6 @@ def main(argv=None):
     s = settings(parse_namelists(box[0]))
     hv = vertical_coordinate(s)
 
-    from . import cube_mesh as cm
     from .driver import PrimRun
     from .hip_mod import TseError
     if os.environ.get("TSE_TEST_FAIL_REMAP_RANK") == str(rank):   # tests: this rank alone meets a negative layer thickness
@@ -302,8 +301,7 @@ def main(argv=None):
     def gather(x):
         return dg.gather_by_gid(x, gid, nelem, dist, rank, world)
 
-    tr = 0 if s["test"] == 1 else 1
-    q0 = gather(run.fetch_qdp(1)[:, tr].copy())              # the norm script's tracer only (Q for 1-1, Q2 for 1-2)
+    run.norm_reference()                                     # Q(t0) of the norm script's tracer (Q for 1-1, Q2 for 1-2) stays on the device
     m0 = gsum(hip.element_mass(1))
     nsteps = (s["nmax"] // s["rsplit"]) * s["rsplit"]
     say(" nmax = %d tracer steps, tstep = %g, ne = %d, qsize = %d, nu_q = %g, %d rank(s), exchange = %s"
@@ -384,14 +382,10 @@ def main(argv=None):
     if rank == 0:
         write_hommetime("HommeTime_stats", hommetime_timers(stack, counts), world)
     # error norms on the unique-column grid (dcmip1-*_error_norm_ng.ncl:39-77) and tracer mass ("Q, Q diss")
-    q1 = gather(run.fetch_qdp(np1)[:, tr].copy())
-    ps_v = gather(hip.fetch("ps_v", (gid.size, 4, 4)))
+    # (element partials formed on the device, added exactly on rank 0: no tracer field crosses to the host)
+    nrm = run.norms(np1)
     m1 = gsum(hip.element_mass(np1))
     if rank == 0:
-        geo = cm.geometry(s["ne"])
-        dp0 = dg.hybrid_dp(run.hv.hyai, run.hv.hybi, np.full((nelem, 4, 4), dg.P0))
-        nrm = dg.dcmip_norms(s["ne"], geo["lat"], geo["lon"], q0 / dp0, q1 / dg.hybrid_dp(run.hv.hyai, run.hv.hybi, ps_v),
-                             dg.level_heights(run.hv.hyam, run.hv.hybm))
         print("DCMIP 1-%d: L1=%8.6f L2=%8.6f Linf=%8.6f q_max=%8.6f q_min=%14.6e" % (s["test"], nrm["L1"], nrm["L2"], nrm["Linf"], nrm["q_max"], nrm["q_min"]))
         for t in range(s["qsize"]):
             print("Q%d mass: %22.14E -> %22.14E (relative change %10.3e)" % (t + 1, m0[t], m1[t], (m1[t] - m0[t]) / max(abs(m0[t]), 1e-300)))
