@@ -247,6 +247,22 @@ int tse_norm_reference(tse_ctx *ctx, int nt, int q, double *sum0);
  * tse_norm_setup has not been called, tse_norm_partials also before the first tse_norm_reference, for q outside 0..qsize-1 and nt outside 1|2. */
 int tse_norm_partials(tse_ctx *ctx, int nt, int q, double avg, double *out);
 
+/* ---- the numerical-mixing and filament diagnostics from element partials (Lauritzen and Thuburn 2012, QJRMS 138: l_r, l_u, l_o, l_f) ----
+ * Two tracers chi = Q[qa], xi = Q[qb] (Q = Qdp(nt)/dp(current ps_v), formed as tse_state_q forms it) that started on the curve
+ * xi = psi(chi) = c0 + c2*(chi*chi), c2 < 0, with chi in [xmin, xmax] (DCMIP 1-1: qa = 0, qb = 1, c0 = 0.9, c2 = -0.8).  Every owned
+ * (point, level) is put into class A (real mixing: xmin <= chi <= xmax and chord(chi) <= xi <= psi(chi), the chord joining the curve's two
+ * ends), B (range-preserving unmixing: not A, chi in [xmin, xmax] and xi in [psi(xmax), psi(xmin)]) or C (overshooting: the rest), and
+ * d = its distance to the curve over chi in [xmin, xmax], normalised by the ranges xmax - xmin and psi(xmin) - psi(xmax) (csrc/tse_kernels.h:
+ * mix_distance -- + - * / sqrt, comparisons and selects only, no contraction, fixed trip counts).  Weights and owner mask are those of
+ * tse_norm_setup, dV = colw*dh(k).  out[nelemd][32], owned points only, sums in the order of k_norm_partials:
+ *   0 sum_A d dV   1 sum_B d dV   2 sum_C d dV   3 sum dV   4 5 6 the number of (point, level) in A, B, C (exact)   7 max d
+ *   8+j sum dV [chi >= tau[j]], j < ntau   the remaining entries 0
+ * An element without an owned point gives 0 everywhere.  The host adds entries 0 to 3 and 8.. exactly over elements and ranks:
+ * l_r, l_u, l_o = S0, S1, S2 / S3;  l_f(tau_j) = 100 * S(8+j)(t) / S(8+j)(t0).  All inputs finite.  Returns nonzero with a message (and
+ * launches nothing) before tse_norm_setup, for nt outside 1|2, qa or qb outside 0..qsize-1, xmax <= xmin, c2 >= 0, ntau outside 0..24 and
+ * a null out (or a null tau with ntau > 0). */
+int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double xmax, double c0, double c2, const double *tau, int ntau, double *out);
+
 /* ---- introspection for tests and the benchmark harness ---- */
 /* device pointers of internal fields: "qdp1", "qdp2" [nelemd][qsize][nlev][16] (the two time levels are two allocations), "vn0", "dp", "divdp", "divdp_proj",
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
@@ -254,7 +270,7 @@ int tse_norm_partials(tse_ctx *ctx, int nt, int q, double avg, double *out);
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -138,7 +138,7 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchr
            "tse_dcmip_step_inputs", "tse_prim_run_subcycle", "tse_device_ptr", "tse_kernel_time", "tse_timing", "tse_comm_timing",
            "tse_halo_layout", "tse_halo_minmax_layout", "tse_comm_unique_id", "tse_comm_init", "tse_comm_precheck", "tse_comm_version", "tse_comm_info", "tse_comm_abort",
            "tse_boundary_layout", "tse_patch_layout", "tse_placement", "tse_invalidate_cache", "tse_divergence_sphere", "tse_laplace_sphere_wk", "tse_remap_q_ppm", "tse_host_register", "tse_element_mass", "tse_element_qdiag",
-           "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h", "tse_norm_setup", "tse_norm_reference", "tse_norm_partials"]
+           "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h", "tse_norm_setup", "tse_norm_reference", "tse_norm_partials", "tse_mix_partials"]
 COMM_ID_BYTES = 128
 
 
@@ -218,6 +218,7 @@ def lib(path=None, nlev=None):
     L.tse_norm_setup.argtypes = [vp, vp, vp, vp]
     L.tse_norm_reference.argtypes = [vp, i, i, vp]
     L.tse_norm_partials.argtypes = [vp, i, i, d, vp]
+    L.tse_mix_partials.argtypes = [vp, i, i, i, d, d, d, d, vp, i, vp]
     _libs[path] = L
     _check_nlev(L, path, nlev)
     return L

@@ -1520,6 +1520,39 @@ int tse_norm_partials(tse_ctx* c, int nt, int q, double avg, double* out) {
   return norm_fetch(c, "tse_norm_partials", d, out, (size_t)c->nelemd * 8, ok);
 }
 
+// ---- the mixing and filament diagnostics from element partials (k_mix_partials, tse_kernels.h) ----
+int tse_mix_partials(tse_ctx* c, int nt, int qa, int qb, double xmin, double xmax, double c0, double c2, const double* tau, int ntau, double* out) {
+#pragma clang fp contract(off)
+  const char* who = "tse_mix_partials";
+  if (!c->norm_ready) return fail("%s: call tse_norm_setup first", who);
+  if (nt < 1 || nt > 2) return fail("%s: nt=%d", who, nt);
+  for (int q : {qa, qb})
+    if (q < 0 || q >= c->qsize) return fail("%s: tracer q=%d outside 0..%d", who, q, c->qsize - 1);
+  if (!(xmax > xmin)) return fail("%s: xmax=%.17g <= xmin=%.17g", who, xmax, xmin);
+  if (!(c2 < 0.0)) return fail("%s: c2=%.17g (the relation c0 + c2*x*x must be concave: c2 < 0)", who, c2);
+  if (ntau < 0 || ntau > MIX_NTAU) return fail("%s: ntau=%d outside 0..%d", who, ntau, MIX_NTAU);
+  if (!out || (ntau > 0 && !tau)) return fail("%s: null argument", who);
+  // the derived values, each operation rounded once (tests/mixing_model.py: constants() forms the same bits)
+  MixPar m;
+  m.xmin = xmin; m.xmax = xmax; m.c0 = c0; m.c2 = c2;
+  m.yhi = c0 + c2 * (xmin * xmin); m.ylo = c0 + c2 * (xmax * xmax);
+  m.Rx = xmax - xmin; m.Ry = m.yhi - m.ylo;
+  m.sl = (m.ylo - m.yhi) / m.Rx;
+  m.kk = (m.Ry * m.Ry) / (m.Rx * m.Rx);
+  m.i2 = 1.0 / ((2.0 * c2) * c2);
+  for (int j = 0; j < MIX_NTAU; j++) m.tau[j] = j < ntau ? tau[j] : __builtin_huge_val();
+  double* d = nullptr;
+  if (dalloc(&d, (size_t)c->nelemd * MIX_OUT)) return 1;
+  bool ok;
+  {
+    Scope s(c, "mixing");
+    hipLaunchKernelGGL(k_mix_partials<>, dim3((unsigned)c->nelemd), dim3(NORM_THREADS), 0, c->stream, c->qsize, qa, qb, (const double*)c->q(nt), (const double*)c->ps_v,
+                       (const double*)c->hyai, (const double*)c->hybi, c->ps0, (const int*)c->norm_owner, (const double*)c->norm_colw, (const double*)c->norm_dh, m, d);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  return norm_fetch(c, who, d, out, (size_t)c->nelemd * MIX_OUT, ok);
+}
+
 // ---- prescribed fields + device-resident driver ---------------------------------------------------
 int tse_dcmip_init(tse_ctx* c, int test, const double* lat, const double* lon, const double* hyam, const double* hybm) {
   if (test != 1 && test != 2) return fail("tse_dcmip_init: test_case=%d", test);

@@ -280,6 +280,117 @@ __global__ __launch_bounds__(NORM_THREADS) void k_norm_partials(int qsize, int q
   }
 }
 
+// The element shares of the numerical-mixing and filament diagnostics of Lauritzen and Thuburn (2012, "Evaluating advection/transport schemes
+// using interrelated tracers, scatter plots and numerical mixing diagnostics", QJRMS 138) for two tracers chi, xi that start on the curve
+// xi = psi(chi) = c0 + c2*(chi*chi), c2 < 0, with chi in [xmin, xmax] (DCMIP 1-1: q2 = 0.9 - 0.8*q1^2, dcmip_point).  In the (chi, xi)
+// plane the curve and its chord F(chi) = yhi + (chi - xmin)*sl enclose the hull that real mixing can reach.  An owned (point, level) is of
+//   class A (real mixing):             xmin <= chi <= xmax and F(chi) <= xi <= psi(chi)
+//   class B (range-preserving unmixing): not A, and xmin <= chi <= xmax and ylo <= xi <= yhi      (yhi = psi(xmin), ylo = psi(xmax))
+//   class C (overshooting):            everything else
+// and contributes d*dV to its class, d = the distance to the curve normalised by the ranges Rx = xmax - xmin, Ry = yhi - ylo:
+//   d = sqrt(min over x in [xmin, xmax] of g(x)),  g(x) = ((chi - x)/Rx)^2 + ((xi - psi(x))/Ry)^2.
+// MixPar holds what the host derives once in fp64 (tse_mix_partials): sl = (ylo - yhi)/Rx, kk = (Ry*Ry)/(Rx*Rx), i2 = 1/(2*c2*c2), and the
+// filament thresholds tau (unused ones +inf, so that they count nothing).
+//
+// d uses + - * / sqrt, comparisons and selects only, each rounded once (no contraction), with fixed trip counts: tests/mixing_model.py restates
+// it in numpy and gives every d in every bit.  The stationary points of g are the roots of the depressed cubic h(x) = (x*x + P)*x + Qc,
+//   P = (kk - 2*c2*(xi - c0))*i2,  Qc = -(chi*kk)*i2;
+// h' = 3x^2 + P vanishes at -s and s, s = sqrt(max(-P/3, 0)), so h is monotone on each of the three intervals that the break points
+// b0 = xmin, b1 = clamp(-s), b2 = clamp(s), b3 = xmax (clamped to [xmin, xmax]) cut out of [xmin, xmax].  MIX_NB bisection steps on every
+// interval (all three are always computed; an interval over which h does not change sign is dropped by a select), the end points xmin and
+// xmax as the candidates a stationary point cannot replace.  Every candidate lies in [xmin, xmax], so d never falls below the true minimum,
+// and an empty interval (both ends equal) is harmless.
+constexpr int MIX_NTAU = 24, MIX_OUT = 32, MIX_NB = 60;
+struct MixPar { double xmin, xmax, c0, c2, yhi, ylo, Rx, Ry, sl, kk, i2, tau[MIX_NTAU]; };
+
+__device__ __forceinline__ double mix_h(double x, double P, double Qc) {
+#pragma clang fp contract(off)
+  return (x * x + P) * x + Qc;
+}
+__device__ __forceinline__ double mix_g(const MixPar& m, double x, double chi, double xi) {
+#pragma clang fp contract(off)
+  const double a = (chi - x) / m.Rx, b = (xi - (m.c0 + m.c2 * (x * x))) / m.Ry;
+  return a * a + b * b;
+}
+__device__ __forceinline__ double mix_distance(const MixPar& m, double chi, double xi) {
+#pragma clang fp contract(off)
+  const double P = (m.kk - (2.0 * m.c2) * (xi - m.c0)) * m.i2;
+  const double Qc = (-(chi * m.kk)) * m.i2;
+  const double s = sqrt(fmax((-P) / 3.0, 0.0));
+  const double b[4] = {m.xmin, fmin(fmax(-s, m.xmin), m.xmax), fmin(fmax(s, m.xmin), m.xmax), m.xmax};
+  double best = fmin(mix_g(m, b[0], chi, xi), mix_g(m, b[3], chi, xi));
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    double lo = b[i], hi = b[i + 1];
+    const double hl = mix_h(lo, P, Qc), hh = mix_h(hi, P, Qc);
+    const bool has = (hl <= 0.0 && hh >= 0.0) || (hl >= 0.0 && hh <= 0.0);
+    const bool up = hh >= hl;
+#pragma nounroll
+    for (int n = 0; n < MIX_NB; n++) {
+      const double mid = 0.5 * (lo + hi);
+      const bool right = (mix_h(mid, P, Qc) < 0.0) == up;   // the root lies to the right of mid
+      lo = right ? mid : lo;
+      hi = right ? hi : mid;
+    }
+    const double gm = mix_g(m, 0.5 * (lo + hi), chi, xi);
+    best = has ? fmin(best, gm) : best;
+  }
+  return sqrt(best);
+}
+
+// out[e][32], chi = Qdp(nt)[qa]/dp(ps_v), xi = Qdp(nt)[qb]/dp(ps_v) (formed as k_state_q forms Q), dV = colw[e][p]*dh[k], owned points only:
+//   0 sum_A d dV   1 sum_B d dV   2 sum_C d dV   3 sum dV   4, 5, 6 the number of (point, level) in A, B, C (doubles, exact)   7 max d
+//   8 + j  sum dV [chi >= tau_j]  (j < 24; 0 for an unused threshold)
+// The sums in THE ORDER of k_norm_partials (a term outside its class or below its threshold enters as + 0.0, which changes nothing); an
+// element without an owned point gives 0 everywhere.  Same skeleton as k_norm_partials: block = element, lane = (point, level group).
+template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)
+__global__ __launch_bounds__(NORM_THREADS) void k_mix_partials(int qsize, int qa, int qb, const double* __restrict__ Qdp, const double* __restrict__ ps_v,
+                                                               const double* __restrict__ hyai, const double* __restrict__ hybi, double ps0,
+                                                               const int* __restrict__ owner, const double* __restrict__ colw, const double* __restrict__ dh,
+                                                               MixPar m, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double sh[MIX_OUT][NORM_THREADS];
+  const int e = blockIdx.x, t = threadIdx.x, p = t & 15, g = t >> 4;
+  const double* xa = Qdp + ((size_t)e * qsize + qa) * NLEV * 16 + p;
+  const double* xb = Qdp + ((size_t)e * qsize + qb) * NLEV * 16 + p;
+  const double ps = ps_v[(size_t)e * 16 + p], w = colw[(size_t)e * 16 + p];
+  double sA = 0.0, sB = 0.0, sC = 0.0, sV = 0.0, nA = 0.0, nB = 0.0, nC = 0.0, dmax = 0.0, f[MIX_NTAU];
+#pragma unroll
+  for (int j = 0; j < MIX_NTAU; j++) f[j] = 0.0;
+  for (int k = g * NORM_LPG; k < (g + 1) * NORM_LPG; k++) {
+    const double dpk = level_dp(hyai, hybi, ps0, k, ps);
+    const double chi = mixing_ratio(xa[(size_t)k * 16], dpk), xi = mixing_ratio(xb[(size_t)k * 16], dpk);
+    const double dV = w * dh[k];
+    const double d = mix_distance(m, chi, xi);
+    const bool inx = m.xmin <= chi && chi <= m.xmax;
+    const double chord = m.yhi + (chi - m.xmin) * m.sl, curve = m.c0 + m.c2 * (chi * chi);
+    const bool A = inx && chord <= xi && xi <= curve;
+    const bool B = !A && inx && m.ylo <= xi && xi <= m.yhi;
+    const bool C = !A && !B;
+    const double dd = d * dV;
+    sA = sA + (A ? dd : 0.0); sB = sB + (B ? dd : 0.0); sC = sC + (C ? dd : 0.0); sV = sV + dV;
+    nA = nA + (A ? 1.0 : 0.0); nB = nB + (B ? 1.0 : 0.0); nC = nC + (C ? 1.0 : 0.0);
+    dmax = fmax(dmax, d);
+#pragma unroll
+    for (int j = 0; j < MIX_NTAU; j++) f[j] = f[j] + (chi >= m.tau[j] ? dV : 0.0);
+  }
+  sh[0][t] = sA; sh[1][t] = sB; sh[2][t] = sC; sh[3][t] = sV; sh[4][t] = nA; sh[5][t] = nB; sh[6][t] = nC; sh[7][t] = dmax;
+#pragma unroll
+  for (int j = 0; j < MIX_NTAU; j++) sh[8 + j][t] = f[j];
+  __syncthreads();
+  if (t < MIX_OUT) {   // lane t combines entry t
+    const int* own = owner + (size_t)e * 16;
+    const double* v = sh[t];
+    double a = 0.0;
+    for (int i = 0; i < 16; i++) {
+      if (!own[i]) continue;
+      if (t == 7) a = fmax(a, fmax(fmax(v[i], v[16 + i]), fmax(v[32 + i], v[48 + i])));
+      else a = a + (((v[i] + v[16 + i]) + v[32 + i]) + v[48 + i]);
+    }
+    out[(size_t)e * MIX_OUT + t] = a;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // element min/max of Q = Qdp/dp, dp = derived%dp - rhs_multiplier*dt*divdp_proj  (prim_advection_mod.F90:750-775)
 template <int = 0>   // (a template only so that two translation units can include this header: tse_stage3.hip)

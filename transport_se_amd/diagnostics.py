@@ -5,6 +5,9 @@
   from the level heights by the "2*(h-base)" recursion, relative to (q0 - avg(q0)).
 * `column_weights` / `norms_from_partials`: the same norm line without the field on the host -- the device forms every element's share
   over the columns it owns (tse_norm_partials), rank 0 adds the shares exactly.
+* `mixing_diagnostics` / `mixing_from_partials`: the numerical-mixing diagnostics l_r, l_u, l_o and the filament diagnostic l_f of
+  Lauritzen and Thuburn (2012) for two tracers that start on a quadratic curve (DCMIP 1-1's q1, q2) -- from whole fields on the host, and
+  from the element shares the device forms (tse_mix_partials), added exactly on rank 0.
 * `tracer_mass`: the conserved integral behind the "Q,Q diss" line (prim_state_mod.F90:352-385 through
   global_integral, global_norms_mod.F90:39-86).
 * `printstate_lines`: the `qv=  min max sum` lines of prim_printstate (prim_state_mod.F90:341-347).
@@ -106,6 +109,112 @@ def norms_from_partials(partials, gid, nelem, dist_mod=None, rank=0, world=1):
     s = [math.fsum(full[:, j].tolist()) for j in range(4)]
     return dict(L1=float(s[0] / s[1]), L2=float(np.sqrt(s[2]) / np.sqrt(s[3])), Linf=float(full[:, 4].max() / full[:, 5].max()),
                 q_max=float(full[:, 6].max()), q_min=float(full[:, 7].min()))
+
+
+# ---- numerical mixing and filaments (Lauritzen and Thuburn 2012, QJRMS 138, "Evaluating advection/transport schemes using interrelated
+# tracers, scatter plots and numerical mixing diagnostics") ----
+MIX_NB = 60      # bisection steps per interval (csrc/tse_kernels.h: MIX_NB)
+MIX_NTAU = 24    # the most filament thresholds of one call
+MIX_TAU = tuple(k / 100.0 for k in range(10, 101, 5))   # 0.10, 0.15, ..., 1.00 (the paper's thresholds)
+
+
+def mixing_constants(xmin, xmax, c0, c2):
+    """what tse_mix_partials derives from its arguments, each operation rounded once: dict(xmin, xmax, c0, c2, yhi = psi(xmin),
+    ylo = psi(xmax), Rx, Ry, sl = the chord's slope, kk = (Ry*Ry)/(Rx*Rx), i2 = 1/(2*c2*c2)) for the curve psi(x) = c0 + c2*(x*x)"""
+    xmin, xmax, c0, c2 = (np.float64(v) for v in (xmin, xmax, c0, c2))
+    if not (xmax > xmin and c2 < 0):
+        raise ValueError("mixing_constants: needs xmin < xmax and c2 < 0 (xmin = %r, xmax = %r, c2 = %r)" % (xmin, xmax, c2))
+    yhi = c0 + c2 * (xmin * xmin); ylo = c0 + c2 * (xmax * xmax)
+    Rx = xmax - xmin; Ry = yhi - ylo
+    return dict(xmin=xmin, xmax=xmax, c0=c0, c2=c2, yhi=yhi, ylo=ylo, Rx=Rx, Ry=Ry, sl=(ylo - yhi) / Rx, kk=(Ry * Ry) / (Rx * Rx),
+                i2=np.float64(1.0) / ((np.float64(2.0) * c2) * c2))
+
+
+def mixing_distance(m, chi, xi):
+    """d = sqrt(min over x in [xmin, xmax] of ((chi-x)/Rx)^2 + ((xi-psi(x))/Ry)^2): the normalised distance of (chi, xi) to the curve, by
+    the device's algorithm (csrc/tse_kernels.h: mix_distance) operation for operation -- the stationary points are the roots of the cubic
+    h(x) = (x*x + P)*x + Qc, bracketed by the break points xmin, clamp(-s), clamp(s), xmax, s = sqrt(max(-P/3, 0)), and found by MIX_NB
+    bisection steps on each of the three intervals; the end points are candidates of their own"""
+    chi = np.asarray(chi, np.float64); xi = np.asarray(xi, np.float64)
+    xmin, xmax, c0, c2, Rx, Ry, kk, i2 = (m[k] for k in ("xmin", "xmax", "c0", "c2", "Rx", "Ry", "kk", "i2"))
+
+    def g(x):
+        a = (chi - x) / Rx; b = (xi - (c0 + c2 * (x * x))) / Ry
+        return a * a + b * b
+    P = (kk - (2.0 * c2) * (xi - c0)) * i2
+    Qc = (-(chi * kk)) * i2
+
+    def h(x):
+        return (x * x + P) * x + Qc
+    s = np.sqrt(np.maximum((-P) / 3.0, 0.0))
+    b = [np.full_like(chi, xmin), np.minimum(np.maximum(-s, xmin), xmax), np.minimum(np.maximum(s, xmin), xmax), np.full_like(chi, xmax)]
+    best = np.minimum(g(b[0]), g(b[3]))
+    for i in range(3):
+        lo, hi = b[i], b[i + 1]
+        hl, hh = h(lo), h(hi)
+        has = ((hl <= 0) & (hh >= 0)) | ((hl >= 0) & (hh <= 0))
+        up = hh >= hl
+        for _ in range(MIX_NB):
+            mid = 0.5 * (lo + hi)
+            right = (h(mid) < 0) == up
+            lo = np.where(right, mid, lo); hi = np.where(right, hi, mid)
+        best = np.where(has, np.minimum(best, g(0.5 * (lo + hi))), best)
+    return np.sqrt(best)
+
+
+def mixing_classes(m, chi, xi):
+    """(A, B, C): real mixing (between the chord and the curve), range-preserving unmixing (the rest of the rectangle
+    [xmin, xmax] x [ylo, yhi]) and overshooting (everything else), as boolean arrays; every point is in exactly one"""
+    chi = np.asarray(chi, np.float64); xi = np.asarray(xi, np.float64)
+    inx = (m["xmin"] <= chi) & (chi <= m["xmax"])
+    chord = m["yhi"] + (chi - m["xmin"]) * m["sl"]; curve = m["c0"] + m["c2"] * (chi * chi)
+    A = inx & (chord <= xi) & (xi <= curve)
+    B = ~A & inx & (m["ylo"] <= xi) & (xi <= m["yhi"])
+    return A, B, ~A & ~B
+
+
+def mixing_diagnostics(ne, lat, lon, chi, xi, zm, xmin, xmax, c0, c2, tau, chi0=None):
+    """dict(l_r, l_u, l_o, l_f=[...], d_max, counts=(nA, nB, nC)) from whole fields chi, xi [nelem][nlev][4][4] on the unique-column grid:
+    l_r, l_u, l_o = sum over class A, B, C of d dV / sum dV with dcmip_norms' dV, l_f(tau) = 100 * ((sum of dV where chi >= tau) / (the same
+    of chi0, the field at t0; default: chi itself)) -- the quotient first, so that an unchanged area gives exactly 100 --, 0.0 where the
+    denominator is 0.  The terms are the device's in every bit; the sums are numpy's."""
+    nlev = chi.shape[1]
+    m = mixing_constants(xmin, xmax, c0, c2)
+    cols, colw = _norm_columns(ne, lat, lon)
+    x = np.moveaxis(chi, 1, 0).reshape(nlev, -1)[:, cols]
+    y = np.moveaxis(xi, 1, 0).reshape(nlev, -1)[:, cols]
+    dV = colw[None, :] * layer_depths(zm)[:, None]
+    d = mixing_distance(m, x, y)
+    cls = mixing_classes(m, x, y)
+    ddV = d * dV
+    V = dV.sum()
+    x0 = x if chi0 is None else np.moveaxis(chi0, 1, 0).reshape(nlev, -1)[:, cols]
+    l_f = []
+    for t in np.asarray(tau, np.float64).reshape(-1):
+        a0 = np.where(x0 >= t, dV, 0.0).sum()
+        l_f.append(float(100.0 * (np.where(x >= t, dV, 0.0).sum() / a0)) if a0 != 0 else 0.0)
+    return dict(l_r=float(np.where(cls[0], ddV, 0.0).sum() / V), l_u=float(np.where(cls[1], ddV, 0.0).sum() / V),
+                l_o=float(np.where(cls[2], ddV, 0.0).sum() / V), l_f=l_f, d_max=float(d.max()),
+                counts=tuple(int(c.sum()) for c in cls))
+
+
+def mixing_from_partials(partials, partials0, gid, nelem, dist_mod=None, rank=0, world=1, ntau=MIX_NTAU):
+    """partials, partials0 [n_local][32] (tse_mix_partials now and at t0: one row per local element) -> the dict of mixing_diagnostics on
+    rank 0 (None elsewhere): entries 0 to 3 and 8.. added exactly over all elements (math.fsum: no order, hence no dependence on the
+    partition), l_r, l_u, l_o = S0, S1, S2 / S3, l_f(tau_j) = 100 * (S(8+j)(t) / S(8+j)(t0)) (0.0 where the denominator is 0) for j < ntau,
+    the counts added (small integers held in doubles: exact), d_max = the largest entry 7"""
+    both = np.concatenate([np.asarray(partials, dtype=np.float64), np.asarray(partials0, dtype=np.float64)], axis=1)
+    full = gather_by_gid(both, gid, nelem, dist_mod, rank, world)
+    if full is None:
+        return None
+    now, then = full[:, :32], full[:, 32:]
+    S = [math.fsum(now[:, j].tolist()) for j in range(4)]
+    l_f = []
+    for j in range(8, 8 + int(ntau)):
+        a0 = math.fsum(then[:, j].tolist())
+        l_f.append(float(100.0 * (math.fsum(now[:, j].tolist()) / a0)) if a0 != 0 else 0.0)
+    return dict(l_r=float(S[0] / S[3]), l_u=float(S[1] / S[3]), l_o=float(S[2] / S[3]), l_f=l_f, d_max=float(now[:, 7].max()),
+                counts=tuple(int(now[:, j].sum()) for j in (4, 5, 6)))
 
 
 def tracer_mass(spheremp, qdp):

@@ -137,6 +137,8 @@ class PrimRun:
         self.lat, self.lon = geo["lat"][mine], geo["lon"][mine]
         self._mesh_latlon = (geo["lat"], geo["lon"])   # the whole mesh: which point owns a GLL column is a global question (norm_reference)
         self._norm = None
+        self._weights_set = False   # tse_norm_setup has been called (norm_reference or mixing_reference)
+        self._mix = None
         callback = None
         if world > 1:
             if exchange not in ("rccl", "torch", "staged"):
@@ -270,6 +272,7 @@ class PrimRun:
         lat, lon = self._mesh_latlon
         owner, colw, dh = dg.column_weights(self.ne, lat, lon, dg.level_heights(self.hv.hyam, self.hv.hybm))
         self.hip.norm_setup(owner[self.mine], colw[self.mine], dh)
+        self._weights_set = True
         sum0 = self.hip.norm_reference(tl, tracer)
         full = dg.gather_by_gid(sum0, self.mine, self.nelem, self._dist, self.rank, self.world)
         box = [math.fsum(full.tolist()) / (self.nlev * int(owner.sum())) if self.rank == 0 else None]
@@ -287,6 +290,40 @@ class PrimRun:
             raise RuntimeError("PrimRun.norms: call norm_reference first")
         tracer, avg = self._norm
         return dg.norms_from_partials(self.hip.norm_partials(tl, tracer, avg), self.mine, self.nelem, self._dist, self.rank, self.world)
+
+    def mixing_reference(self, tl=1, qa=0, qb=1, tau=None, c0=0.9, c2=-0.8):
+        """collective: take Q(tl) of tracers qa (chi) and qb (xi = c0 + c2*chi^2 at this time: DCMIP 1-1's q1 and q2) as the start of the
+        mixing and filament diagnostics of Lauritzen and Thuburn (2012).  Sets up the norm weights if norm_reference has not, takes xmin and
+        xmax as the global extrema of chi (tse_element_qdiag; broadcast from rank 0, so that every rank passes the same bits) and keeps this
+        rank's element partials of t0, the denominators of l_f.  tau: the filament thresholds (default 0.10, 0.15, ..., 1.00).  Returns
+        (xmin, xmax)."""
+        from . import diagnostics as dg
+        tau = np.asarray(dg.MIX_TAU if tau is None else tau, np.float64).reshape(-1)
+        if not self._weights_set:
+            lat, lon = self._mesh_latlon
+            owner, colw, dh = dg.column_weights(self.ne, lat, lon, dg.level_heights(self.hv.hyam, self.hv.hybm))
+            self.hip.norm_setup(owner[self.mine], colw[self.mine], dh)
+            self._weights_set = True
+        _, _, lo, hi = self.hip.element_qdiag(tl)
+        ext = dg.gather_by_gid(np.stack([lo[:, qa], hi[:, qa]], 1), self.mine, self.nelem, self._dist, self.rank, self.world)
+        box = [(float(ext[:, 0].min()), float(ext[:, 1].max())) if self.rank == 0 else None]
+        if self.world > 1:
+            self._dist.broadcast_object_list(box, src=0)
+        xmin, xmax = box[0]
+        par = (qa, qb, xmin, xmax, float(c0), float(c2), tau)
+        self._mix = (par, self.hip.mix_partials(tl, *par))
+        return xmin, xmax
+
+    def mixing(self, tl):
+        """collective: dict(l_r, l_u, l_o, l_f=[...], d_max, counts=(nA, nB, nC)) of Q(tl) against the start taken by mixing_reference, on
+        rank 0 (None elsewhere): element partials from the device, added exactly on rank 0 (diagnostics.mixing_from_partials) -- the same
+        digits on any number of ranks, and no field on the host"""
+        from . import diagnostics as dg
+        if self._mix is None:
+            raise RuntimeError("PrimRun.mixing: call mixing_reference first")
+        par, P0 = self._mix
+        return dg.mixing_from_partials(self.hip.mix_partials(tl, *par), P0, self.mine, self.nelem, self._dist, self.rank, self.world,
+                                       ntau=par[-1].size)
 
     def close(self):
         self.hip.close()

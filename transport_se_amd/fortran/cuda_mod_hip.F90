@@ -43,6 +43,8 @@ module cuda_mod
   ! the DCMIP error norms from element partials (INTEGRATION.md section 2c): the device forms every element's share of the norm line's
   ! sums and extrema, the host reduces them over elements and ranks (repro_sum for the sums)
   public :: norm_setup_hip, norm_reference_hip, norm_partials_hip
+  ! the numerical-mixing and filament diagnostics of two correlated tracers from element partials (INTEGRATION.md section 2d)
+  public :: mix_partials_hip
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
   integer(c_int), save :: res_nstep = 0   ! the library's step count after the last prim_run_subcycle_hip
   integer(kind=8), save :: t_c0
@@ -151,6 +153,9 @@ module cuda_mod
      end function
      integer(c_int) function tse_norm_partials(ctx, nt, q, avg, out) bind(C, name='tse_norm_partials')
        import; type(c_ptr), value :: ctx, out; integer(c_int), value :: nt, q; real(c_double), value :: avg
+     end function
+     integer(c_int) function tse_mix_partials(ctx, nt, qa, qb, xmin, xmax, c0, c2, tau, ntau, out) bind(C, name='tse_mix_partials')
+       import; type(c_ptr), value :: ctx, tau, out; integer(c_int), value :: nt, qa, qb, ntau; real(c_double), value :: xmin, xmax, c0, c2
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -692,5 +697,23 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine norm_partials_hip
+
+  ! out(1:32,ie): the element's share of the mixing and filament diagnostics (Lauritzen and Thuburn 2012) of tracers qa (chi) and qb (xi),
+  ! counted from 1, against the curve xi = c0 + c2*chi**2 (c2 < 0) over chi in [xmin, xmax], with the weights of norm_setup_hip:
+  ! rows 1:3 sum d*dV over class A (real mixing), B (range-preserving unmixing), C (overshooting), row 4 sum dV, rows 5:7 the class counts,
+  ! row 8 max d, rows 9:8+ntau sum dV where chi >= tau(j).  The host adds rows 1:4 and 9: over elements and ranks with repro_sum:
+  ! l_r, l_u, l_o = s1, s2, s3 / s4; l_f(tau_j) = 100 * s(8+j)(t) / s(8+j)(t0).  ntau <= 24.
+  subroutine mix_partials_hip(nt, qa, qb, xmin, xmax, c0, c2, tau, ntau, out)
+    integer,        intent(in)          :: nt, qa, qb, ntau
+    real(c_double), intent(in)          :: xmin, xmax, c0, c2
+    real(c_double), intent(in),  target :: tau(*)
+    real(c_double), intent(out), target :: out(32,nelemd)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_mix_partials(ctx, int(nt,c_int), int(qa-1,c_int), int(qb-1,c_int), xmin, xmax, c0, c2, c_loc(tau), int(ntau,c_int), &
+                                c_loc(out)), 'mix_partials_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine mix_partials_hip
 
 end module cuda_mod

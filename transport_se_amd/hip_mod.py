@@ -293,6 +293,16 @@ class HipMod:
         self._chk(self.L.tse_norm_partials(self.h, int(nt), int(q), float(avg), _vp(out)))
         return out
 
+    def mix_partials(self, nt, qa, qb, xmin, xmax, c0, c2, tau=()):
+        """[nelemd][32]: the element shares of the mixing and filament diagnostics of tracers qa (chi) and qb (xi) against the curve
+        xi = c0 + c2*chi^2 over chi in [xmin, xmax], with the weights of norm_setup (include/transport_se_hip.h: tse_mix_partials;
+        diagnostics.mixing_from_partials turns them into l_r, l_u, l_o and l_f)"""
+        tau = np.ascontiguousarray(tau, np.float64).reshape(-1)
+        out = np.empty((self.nelemd, 32))
+        self._chk(self.L.tse_mix_partials(self.h, int(nt), int(qa), int(qb), float(xmin), float(xmax), float(c0), float(c2),
+                                          _vp(tau) if tau.size else None, int(tau.size), _vp(out)))
+        return out
+
     def get_qminmax(self):
         qmin = np.empty((self.nelemd, self.qsize, self.nlev)); qmax = np.empty_like(qmin)
         self._chk(self.L.tse_get_qminmax(self.h, _vp(qmin), _vp(qmax)))

@@ -3,6 +3,7 @@
     python -m transport_se_amd.prim_main < dcmip1-1.nl                 # one GPU
     python -m transport_se_amd.prim_main --gpus 8 < dcmip1-1.nl        # starts 8 ranks itself (one per GPU)
     bin/preqx < dcmip1-1.nl                                            # the name the reference's run scripts call ($EXE)
+    bin/preqx --mixing < dcmip1-1.nl                                   # + the mixing / filament lines of q1, q2 (dcmip1-1 only)
 
 Reads the reference's Fortran namelists from stdin the way prim_main/readnl do (src/prim_main.F90:47,
 src/share/namelist_mod.F90:159-351: rank 0 reads, everybody gets a copy), runs the device-resident prim_run loop and leaves
@@ -114,6 +115,19 @@ def settings(groups):
         raise SystemExit("prim_main: test_case must be dcmip1-1 or dcmip1-2")
     s["test"] = 1 if tc.startswith("dcmip1-1") else 2
     return s
+
+
+def check_mixing(s):
+    """--mixing: the mixing and filament diagnostics need the correlated pair q1, q2 = 0.9 - 0.8*q1^2 of DCMIP 1-1 (dcmip_point)"""
+    if s["test"] != 1 or s["qsize"] < 2:
+        raise SystemExit("prim_main: --mixing needs test_case = dcmip1-1 and qsize >= 2 (its tracers q1 and q2 = 0.9 - 0.8*q1^2 are the "
+                         "correlated pair; test_case = %r, qsize = %d)" % (s["test_case"], s["qsize"]))
+
+
+def mixing_lines(nstep, mix, tau):
+    """the two lines of --mixing: l_r, l_u, l_o (real mixing, range-preserving unmixing, overshooting) and l_f per threshold"""
+    return ["mixing   nstep=%d: l_r=%.6e l_u=%.6e l_o=%.6e" % (nstep, mix["l_r"], mix["l_u"], mix["l_o"]),
+            "filament nstep=%d:" % nstep + "".join(" l_f(%.2f)=%.4f" % (t, f) for t, f in zip(tau, mix["l_f"]))]
 
 
 SHIPPED_VCOORD = {"vfile_mid": "acme-72m.ascii", "vfile_int": "acme-72i.ascii"}   # transport_se_amd/data/vcoord
@@ -230,6 +244,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="prim_main")
     ap.add_argument("--gpus", type=int, default=0, help="start this many ranks (one per GPU) and feed them the namelist from stdin")
     ap.add_argument("--namelist", default=None, help="read the namelists from this file instead of stdin")
+    ap.add_argument("--mixing", action="store_true", help="dcmip1-1 only: print the numerical-mixing diagnostics l_r, l_u, l_o and the filament "
+                    "diagnostic l_f of tracers 1 and 2 (Lauritzen and Thuburn 2012) at the middle of the run and at its end")
     a = ap.parse_args(argv)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         text = open(a.namelist).read() if a.namelist else sys.stdin.read()
@@ -239,7 +255,7 @@ def main(argv=None):
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
         rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr", "127.0.0.1",
-                              "--master-port", str(port), "-m", "transport_se_amd.prim_main", "--namelist", f.name])
+                              "--master-port", str(port), "-m", "transport_se_amd.prim_main", "--namelist", f.name] + (["--mixing"] if a.mixing else []))
         os.unlink(f.name)
         return rc
     rank, world, local = _rank_world()
@@ -275,6 +291,8 @@ def main(argv=None):
     if world > 1:
         dist.broadcast_object_list(box, src=0)
     s = settings(parse_namelists(box[0]))
+    if a.mixing:
+        check_mixing(s)
     hv = vertical_coordinate(s)
 
     from .driver import PrimRun
@@ -304,6 +322,11 @@ def main(argv=None):
     run.norm_reference()                                     # Q(t0) of the norm script's tracer (Q for 1-1, Q2 for 1-2) stays on the device
     m0 = gsum(hip.element_mass(1))
     nsteps = (s["nmax"] // s["rsplit"]) * s["rsplit"]
+    mix_mid = None
+    if a.mixing:
+        run.mixing_reference()                               # q1, q2 of t0: the range of q1 and the filament areas, kept on this rank
+        # the end of the remap cycle nearest to the middle of the run, where the deformation is largest
+        mix_mid = min(max(int(nsteps / (2.0 * s["rsplit"]) + 0.5), 1) * s["rsplit"], nsteps)
     say(" nmax = %d tracer steps, tstep = %g, ne = %d, qsize = %d, nu_q = %g, %d rank(s), exchange = %s"
         % (nsteps, s["tstep"], s["ne"], s["qsize"], s["nu_q"], world, run.exchange_kind))
     if world > 1:
@@ -343,6 +366,8 @@ def main(argv=None):
                 stop = min(nsteps, end)
                 if end <= nsteps:
                     before = (run.nstep,) + qdiag(np1 if run.nstep else 1)[:2]   # Qdp(n0) of the cycle's first step = what the last step wrote
+        if mix_mid is not None and n < mix_mid:
+            stop = min(stop, mix_mid)
         if watchdog.limit > 0:   # bounded chunks, so that "no progress" can be told from "a long run" (whole rsplit cycles)
             stop = min(stop, n + max(s["rsplit"], WATCHDOG_CHUNK // s["rsplit"] * s["rsplit"]))
         try:
@@ -364,6 +389,10 @@ def main(argv=None):
                                                                     _fortran_e((m2[t] - before[1][t]) / s["tstep"], 15, 7),
                                                                     _fortran_e((v2[t] - before[2][t]) / s["tstep"], 15, 7)))
             before = None
+        if n == mix_mid and n < nsteps:
+            mix = run.mixing(np1)
+            if rank == 0:
+                print("\n".join(mixing_lines(run.nstep, mix, dg.MIX_TAU)))
     hip.synchronize()
     wall = time.perf_counter() - t0
     groups = {k: hip.kernel_time(k)[0] / 1e3 for k in ("advance", "dss", "lap", "minmax", "level", "remap", "dcmip")}
@@ -385,8 +414,11 @@ def main(argv=None):
     # (element partials formed on the device, added exactly on rank 0: no tracer field crosses to the host)
     nrm = run.norms(np1)
     m1 = gsum(hip.element_mass(np1))
+    mix = run.mixing(np1) if a.mixing else None
     if rank == 0:
         print("DCMIP 1-%d: L1=%8.6f L2=%8.6f Linf=%8.6f q_max=%8.6f q_min=%14.6e" % (s["test"], nrm["L1"], nrm["L2"], nrm["Linf"], nrm["q_max"], nrm["q_min"]))
+        if a.mixing:
+            print("\n".join(mixing_lines(run.nstep, mix, dg.MIX_TAU)))
         for t in range(s["qsize"]):
             print("Q%d mass: %22.14E -> %22.14E (relative change %10.3e)" % (t + 1, m0[t], m1[t], (m1[t] - m0[t]) / max(abs(m0[t]), 1e-300)))
         print("prim_run wall %.3f s: %.4e tracer-DOF-steps/s on %d rank(s)" % (float(stack[:, 0].max()), nelem * 16 * run.nlev * s["qsize"] * nsteps / float(stack[:, 0].max()), world))
