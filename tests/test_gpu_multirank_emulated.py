@@ -23,11 +23,16 @@ def _run(world, ne=None):
     return _run_ne(world)
 
 
-def _run_ne(world):
+def _run_ne(world, ne=None, qsize=None, nu_q=None, limiter_option=8, rsplit=3, body=None):
+    """`world` contexts on one GPU.  Without `body`: the DCMIP 1-1 initial state and two prim_run_subcycle cycles -> (Qdp, divdp_proj) by
+    global element.  With body(rank, hip, mine, geo, hv) -> result: each rank's context (ne, qsize, nu_q, limiter_option, rsplit as
+    given) is handed to body instead -- the initial state and the calls are the caller's, every rank must make the same ones --
+    and the list of (mine, result) per rank comes back."""
+    ne, qsize, nu_q = ne or NE, qsize or QSIZE, NU_Q if nu_q is None else nu_q
     hv = HvCoord()
-    topo = cm.topology(NE); geo = cm.geometry(NE, topo)
-    nelem = 6 * NE * NE
-    owner = partition(NE, world)
+    topo = cm.topology(ne); geo = cm.geometry(ne, topo)
+    nelem = 6 * ne * ne
+    owner = partition(ne, world)
     descs = [cm.edge_descriptors(topo, owner, r) for r in range(world)]
     hip = C.CDLL("libamdhip64.so")
     barrier = threading.Barrier(world)
@@ -77,13 +82,22 @@ def _run_ne(world):
             elem = dict(Dinv=geo["Dinv"][mine], metdet=geo["metdet"][mine], rmetdet=geo["rmetdet"][mine],
                         spheremp=geo["spheremp"][mine], rspheremp=geo["rspheremp"][mine],
                         putmapP=d["putmapP"], getmapP=d["getmapP"], reverse=d["reverse"])
-            h = HipMod(elem, cm.dvv(), (hv.hyai, hv.hybi, hv.ps0), QSIZE, NU_Q, device=0,
+            h = HipMod(elem, cm.dvv(), (hv.hyai, hv.hybi, hv.ps0), qsize, nu_q, limiter_option=limiter_option, rsplit=rsplit, device=0,
                        schedule=dict(send=d["send"], recv=d["recv"]), exchange=make_exchange(r) if world > 1 else None)
             ctxs[r] = h
+            if body is not None:
+                try:
+                    result[r] = (mine, body(r, h, mine, geo, hv))
+                except BaseException:
+                    barrier.abort()     # the other ranks may wait for this one in an exchange: release them before this context closes
+                    raise
+                finally:
+                    h.close()
+                return
             h.dcmip_init(1, geo["lat"][mine], geo["lon"][mine], hv.hyam, hv.hybm)
             h.dcmip_set_initial()
             assert h.prim_run_subcycle(DT, 2, 0) == 6
-            result[r] = (mine, h.fetch("qdp", (2, mine.size, QSIZE, 72, 4, 4))[0].copy(),
+            result[r] = (mine, h.fetch("qdp", (2, mine.size, qsize, 72, 4, 4))[0].copy(),
                          h.fetch("divdp_proj", (mine.size, 72, 4, 4)).copy())
             h.close()
         except Exception as ex:  # noqa: BLE001
@@ -99,7 +113,9 @@ def _run_ne(world):
     for t in ts:
         t.join(timeout=240)
     assert not errors, errors
-    q = np.empty((nelem, QSIZE, 72, 4, 4)); dv = np.empty((nelem, 72, 4, 4))
+    if body is not None:
+        return result
+    q = np.empty((nelem, qsize, 72, 4, 4)); dv = np.empty((nelem, 72, 4, 4))
     for mine, qq, dd in result:
         q[mine] = qq; dv[mine] = dd
     return q, dv
