@@ -23,6 +23,15 @@ __device__ __forceinline__ double dppq(double x) {
   hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
 }
+// one bank-masked DPP row move of a double (two v_mov_b32_dpp): the lanes of the banks in BANKS (a bank = 4 lanes of the 16-lane row)
+// take `src` from the lane CTRL names (0x110 + n: row_shr:n, from lane - n; 0x100 + n: row_shl:n, from lane + n), every other lane
+// keeps `old`.  An exchange and the select that would follow it, in one move.
+template <int CTRL, int BANKS>
+__device__ __forceinline__ double dpp_row_banks(double old, double src) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xF, BANKS, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xF, BANKS, false);
+  return __hiloint2double(hi, lo);
+}
 // broadcast quad lane M to the 4 lanes of the quad
 template <int M>
 __device__ __forceinline__ double quad_bcast(double x) { return dppq<M * 0x55>(x); }

@@ -550,12 +550,6 @@ struct GatherArgs {
 struct BoundsLds { static constexpr int ENT = PS + NER; double v[2][ENT][2][CL]; };   // 8 KB
 struct PatchLds { double v[2][Patch::LDS_ENT][CL]; };   // 2 x 13.3 KB
 
-__device__ __forceinline__ double swz_xor4(double x) {   // value of lane ^ 4 (the other level of the pair)
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __builtin_amdgcn_ds_swizzle(lo, 0x101F); hi = __builtin_amdgcn_ds_swizzle(hi, 0x101F);   // and 0x1f, or 0, xor 4
-  return __hiloint2double(hi, lo);
-}
-
 // block -> (patch, chunk), lane -> (slot of the patch, level of the chunk, row).  The 8 XCDs each take a contiguous range of
 // patches and walk it chunk by chunk, so that the patches whose own values are a block's ring are in flight on the same XCD.
 struct PatchId { int patch, tslot /* patch * PS + position: index into the patch tables */, slot /* storage slot of the element */, e, k, j; bool live, any; };
@@ -583,6 +577,7 @@ struct RowGather {
   unsigned ring;       // plane-relative byte offset of the lane's half of a ring entry
   unsigned lw, lw1, lwr;  // LDS byte offsets (buffer 0) where the lane publishes its two own loads / its ring load
   unsigned lr[5];      // LDS byte offsets (buffer 0) of the lane's five neighbour values
+  unsigned lo[4];      // LDS byte offsets (buffer 0) of the lane's four own values (its level of the published pieces)
   double rs[4];
 };
 __device__ __forceinline__ void gather_setup(RowGather& R, PatchLds& L, const GatherArgs& A, const PatchId& P) {
@@ -616,6 +611,8 @@ __device__ __forceinline__ void gather_setup(RowGather& R, PatchLds& L, const Ga
   R.lwr = (unsigned)((Patch::LDS_RING + r) * CL + half * 2) * 8u;
 #pragma unroll
   for (int m = 0; m < 5; m++) R.lr[m] = ((unsigned)le[m] * CL + kk) * 8u;
+#pragma unroll
+  for (int i = 0; i < 4; i++) R.lo[i] = (unsigned)(lds_own_entry(sl, j * 4 + i) * CL + kk) * 8u;
   load4(A.rspheremp + (size_t)P.e * 16 + j * 4, R.rs);
 }
 // loads only, all 3 in flight together; every use comes later.
@@ -628,18 +625,17 @@ __device__ __forceinline__ void gather_issue(RowGather& R, const GatherArgs& A, 
   raw.w[1] = *reinterpret_cast<const double2*>(pq + R.own1);
   raw.r = *reinterpret_cast<const double2*>(pq + R.ring);
 }
-// publish the lane's loads of tracer q in LDS buffer `b` and keep its own 4 values (level pair exchange: keep my level's half
-// of what I loaded, send the other half to lane ^ 4).  Holes publish their copy into their own (unreferenced) entries.
-__device__ __forceinline__ void gather_publish(const RowGather& R, PatchLds& L, int b, int k, const GatherRaw& raw, double v[4]) {
-  const bool odd = k & 1;
+// publish the lane's loads of tracer q in LDS buffer `b`.  The lane loaded two points of its row for both levels of a pair and its
+// partner (lane ^ 4) the other two; the pieces are not sorted in registers: the lane's own 4 values come back out of the image
+// behind the barrier (gather_own), with its neighbour values.  Holes publish their copy into their own (unreferenced) entries and
+// read that back.
+__device__ __forceinline__ void gather_publish(const RowGather& R, PatchLds& L, int b, const GatherRaw& raw) {
   char* base = reinterpret_cast<char*>(&L.v[b][0][0]);
-  *reinterpret_cast<double2*>(base + R.lw) = raw.w[0];
-  *reinterpret_cast<double2*>(base + R.lw1) = raw.w[1];
-  *reinterpret_cast<double2*>(base + R.lwr) = raw.r;
-  const double r0 = swz_xor4(odd ? raw.w[0].x : raw.w[0].y), r1 = swz_xor4(odd ? raw.w[1].x : raw.w[1].y);
-  v[0] = odd ? r0 : raw.w[0].x; v[1] = odd ? raw.w[0].y : r0; v[2] = odd ? r1 : raw.w[1].x; v[3] = odd ? raw.w[1].y : r1;
-  // the values must have left `raw` before the next tracer's loads are issued into it
-  asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
+  // (component by component: as whole-struct copies, memory to memory, the three pieces would keep `raw` in scratch memory)
+  *reinterpret_cast<double2*>(base + R.lw) = make_double2(raw.w[0].x, raw.w[0].y);
+  *reinterpret_cast<double2*>(base + R.lw1) = make_double2(raw.w[1].x, raw.w[1].y);
+  *reinterpret_cast<double2*>(base + R.lwr) = make_double2(raw.r.x, raw.r.y);
+  asm volatile("" : : : "memory");   // (written before the next tracer's loads reuse `raw`)
 }
 // all LDS writes of the workgroup have landed; the loads of the next tracer stay in flight (no vmcnt wait)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory"); }
@@ -651,12 +647,16 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // for bit the 4-tracer run (tests/test_gpu_baseline_configs.py).  An even tracer count therefore ends with a SURPLUS second step that
 // repeats the last tracer (it issues that tracer's stores; its own result is dropped) instead of a fourth copy of the body -- the
 // form before round 4, which gave the last tracer of an even count other last bits than the same tracer inside a longer run.
+// The LDS buffer of a step follows from its ROLE (0, 1, 0), a constant per copy of the body: every LDS access of a step is then
+// "address register + immediate".  Named by the tracer's parity instead, the second step of a pair -- whose tracer is q_ + 1 or,
+// as the surplus step, q_ -- had a run-time buffer and paid one address add per LDS access.  The surplus step so publishes and
+// reads in buffer 0 like any second step (last read two steps before, behind the first step's barrier).
 #define TSE_TRACER_PAIRS(step, put, qsize, A, B)                          \
   do {                                                                    \
-    step(0, nullptr, 0, A);                                               \
+    step(0, nullptr, 0, A, 0);                                            \
     for (int q_ = 1; q_ < (qsize); q_ += 2) {                             \
-      step(q_, &A, q_ - 1, B);                                            \
-      step(q_ + 1 < (qsize) ? q_ + 1 : q_, &B, q_, A);                    \
+      step(q_, &A, q_ - 1, B, 1);                                         \
+      step(q_ + 1 < (qsize) ? q_ + 1 : q_, &B, q_, A, 0);                 \
     }                                                                     \
     if ((qsize) & 1) put(A, (qsize) - 1);                                 \
   } while (0)
@@ -686,6 +686,12 @@ __device__ __forceinline__ void flush_bounds(const BoundsStage& S, int g, const 
   double* dst = (a ? mx_out : mn_out) + (((size_t)el * NCHUNK + kchunk) * mm_qpad(qsize) + g * 4) * CL + piece * 2;
   *reinterpret_cast<double2*>(dst) = v;
 }
+// the lane's own 4 values (points i of its row at its level) out of the image: behind the barrier that follows their publish
+__device__ __forceinline__ void gather_own(const RowGather& R, const PatchLds& L, int b, double v[4]) {
+  const char* base = reinterpret_cast<const char*>(&L.v[b][0][0]);
+#pragma unroll
+  for (int i = 0; i < 4; i++) v[i] = *reinterpret_cast<const double*>(base + R.lo[i]);
+}
 // the reference's order per point: edge contributions (S, E, N, W) first, then the corner; an absent one adds +0.0
 __device__ __forceinline__ void gather_sum(const RowGather& R, const PatchLds& L, int b, int j, const double v[4], double out[4]) {
   const bool edge = (j == 0) | (j == 3);
@@ -707,18 +713,22 @@ __device__ __forceinline__ void gather_sum(const RowGather& R, const PatchLds& L
 // DSS of the extra plane on read, before the tracer loop of a DSS-on-read kernel (LDS buffer 1: the loop starts on buffer 0, and
 // its barrier of tracer 0 separates these reads from the publish of tracer 1 into buffer 1).  All lanes of the block call it.
 __device__ __forceinline__ void gather_var_plane(RowGather& R, PatchLds& L, const GatherArgs& A, const double* __restrict__ src, int plane,
-                                                 int j, int k, double x[4]) {
+                                                 int j, double x[4]) {
   GatherRaw raw;
   double own[4];
   gather_issue(R, A, src, plane, raw);
-  gather_publish(R, L, 1, k, raw, own);
+  gather_publish(R, L, 1, raw);
   lds_barrier();
+  gather_own(R, L, 1, own);
   gather_sum(R, L, 1, j, own, x);
 }
 
 // The slab kernels' output into the scratch layout: the lane's 4 values (points i of row j at level k) leave as two 16-byte
 // stores shared with the lane that holds the other level of the pair (even level: points 0,2 for both levels; odd: 1,3),
-// instead of four 8-byte stores.  All lanes must call it (the swizzle needs both lanes of a pair); `live` gates the stores.
+// instead of four 8-byte stores.  The partner is lane +- 4 of the 16-lane DPP row and a DPP bank is one level of a slot, so the
+// exchange is two bank-masked row shifts per piece (dpp_row_banks): the odd levels take their partner's point 1 / 3 into the first
+// word, the even levels their partner's point 0 / 2 into the second, and the other banks keep what they hold -- no select and no LDS
+// operation in front of the stores.  All lanes must call it (the shifts need both lanes of a pair); `live` gates the stores.
 struct RowStore { unsigned o0, o1; bool s0, s1; };   // plane-relative offsets (doubles) of the lane's two stores, and whether each is made
 // pexp (k_lap1<1> only): lines of the slot that hold points some other patch or rank reads (tse_tables.cpp: slot_point_order puts every exported
 // edge into the slot's first lines); the store of a point beyond them is dropped -- nobody reads the first Laplacian of such a point
@@ -732,12 +742,13 @@ __device__ __forceinline__ RowStore row_store_setup(Scr S, const unsigned long l
   return RowStore{(base + ppos(perm, p0)) * CL + ((k & (CL - 1)) & ~1), (base + ppos(perm, p1)) * CL + ((k & (CL - 1)) & ~1),
                   ppos(perm, p0) < lim, ppos(perm, p1) < lim};
 }
-__device__ __forceinline__ void store_row_pair(double* __restrict__ plane /* &T[q][0] */, const RowStore& R, int k, bool live, const double v[4]) {
-  const bool odd = k & 1;
-  const double r0 = swz_xor4(odd ? v[0] : v[1]), r1 = swz_xor4(odd ? v[2] : v[3]);
+__device__ __forceinline__ void store_row_pair(double* __restrict__ plane /* &T[q][0] */, const RowStore& R, bool live, const double v[4]) {
+  // row_shr:4 into banks 1 and 3 (odd levels, from lane - 4); row_shl:4 into banks 0 and 2 (even levels, from lane + 4)
+  const double x0 = dpp_row_banks<0x114, 0xA>(v[0], v[1]), y0 = dpp_row_banks<0x104, 0x5>(v[1], v[0]);
+  const double x1 = dpp_row_banks<0x114, 0xA>(v[2], v[3]), y1 = dpp_row_banks<0x104, 0x5>(v[3], v[2]);
   if (live) {
-    if (R.s0) *reinterpret_cast<double2*>(plane + R.o0) = odd ? make_double2(r0, v[1]) : make_double2(v[0], r0);
-    if (R.s1) *reinterpret_cast<double2*>(plane + R.o1) = odd ? make_double2(r1, v[3]) : make_double2(v[2], r1);
+    if (R.s0) *reinterpret_cast<double2*>(plane + R.o0) = make_double2(x0, y0);
+    if (R.s1) *reinterpret_cast<double2*>(plane + R.o1) = make_double2(x1, y1);
   }
 }
 // received halo -> the halo columns of every tracer plane of a scratch field (only before a DSS-on-read consumer)
@@ -822,9 +833,54 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
   const RowStore RS = row_store_setup(GA.S, GA.pperm, slot, j, kc);
   RowGather RG;
   if (GIN) gather_setup(RG, lds_[0], GA, pid);
+  // NBR: per tracer the block loads the bounds of its patch's elements and of the element ring (lane = 16 bytes: entry, min|max,
+  // level pair) into LDS with the tracer's other loads; after the barrier a lane reads its element's and its 8 neighbours' values
+  unsigned bsrc = 0, bdst = 0, bnb[3] = {0, 0, 0};
+  const double* bbase = qmin;
+  if (NBR) {
+    const int t = threadIdx.x, u = min(t >> 2, BND_ENT - 1), w = (t >> 1) & 1, h = t & 1;   // lanes beyond the image repeat its last entry
+    // (the bounds of the patch's own slots are formed in this kernel: the lanes that would load them repeat the first ring entry --
+    // same address, same LDS word, same value)
+    const int ul = u < PS ? PS : u;
+    int el = GA.pering[pid.patch * NER + (ul - PS)];
+    if (el < 0) el = pid.e;   // hole
+    bsrc = (unsigned)((((size_t)el * NCHUNK + kc / CL) * mm_qpad(qsize)) * CL + h * 2);   // + q*CL: entry index in qmin / qmax (< 2^32: the arrays are < 32 GB)
+    bbase = w ? qmax : qmin;
+    bdst = (unsigned)(((ul * 2 + w) * CL + h * 2) * 8);
+    // the 9 entries of a slab (its element, then the 8 neighbours) are shared out over the quad: row j takes entries j, j+4 (and 8)
+    const int sl = pid.live ? pid.tslot - pid.patch * PS : 0, kk = kc & (CL - 1);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const int d = j + 4 * i;   // 0: the element itself; d >= 1: neighbour d-1
+      int n = sl;
+      if (d >= 1 && d < 9) { const int v = GA.pnb[((size_t)pid.patch * PS + sl) * 8 + (d - 1)]; if (v != 255) n = v; }
+      bnb[i] = (unsigned)((n * 2 * CL + kk) * 8);
+    }
+  }
+  GatherRaw graw;
+  double2 lring = make_double2(0., 0.);                  // OWNLAP: the lane's ring load of the first Laplacian
+  double2 braw = make_double2(0., 0.);                   // NBR: the lane's piece of the bounds image                                 // raw own / ring loads of the gathered input(s) (DSS on read)
+  double qnx[4] = {0, 0, 0, 0}, lsx[4] = {0, 0, 0, 0}, minx = 0.0, maxx = 0.0;   // plainly loaded inputs of the next tracer
+  auto fetch = [&](int q) {   // loads only
+    const size_t so = (((size_t)e * qsize + q) * NLEV + kc) * 16 + j * 4, mi = mm_idx(e, q, kc, qsize);
+    if (GIN) gather_issue(RG, GA, Qn0, q, graw);              // GIN == 3: graw <- Qn0 (tracers), graw2 <- lap
+    if (OWNLAP) {   // of the first Laplacian only the patch's halo ring comes from memory (what k_lap1 left of it: the exported lines)
+      asm volatile("" : "+v"(RG.ring));
+      lring = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(lap + (size_t)q * GA.S.tps) + RG.ring);
+    }
+    if (GIN == 0) load4(Qn0 + so, qnx);
+    if (RHS == 2 && GIN != 3) load4(lap + so, lsx);
+    if (NBR) braw = *reinterpret_cast<const double2*>(bbase + ((size_t)bsrc + (size_t)q * CL));
+    else if (LIM) { minx = qmin[mi]; maxx = qmax[mi]; }
+  };
+  // Stage 3: the first tracer's loads go out before the block's constants (the geometry and level fields, the divisions), which do
+  // not depend on them.  The others fetch below: the plain kernels have 4 waves per SIMD to hide the latency, and the stage-2
+  // DSS-on-read kernel would pay for the registers these loads hold through its prologue with its third wave (170 against 168).
+  constexpr bool EARLY = GIN == 3;
+  if (EARLY) fetch(0);
   double vdss[4] = {0, 0, 0, 0};   // the previous stage's extra variable, DSS'd on read (stage 2: divdp_proj, which this stage's dp needs)
   if (GIN && GA.var_out) {
-    gather_var_plane(RG, lds_[0], GA, Qn0, qsize, j, kc, vdss);
+    gather_var_plane(RG, lds_[0], GA, Qn0, qsize, j, vdss);
     if (k < NLEV) store4(GA.var_out + ((size_t)e * GA.var_out_lev + k) * 16 + j * 4, vdss);
   }
   // per-(e,k,row) constants, computed once and reused for every tracer:
@@ -861,7 +917,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
       } else load4(GA.var_in + ((size_t)e * GA.var_in_lev + kc) * 16 + j * 4, vin);
 #pragma unroll
       for (int i = 0; i < 4; i++) w[i] = g.spheremp[i] * vin[i];
-      store_row_pair(Tout + (size_t)qsize * GA.S.tps, RS, kc, k < NLEV, w);
+      store_row_pair(Tout + (size_t)qsize * GA.S.tps, RS, k < NLEV, w);
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -879,30 +935,6 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
     }
     if (RHS == 2) make_lap_geo(L, g);
   }
-  // NBR: per tracer the block loads the bounds of its patch's elements and of the element ring (lane = 16 bytes: entry, min|max,
-  // level pair) into LDS with the tracer's other loads; after the barrier a lane reads its element's and its 8 neighbours' values
-  unsigned bsrc = 0, bdst = 0, bnb[3] = {0, 0, 0};
-  const double* bbase = qmin;
-  if (NBR) {
-    const int t = threadIdx.x, u = min(t >> 2, BND_ENT - 1), w = (t >> 1) & 1, h = t & 1;   // lanes beyond the image repeat its last entry
-    // (the bounds of the patch's own slots are formed in this kernel: the lanes that would load them repeat the first ring entry --
-    // same address, same LDS word, same value)
-    const int ul = u < PS ? PS : u;
-    int el = GA.pering[pid.patch * NER + (ul - PS)];
-    if (el < 0) el = pid.e;   // hole
-    bsrc = (unsigned)((((size_t)el * NCHUNK + kc / CL) * mm_qpad(qsize)) * CL + h * 2);   // + q*CL: entry index in qmin / qmax (< 2^32: the arrays are < 32 GB)
-    bbase = w ? qmax : qmin;
-    bdst = (unsigned)(((ul * 2 + w) * CL + h * 2) * 8);
-    // the 9 entries of a slab (its element, then the 8 neighbours) are shared out over the quad: row j takes entries j, j+4 (and 8)
-    const int sl = pid.live ? pid.tslot - pid.patch * PS : 0, kk = kc & (CL - 1);
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      const int d = j + 4 * i;   // 0: the element itself; d >= 1: neighbour d-1
-      int n = sl;
-      if (d >= 1 && d < 9) { const int v = GA.pnb[((size_t)pid.patch * PS + sl) * 8 + (d - 1)]; if (v != 255) n = v; }
-      bnb[i] = (unsigned)((n * 2 * CL + kk) * 8);
-    }
-  }
   const double sumc = quad_sum(((c[0] + c[1]) + c[2]) + c[3]);
   double visc[4];
 #pragma unroll
@@ -918,42 +950,26 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
   auto put = [&](const Out& o, int q) {
     // pre-DSS output in the scratch layout (chunks of 4 levels, slots, points perimeter first): what the next stage's blocks
     // load as their own points and as their halo ring
-    store_row_pair(Tout + (size_t)q * GA.S.tps, RS, kc, k < NLEV, o.x);
+    store_row_pair(Tout + (size_t)q * GA.S.tps, RS, k < NLEV, o.x);
     // Whole-step path (GIN != 0): nothing reads the bounds after stage 2 or stage 3 -- stage 3 recomputes the element min/max
     // (prim_advection_mod.F90:796-809: qmin = minval(...), not min(qmin, ...)), the next step starts from fresh ones (:765-779) -- so only
     // the plain kernels (stage 1 of the whole-step path, whose relaxed bounds stage 2 reuses, :781-793; every stage of the per-stage
     // API, where qmin/qmax are visible state) write them back
     if (LIM && GIN == 0 && k < NLEV && j == 0 && o.ch) { const size_t m = mm_idx(e, q, k, qsize); qmin[m] = o.mn; qmax[m] = o.mx; }
   };
-  GatherRaw graw;
-  double2 lring = make_double2(0., 0.);                  // OWNLAP: the lane's ring load of the first Laplacian
-  double2 braw = make_double2(0., 0.);                   // NBR: the lane's piece of the bounds image                                 // raw own / ring loads of the gathered input(s) (DSS on read)
-  double qnx[4] = {0, 0, 0, 0}, lsx[4] = {0, 0, 0, 0}, minx = 0.0, maxx = 0.0;   // plainly loaded inputs of the next tracer
-  auto fetch = [&](int q) {   // loads only
-    const size_t so = (((size_t)e * qsize + q) * NLEV + kc) * 16 + j * 4, mi = mm_idx(e, q, kc, qsize);
-    if (GIN) gather_issue(RG, GA, Qn0, q, graw);              // GIN == 3: graw <- Qn0 (tracers), graw2 <- lap
-    if (OWNLAP) {   // of the first Laplacian only the patch's halo ring comes from memory (what k_lap1 left of it: the exported lines)
-      asm volatile("" : "+v"(RG.ring));
-      lring = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(lap + (size_t)q * GA.S.tps) + RG.ring);
-    }
-    if (GIN == 0) load4(Qn0 + so, qnx);
-    if (RHS == 2 && GIN != 3) load4(lap + so, lsx);
-    if (NBR) braw = *reinterpret_cast<const double2*>(bbase + ((size_t)bsrc + (size_t)q * CL));
-    else if (LIM) { minx = qmin[mi]; maxx = qmax[mi]; }
-  };
   if (GIN == 3 && threadIdx.x < 2 * CL) lds_[GIN == 3 ? 1 : 0].v[threadIdx.x / CL][LDS_ZERO][threadIdx.x % CL] = 0.0;
-  fetch(0);
+  if (!EARLY) fetch(0);
   // Memory schedule with DSS on read: wait for this tracer's own/ring loads -> publish them in LDS -> issue the previous
   // tracer's stores and the next tracer's loads -> workgroup barrier -> neighbour values from LDS -> compute.
-  auto step = [&](int q, const Out* prev, int qprev, Out& cur) {
+  auto step = [&](int q, const Out* prev, int qprev, Out& cur, int lb /* LDS buffer */) {
     double qn[4], ls[4] = {0, 0, 0, 0}, own[4], own2[4], minp = minx, maxp = maxx;
-    if (GIN) gather_publish(RG, lds_[0], q & 1, kc, graw, own);
+    if (GIN) gather_publish(RG, lds_[0], lb, graw);
     if (OWNLAP) {
-      *reinterpret_cast<double2*>(reinterpret_cast<char*>(&lds_[GIN == 3 ? 1 : 0].v[q & 1][0][0]) + RG.lwr) = lring;
+      *reinterpret_cast<double2*>(reinterpret_cast<char*>(&lds_[GIN == 3 ? 1 : 0].v[lb][0][0]) + RG.lwr) = lring;
       asm volatile("" : : : "memory");   // (written before the next tracer's load reuses lring)
     }
     if (NBR) {
-      *reinterpret_cast<double2*>(reinterpret_cast<char*>(&bnd_.v[q & 1][0][0][0]) + bdst) = braw;
+      *reinterpret_cast<double2*>(reinterpret_cast<char*>(&bnd_.v[lb][0][0][0]) + bdst) = braw;
       asm volatile("" : : : "memory");   // (written before the next tracer's load reuses braw)
     }
     if (GIN == 0) {
@@ -973,7 +989,8 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
     __builtin_amdgcn_sched_barrier(0);
     if (GIN) {
       lds_barrier();
-      gather_sum(RG, lds_[0], q & 1, j, own, qn);
+      gather_own(RG, lds_[0], lb, own);
+      gather_sum(RG, lds_[0], lb, j, own, qn);
       if (OWNLAP) {
         // What k_lap1 does for a slab (prim_advection_mod.F90:750-761,796-809 + viscosity_mod.F90:378-389), for the patch's own slots:
         // Q = Qdp/dp, element min/max, first weak Laplacian -- published in the second image / the bounds image, whose ring parts came
@@ -984,16 +1001,16 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
         const double emn = quad_min(fmin(fmin(x1[0], x1[1]), fmin(x1[2], x1[3]))), emx = quad_max(fmax(fmax(x1[0], x1[1]), fmax(x1[2], x1[3])));
         laplace_lean_row(D, L, x1, own2);
         const int sl = threadIdx.x >> 4, kk = kc & (CL - 1);
-        char* im = reinterpret_cast<char*>(&lds_[GIN == 3 ? 1 : 0].v[q & 1][0][0]);
+        char* im = reinterpret_cast<char*>(&lds_[GIN == 3 ? 1 : 0].v[lb][0][0]);
 #pragma unroll
         for (int i = 0; i < 4; i++) *reinterpret_cast<double*>(im + (lds_own_entry(sl, j * 4 + i) * CL + kk) * 8) = own2[i];
-        if (LIM && j == 0) { bnd_.v[q & 1][sl][0][kk] = emn; bnd_.v[q & 1][sl][1][kk] = emx; }
+        if (LIM && j == 0) { bnd_.v[lb][sl][0][kk] = emn; bnd_.v[lb][sl][1][kk] = emx; }
         lds_barrier();
-        gather_sum(RG, lds_[GIN == 3 ? 1 : 0], q & 1, j, own2, ls);
+        gather_sum(RG, lds_[GIN == 3 ? 1 : 0], lb, j, own2, ls);
       }
     }
     if (NBR) {   // viscosity_mod.F90:429-432 on the element bounds k_lap1 left in qmin/qmax
-      const char* b = reinterpret_cast<const char*>(&bnd_.v[q & 1][0][0][0]);
+      const char* b = reinterpret_cast<const char*>(&bnd_.v[lb][0][0][0]);
       double mn = *reinterpret_cast<const double*>(b + bnb[0]), mx = *reinterpret_cast<const double*>(b + bnb[0] + CL * 8);
 #pragma unroll
       for (int i = 1; i < 3; i++) {
@@ -1050,7 +1067,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS, 1) void k_adva
   if (DB) {
     TSE_TRACER_PAIRS(step, put, qsize, A, B);
   } else {   // plenty of waves (4 per SIMD): store at the end of the step, 12 registers less (one copy of the body)
-    for (int q = 0; q < qsize; q++) { step(q, nullptr, 0, A); put(A, q); }
+    for (int q = 0; q < qsize; q++) { step(q, nullptr, 0, A, q & 1); put(A, q); }
   }
 }
 
@@ -1079,6 +1096,12 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
     e = sid.e; kc = sid.k; k = sid.live ? sid.k : NLEV; slot = GA.slot_of[e];
   }
   const RowStore RS = row_store_setup(GA.S, GA.pperm, slot, j, kc, GIN ? GA.pexp : nullptr);
+  RowGather RG;
+  GatherRaw graw;
+  if (GIN) {   // the first tracer's loads go out before the block's constants, which do not depend on them
+    gather_setup(RG, lds_, GA, pid);
+    gather_issue(RG, GA, Qn0, 0, graw);
+  }
   LapGeo L;
   {
     RowGeo g;
@@ -1090,16 +1113,10 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
   load4(dp + lo, dpk); load4(divdp_proj + lo, dv);
 #pragma unroll
   for (int i = 0; i < 4; i++) dpk[i] = 1.0 / dp_stage(dpk[i], rdt, dv[i]);   // (the same routine as in k_advance<2,3>: tse_device.h)
-  RowGather RG;
-  GatherRaw graw;
-  if (GIN) {
-    gather_setup(RG, lds_, GA, pid);
-    if (GA.var_out) {   // the previous stage's extra variable (stage 3: eta_dot_dpdn), DSS'd on read
-      double vdss[4];
-      gather_var_plane(RG, lds_, GA, Qn0, qsize, j, kc, vdss);
-      if (k < NLEV) store4(GA.var_out + ((size_t)e * GA.var_out_lev + k) * 16 + j * 4, vdss);
-    }
-    gather_issue(RG, GA, Qn0, 0, graw);
+  if (GIN && GA.var_out) {   // the previous stage's extra variable (stage 3: eta_dot_dpdn), DSS'd on read
+    double vdss[4];
+    gather_var_plane(RG, lds_, GA, Qn0, qsize, j, vdss);
+    if (k < NLEV) store4(GA.var_out + ((size_t)e * GA.var_out_lev + k) * 16 + j * 4, vdss);
   }
   if (!GIN) {
     for (int q = 0; q < qsize; q++) {
@@ -1110,7 +1127,7 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
       double mn = quad_min(fmin(fmin(x[0], x[1]), fmin(x[2], x[3])));
       double mx = quad_max(fmax(fmax(x[0], x[1]), fmax(x[2], x[3])));
       laplace_lean_row(D, L, x, l1);
-      store_row_pair(Bout + (size_t)q * GA.S.tps, RS, kc, k < NLEV, l1);   // scratch layout, as T
+      store_row_pair(Bout + (size_t)q * GA.S.tps, RS, k < NLEV, l1);   // scratch layout, as T
       if (LIM && k < NLEV && j == 0) { qmin[mm_idx(e, q, k, qsize)] = mn; qmax[mm_idx(e, q, k, qsize)] = mx; }
     }
     return;
@@ -1124,19 +1141,20 @@ __global__ __launch_bounds__(GIN ? Patch::THREADS : FLAT_THREADS) void k_lap1(in
   // the whole step and nothing waits for them.
   struct Out { double l[4], mn, mx; };
   auto put = [&](const Out& o, int q) {   // stores of tracer q
-    store_row_pair(Bout + (size_t)q * GA.S.tps, RS, kc, k < NLEV, o.l);
+    store_row_pair(Bout + (size_t)q * GA.S.tps, RS, k < NLEV, o.l);
   };
   if (LIM) stage_init(stg_);   // (ordered before its first use by the first tracer's barrier)
-  auto step = [&](int q, const Out* prev, int qprev, Out& cur) {
+  auto step = [&](int q, const Out* prev, int qprev, Out& cur, int lb /* LDS buffer */) {
     double x[4], own[4];
-    gather_publish(RG, lds_, q & 1, kc, graw, own);
+    gather_publish(RG, lds_, lb, graw);
     __builtin_amdgcn_sched_barrier(0);
     if (prev) put(*prev, qprev);
     gather_issue(RG, GA, Qn0, q + 1 < qsize ? q + 1 : q, graw);   // branch-free: the last step re-reads its own tracer
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();
     if (LIM && (q & 3) == 0 && q) flush_bounds(stg_, (q >> 2) - 1, GA.pslots, pid.patch, kc / CL, qsize, qmin, qmax);   // the element bounds of the 4 tracers before
-    gather_sum(RG, lds_, q & 1, j, own, x);
+    gather_own(RG, lds_, lb, own);
+    gather_sum(RG, lds_, lb, j, own, x);
     lap_q_of(x, dpk, x);
     cur.mn = quad_min(fmin(fmin(x[0], x[1]), fmin(x[2], x[3])));
     cur.mx = quad_max(fmax(fmax(x[0], x[1]), fmax(x[2], x[3])));
@@ -1197,15 +1215,16 @@ __global__ __launch_bounds__(Patch::THREADS) void k_dss_patch(int qsize, const d
   GatherRaw graw;
   gather_setup(RG, lds_, GA, pid);
   double dn[4] = {1, 1, 1, 1}, q0x[4] = {0, 0, 0, 0};
+  auto fetch = [&](int q) {
+    gather_issue(RG, GA, src, q, graw);
+    if (MODE == 1) load4(Qn0 + (((size_t)e * qsize + q) * NLEV + kc) * 16 + j * 4, q0x);
+  };
+  fetch(0);   // before the block's constants and the extra plane, which do not depend on the first tracer's loads
   if (MODE == 1 && mn_out) {   // 1/dp of the next step's stage 1 (the bounds are Qdp * (1/dp) everywhere: k_qminmax)
     load4(dpnext + ((size_t)e * NLEV + kc) * 16 + j * 4, dn);
 #pragma unroll
     for (int i = 0; i < 4; i++) dn[i] = 1.0 / dn[i];
   }
-  auto fetch = [&](int q) {
-    gather_issue(RG, GA, src, q, graw);
-    if (MODE == 1) load4(Qn0 + (((size_t)e * qsize + q) * NLEV + kc) * 16 + j * 4, q0x);
-  };
   struct Out { double x[4], mn, mx; };
   auto put = [&](const Out& o, int q) {
     if (k < NLEV) {
@@ -1216,9 +1235,9 @@ __global__ __launch_bounds__(Patch::THREADS) void k_dss_patch(int qsize, const d
   if (emit) stage_init(stg_);
   // wait for this tracer's loads -> publish in LDS -> issue the PREVIOUS tracer's stores and the NEXT tracer's loads ->
   // workgroup barrier -> neighbour values from LDS -> sum (results alternate between two register sets, see k_lap1)
-  auto step = [&](int q, const Out* prev, int qprev, Out& cur) {
+  auto step = [&](int q, const Out* prev, int qprev, Out& cur, int lb /* LDS buffer */) {
     double own[4], qa[4], x[4];
-    gather_publish(RG, lds_, q & 1, kc, graw, own);
+    gather_publish(RG, lds_, lb, graw);
     if (MODE == 1) {
 #pragma unroll
       for (int i = 0; i < 4; i++) qa[i] = q0x[i];
@@ -1230,7 +1249,8 @@ __global__ __launch_bounds__(Patch::THREADS) void k_dss_patch(int qsize, const d
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();
     if (emit && (q & 3) == 0 && q) flush_bounds(stg_, (q >> 2) - 1, GA.pslots, pid.patch, kc / CL, qsize, mn_out, mx_out);   // the bounds of the 4 tracers before
-    gather_sum(RG, lds_, q & 1, j, own, x);
+    gather_own(RG, lds_, lb, own);
+    gather_sum(RG, lds_, lb, j, own, x);
 #pragma unroll
     for (int i = 0; i < 4; i++) cur.x[i] = MODE == 1 ? (qa[i] + 2 * x[i]) / 3 : x[i];   // (Qdp(n0) + (rkstage-1)*Qdp(np1))/rkstage
     if (emit) {
@@ -1244,10 +1264,9 @@ __global__ __launch_bounds__(Patch::THREADS) void k_dss_patch(int qsize, const d
   };
   if (GA.var_out) {   // the last stage's extra variable (omega_p), DSS'd on read
     double vdss[4];
-    gather_var_plane(RG, lds_, GA, src, qsize, j, kc, vdss);
+    gather_var_plane(RG, lds_, GA, src, qsize, j, vdss);
     if (k < NLEV) store4(GA.var_out + ((size_t)e * GA.var_out_lev + k) * 16 + j * 4, vdss);
   }
-  fetch(0);
   Out A, B;
   TSE_TRACER_PAIRS(step, put, qsize, A, B);
   if (emit) {
