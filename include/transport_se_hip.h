@@ -218,7 +218,7 @@ int tse_element_qdiag(tse_ctx *ctx, int nt, double *mass, double *var, double *q
  * extrema of -- and state%lnps = log(ps_v), from the current ps_v.  The two fields are allocated by the first call (one tracer-sized
  * field and one level); a context that never calls it holds neither.  They stay valid until the state changes: every entry that changes
  * Qdp or ps_v (those that drop the bounds cache, see tse_invalidate_cache, and so tse_prim_run_subcycle, tse_vertical_remap,
- * tse_dcmip_set_initial, tse_copy_qdp_h2d, tse_remap_q_ppm, the tracer steps) makes them stale, and the two copies then return nonzero
+ * tse_dcmip_set_initial, tse_copy_qdp_h2d, tse_view_put of "qdp" or "dp", tse_remap_q_ppm, the tracer steps) makes them stale, and the two copies then return nonzero
  * instead of old data. */
 int tse_state_q(tse_ctx *ctx, int nt);
 /* elem(ie)%state%Q(np,np,nlev,qsize_d) <- device Q: tracers 1..qsize only, no other byte of the host element is written (same 2-D DMA /
@@ -226,6 +226,41 @@ int tse_state_q(tse_ctx *ctx, int nt);
 int tse_copy_q_d2h(tse_ctx *ctx, double *q_elem1, size_t elem_stride, int qsize_d);
 /* elem(ie)%state%lnps(:,:,np1) <- device lnps; lnps_elem1 = address of elem(1)%state%lnps(1,1,np1) */
 int tse_copy_lnps_d2h(tse_ctx *ctx, double *lnps_elem1, size_t elem_stride);
+
+/* ---- state exchange with a GPU-resident host: strided DEVICE views (no byte crosses the host link) ----
+ * A view describes the host's own device array of one field: the device address of its first entry and, in doubles, the stride of each
+ * of the five axes element, q (tracer; the wind component for "vn0"), level, j, i.  An axis the field does not have (q for the level
+ * fields; q and level for "ps_v" / "lnps") carries stride 0.  The library side is always its dense internal array; the copy is a bit copy.
+ *   tse_view_put   host view -> library.  Fields: "qdp" (time level nt, 1|2), "vn0" (q extent 2), "dp", "eta_dot_dpdn" (nlev+1 levels),
+ *                  "omega_p", "divdp", "divdp_proj" -- what tse_copy_qdp_h2d, tse_set_derived and tse_set_divdp write, with the same side
+ *                  effects as those: "qdp" and "dp" drop the cached element bounds and make Q / lnps stale, "dp" and "omega_p" end the
+ *                  prescribed case's static inputs.  A zero stride broadcasts.
+ *   tse_view_get   library -> host view.  Fields: "qdp" (nt), "q" and "lnps" (refused as stale under the rule of tse_copy_q_d2h), and the six
+ *                  of tse_get_derived: "divdp_proj", "eta_dot_dpdn" (levels 1..nlev only: the view has nlev levels), "omega_p", "divdp",
+ *                  "dp3d", "ps_v".  Only the addresses of the view are written (padding keeps its bytes).  No two index tuples of the view may
+ *                  share an address; this is decided by the nested-extent test (the axes sorted by |stride|, each stride at least the previous
+ *                  stride times its extent), which is conservative: it never accepts an overlapping view.  Zero strides are refused.
+ * nt is ignored for fields with one time level.
+ * stream is the caller's hipStream_t (void * keeps this header free of HIP includes).  Not null: the library's compute stream waits for
+ * what the caller's stream holds at the call, the conversion runs on the compute stream, and the caller's stream waits for it -- no host
+ * synchronisation; the source's producer, a caller that reuses the source after a put, and the consumer after a get are all ordered.
+ * Null: the call is complete on return, as the host copies are (the source must be ready: the compute stream orders itself behind the
+ * legacy default stream only).  A stream that is being captured, or one of another device, is refused.
+ * Before anything is enqueued: field and direction, nt, null pointers; v->ptr must be device memory of the context's device
+ * (hipPointerGetAttributes) and the footprint of the view must lie inside the allocation that holds ptr (hipMemGetAddressRange).  On
+ * failure: nonzero, tse_last_error(), nothing enqueued.  Timer group "view".
+ *   tse_view_plan  needs no context and no device: the path put/get take for this view -- 0 point-fastest (stride i = 1, j = 4: 128-byte
+ *                  lines on both sides), 1 level-fastest (stride level = 1, i = S, j = 4S, S >= the level extent: transposed through LDS),
+ *                  2 anything else (one address computation per entry) -- and the footprint [lo, hi) in doubles relative to ptr
+ *                  (v->ptr itself is not read).  Nonzero with a message naming the axis for a view put/get would refuse. */
+typedef struct {
+  void *ptr;            /* DEVICE address of the entry (element 0, q 0, level 0, j 0, i 0) */
+  long long stride[5];  /* in doubles: element, q (tracer, or wind component for "vn0"), level, j, i */
+} tse_view;
+int tse_view_put(tse_ctx *ctx, const char *field, int nt, const tse_view *v, void *stream);
+int tse_view_get(tse_ctx *ctx, const char *field, int nt, const tse_view *v, void *stream);
+int tse_view_plan(const char *field, int nelemd, int qsize, const tse_view *v, int for_get,
+                  int *path, long long *lo, long long *hi);
 
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
@@ -270,7 +305,7 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -1,0 +1,267 @@
+"""The strided device views without a GPU: the C ABI (tse_view, tse_view_put / _get / _plan) in the header, the symbol list, the three
+product libraries and the Fortran seam; tse_view_plan (csrc/tse_views.cpp: path, footprint, overlap test, refusals) against the
+brute-force model tests/view_model.py; the Python view builder on fake device arrays; and the entries without a context."""
+import ctypes as C
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import view_model as vm
+from transport_se_amd import _lib
+from transport_se_amd import hip_mod
+from transport_se_amd.hip_mod import TseError, build_view, view_plan
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED = 20240611
+
+SIGNATURES = {
+    "tse_view_put": "int tse_view_put(tse_ctx *ctx, const char *field, int nt, const tse_view *v, void *stream)",
+    "tse_view_get": "int tse_view_get(tse_ctx *ctx, const char *field, int nt, const tse_view *v, void *stream)",
+    "tse_view_plan": "int tse_view_plan(const char *field, int nelemd, int qsize, const tse_view *v, int for_get, int *path, long long *lo, long long *hi)",
+}
+
+
+def _header():
+    text = open(os.path.join(ROOT, "include", "transport_se_hip.h")).read()
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+# ---- ABI ---------------------------------------------------------------------------------------------------------------------
+def test_header_declares_the_view_type_and_the_three_entries():
+    text = _header()
+    m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*tse_view\s*;", text)
+    assert m, "tse_view"
+    body = " ".join(m.group(1).split())
+    assert re.fullmatch(r"void \*ptr; long long stride\[5\];", body), body
+    decl = {m.group(1): " ".join(m.group(0).split()).rstrip(";").strip()
+            for m in re.finditer(r"\bint\s+(tse_[a-z0-9_]+)\s*\([^)]*\)\s*;", text)}
+    for name, sig in SIGNATURES.items():
+        assert name in decl, name
+        assert decl[name] == sig, decl[name]
+
+
+def test_view_entries_are_listed_bound_and_exported_by_every_product_library():
+    for name in SIGNATURES:
+        assert name in _lib.SYMBOLS, name
+    assert C.sizeof(_lib.View) == 48 and _lib.View.stride.offset == 8
+    for nlev in (None,) + tuple(_lib.NLEV_BUILDS):
+        L = _lib.lib(nlev=nlev)
+        missing = [n for n in SIGNATURES if not hasattr(L, n)]
+        assert not missing, (nlev, missing)
+    assert "tse_views.cpp" in [u[0] for u in _lib.UNITS] and dict(_lib.UNITS)["tse_views.cpp"] == ["-x", "c++"]
+    assert any(p.endswith("tse_views.cpp") for p in _lib.SRC)
+
+
+def test_fortran_seam_binds_the_view_entries():
+    src = open(os.path.join(ROOT, "transport_se_amd", "fortran", "cuda_mod_hip.F90")).read().lower()
+    for c_name in ("tse_view_put", "tse_view_get"):
+        assert "name='%s'" % c_name in src, c_name
+    assert re.search(r"type\s*,\s*bind\(c\)\s*::\s*tse_view\b", src)
+    assert re.search(r"integer\(c_long_long\)\s*::\s*stride\(5\)", src)
+    for name in ("view_put_hip", "view_get_hip"):
+        assert re.search(r"subroutine\s+%s\s*\(\s*field, nt, ptr, strides, stream\s*\)" % name, src), name
+        assert re.search(r"public\s*::[^\n]*\b%s\b" % name, src), name
+        body = src.split("subroutine %s" % name)[1].split("end subroutine")[0]
+        assert "call check(" in body, name   # check() ends in seam_abort on a nonzero return
+
+
+# ---- tse_view_plan against the model -----------------------------------------------------------------------------------------
+def _stride_table(field, ext, has, for_get):
+    """(label, strides, expected path): the layouts a GPU-resident host keeps, and some it should not"""
+    e, q, k, j, i = range(5)
+    present = lambda order: [a for a in order if has[a]]   # noqa: E731
+    K = ext[k]
+    lev = 1 if has[k] else 0   # fields without a level axis: "level-fastest" degenerates to point-fastest
+    rows = []
+    s, _ = vm.nested_strides(ext, present((i, j, k, q, e)))
+    rows.append(("point-fastest dense", s, 0))
+    s, _ = vm.nested_strides(ext, present((i, j, k, q, e)), pads={q: 2 * K * 16 + 48, k: 0 if has[q] else 48, j: 0 if has[k] else 16})
+    rows.append(("point-fastest, qsize_d > qsize and an element gap", s, 0))
+    s, _ = vm.nested_strides(ext, present((k, i, j, q, e)))
+    rows.append(("level-fastest dense", s, 1 if lev else 0))
+    if lev:
+        for S in (K + 3, 80 if K == 73 else K + 8):
+            s, _ = vm.nested_strides(ext, present((k, i, j, q, e)), pads={k: S - K})
+            assert s[i] == S and s[j] == 4 * S
+            rows.append(("level-fastest, rows of %d" % S, s, 1))
+    s, _ = vm.nested_strides(ext, present((j, i, k, q, e)))
+    rows.append(("j and i swapped", s, 2))
+    s, _ = vm.nested_strides(ext, present((e, i, j, k, q)))
+    rows.append(("element-fastest", s, 2 if ext[e] > 1 else 0))
+    s, _ = vm.nested_strides(ext, present((i, j, k, q, e)))
+    s = [-x if a in (e, k) else x for a, x in enumerate(s)]
+    rows.append(("negative element and level strides", s, 0))
+    s, _ = vm.nested_strides(ext, present((i, j, k, q, e)))
+    s = [-x if a in (i, q) else x for a, x in enumerate(s)]
+    rows.append(("negative i and q strides", s, 2))
+    return rows
+
+
+@pytest.mark.parametrize("nlev", [72, 64, 80])
+def test_plan_paths_and_footprints_match_the_model(nlev):
+    seen = set()
+    for nelemd, qsize in itertools.product((1, 3), (1, 3)):
+        for for_get, fields in ((False, vm.PUT_FIELDS), (True, vm.GET_FIELDS)):
+            for field in fields:
+                ext = vm.extents(field, nelemd, qsize, nlev, for_get)
+                has = vm.has_axes(field, for_get)
+                for label, strides, path in _stride_table(field, ext, has, for_get):
+                    off = vm.offsets(field, nelemd, qsize, nlev, strides, for_get)
+                    assert np.unique(off).size == off.size, (field, label)   # every row of the table is a proper (non-overlapping) view
+                    got = view_plan(field, nelemd, qsize, strides, for_get, nlev=nlev)
+                    key = (field, nelemd, qsize, for_get, label, strides)
+                    assert got["path"] == path == vm.expected_path(field, strides, nlev, for_get), key + (got,)
+                    assert (got["lo"], got["hi"]) == (int(off.min()), int(off.max()) + 1), key + (got,)
+                    seen.add((label, path))
+    assert {p for _, p in seen} == {0, 1, 2}
+    assert ("level-fastest, rows of 80", 1) in seen or nlev != 72   # 73 interfaces stored in rows of 80
+
+
+def _is_nested(ext, strides):
+    mv = sorted((abs(s), n) for s, n in zip(strides, ext) if n > 1)
+    return all(s > 0 for s, _ in mv) and all(mv[t][0] >= mv[t - 1][0] * mv[t - 1][1] for t in range(1, len(mv)))
+
+
+def test_get_never_accepts_an_overlapping_view_and_accepts_every_nested_one():
+    rng = np.random.default_rng(SEED)
+    nlev = 72
+    accepted = refused_overlap = refused_disjoint = 0
+    for trial in range(200):
+        field = ("ps_v", "lnps", "omega_p", "qdp", "eta_dot_dpdn")[trial % 5]
+        nelemd, qsize = int(rng.integers(1, 4)), int(rng.integers(1, 3))
+        ext = vm.extents(field, nelemd, qsize, nlev, True)
+        has = vm.has_axes(field, True)
+        if trial % 2:   # near a nested layout: permuted axes, small pads, then one stride perturbed -- overlaps and near misses
+            order = [a for a in rng.permutation(5) if has[a]]
+            strides, _ = vm.nested_strides(ext, order, pads={int(a): int(rng.integers(0, 3)) for a in order})
+            a = int(rng.choice(order))
+            strides[a] = max(1, strides[a] + int(rng.integers(-3, 2)))
+        else:
+            strides = [int(rng.integers(1, 2000)) * int(rng.choice((-1, 1))) if h else 0 for h in has]
+        off = vm.offsets(field, nelemd, qsize, nlev, strides, True)
+        overlaps = np.unique(off).size != off.size
+        try:
+            got = view_plan(field, nelemd, qsize, strides, True)
+        except TseError as ex:
+            assert "overlap" in str(ex), (strides, str(ex))
+            assert not _is_nested(ext, strides), (field, ext, strides)
+            refused_overlap += overlaps; refused_disjoint += not overlaps
+            continue
+        assert not overlaps, (field, nelemd, qsize, strides)
+        assert (got["lo"], got["hi"]) == (int(off.min()), int(off.max()) + 1)
+        accepted += 1
+    assert accepted >= 10 and refused_overlap >= 10, (accepted, refused_overlap, refused_disjoint)
+    for trial in range(200):   # built by nesting, any axis order, pads and signs: always accepted
+        field = ("ps_v", "omega_p", "qdp", "q", "dp3d")[trial % 5]
+        nelemd, qsize = int(rng.integers(1, 4)), int(rng.integers(1, 4))
+        ext = vm.extents(field, nelemd, qsize, nlev, True)
+        has = vm.has_axes(field, True)
+        order = [int(a) for a in rng.permutation(5) if has[a]]
+        strides, _ = vm.nested_strides(ext, order, pads={a: int(rng.integers(0, 9)) for a in order})
+        strides = [s * int(rng.choice((-1, 1))) for s in strides]
+        off = vm.offsets(field, nelemd, qsize, nlev, strides, True)
+        assert np.unique(off).size == off.size
+        got = view_plan(field, nelemd, qsize, strides, True)
+        assert (got["lo"], got["hi"]) == (int(off.min()), int(off.max()) + 1)
+        assert got["path"] == vm.expected_path(field, strides, nlev, True)
+
+
+def test_plan_refusals_name_the_axis():
+    dense = lambda f, g=False: vm.nested_strides(vm.extents(f, 3, 3, 72, g), [a for a in (4, 3, 2, 1, 0) if vm.has_axes(f, g)[a]])[0]   # noqa: E731
+    with pytest.raises(TseError, match="unknown field"):
+        view_plan("temperature", 3, 3, [1152, 0, 16, 4, 1])
+    s = dense("dp"); s[1] = 7
+    with pytest.raises(TseError, match=r"no q axis"):
+        view_plan("dp", 3, 3, s)
+    s = dense("ps_v", True); s[2] = 16
+    with pytest.raises(TseError, match=r"no level axis"):
+        view_plan("ps_v", 3, 3, s, True)
+    for axis, name in enumerate(("element", "q", "level", "j", "i")):
+        s = dense("qdp", True); s[axis] = 0
+        with pytest.raises(TseError, match=r"stride 0 on the %s axis" % name):
+            view_plan("qdp", 3, 3, s, True)
+        got = view_plan("qdp", 3, 3, s, False)   # a put may broadcast
+        off = vm.offsets("qdp", 3, 3, 72, s)
+        assert (got["lo"], got["hi"]) == (int(off.min()), int(off.max()) + 1)
+    for field, for_get, word in (("dp3d", False, "written"), ("q", False, "written"), ("ps_v", False, "written"), ("vn0", True, "read"),
+                                 ("dp", True, "read")):
+        with pytest.raises(TseError, match="cannot be %s through a view" % word):
+            view_plan(field, 3, 3, [0, 0, 0, 4, 1], for_get)
+    with pytest.raises(TseError, match="out of range"):
+        view_plan("omega_p", 3, 3, [1 << 62, 0, 16, 4, 1])
+    L = _lib.lib()
+    assert L.tse_view_plan(b"dp", 3, 3, None, 0, None, None, None) != 0 and b"null" in L.tse_last_error()
+    v = _lib.View(None, (C.c_longlong * 5)(1152, 0, 16, 4, 1))
+    assert L.tse_view_plan(b"dp", 3, 3, C.byref(v), 0, None, None, None) == 0   # the outputs are optional
+
+
+# ---- the Python view builder -------------------------------------------------------------------------------------------------
+class FakeDeviceArray:
+    def __init__(self, shape, strides=None, typestr="<f8", ptr=0x7F0000001000, readonly=False):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(ptr, readonly), strides=strides, version=3)
+
+
+def test_view_builder_reads_the_cuda_array_interface():
+    ne, qs, nlev = 6, 3, 72
+    v = build_view("qdp", FakeDeviceArray((ne, qs, 4, 4, nlev)), "eqjik", ne, qs, nlev)   # C-contiguous, strides = None
+    assert v.ptr == 0x7F0000001000
+    assert list(v.stride) == [qs * 16 * nlev, 16 * nlev, 1, 4 * nlev, nlev]
+    assert view_plan("qdp", ne, qs, v)["path"] == 1
+    # bytes -> doubles, padded rows of 80 for the 73 interfaces, axes in another order
+    a = FakeDeviceArray((ne, 4, 4, 73), strides=(16 * 80 * 8, 4 * 80 * 8, 80 * 8, 8))
+    v = build_view("eta_dot_dpdn", a, "ejik", ne, qs, nlev)
+    assert list(v.stride) == [1280, 0, 1, 320, 80]
+    assert view_plan("eta_dot_dpdn", ne, qs, v) == dict(path=1, lo=0, hi=(ne - 1) * 1280 + 15 * 80 + 73)
+    v = build_view("eta_dot_dpdn", FakeDeviceArray((ne, nlev, 4, 4)), "ekji", ne, qs, nlev, for_get=True)   # get: nlev levels
+    assert list(v.stride) == [nlev * 16, 0, 16, 4, 1]
+    v = build_view("ps_v", FakeDeviceArray((4, 4, ne)), "jie", ne, qs, nlev, for_get=True)
+    assert list(v.stride) == [1, 0, 0, 4 * ne, ne]
+    v = build_view("vn0", FakeDeviceArray((ne, nlev, 2, 4, 4)), "ekqji", ne, qs, nlev)
+    assert list(v.stride) == [nlev * 32, 16, 32, 4, 1]
+    assert build_view("qdp", FakeDeviceArray((ne, qs, 64, 4, 4)), "eqkji", ne, qs, 64).stride[0] == qs * 64 * 16
+
+
+def test_view_builder_refusals():
+    ne, qs, nlev = 6, 3, 72
+    ok = (ne, qs, nlev, 4, 4)
+    cases = [
+        ("<f8 only", dict(array=FakeDeviceArray(ok, typestr="<f4"))),
+        ("not a multiple of 8", dict(array=FakeDeviceArray(ok, strides=(qs * nlev * 128, nlev * 128, 128, 32, 4)))),
+        ("has extent 72, the array has 71", dict(array=FakeDeviceArray((ne, qs, 71, 4, 4)))),
+        ("has extent 3, the array has 5", dict(array=FakeDeviceArray((ne, 5, nlev, 4, 4)))),
+        ("read-only", dict(array=FakeDeviceArray(ok, readonly=True), for_get=True)),
+        ("appears twice", dict(axes="eqkjj")),
+        ("unknown axis letter", dict(axes="eqkjx")),
+        ("has the axes", dict(axes="ekji", array=FakeDeviceArray((ne, nlev, 4, 4)))),
+        ("unknown field", dict(field="temperature")),
+        ("cannot be written", dict(field="dp3d", axes="ekji", array=FakeDeviceArray((ne, nlev, 4, 4)))),
+        ("cannot be read", dict(field="vn0", for_get=True)),
+        ("__cuda_array_interface__", dict(array=np.zeros(ok))),
+    ]
+    for text, kw in cases:
+        args = dict(field="qdp", array=FakeDeviceArray(ok), axes="eqkji", for_get=False)
+        args.update(kw)
+        with pytest.raises(TseError, match=text):
+            build_view(args["field"], args["array"], args["axes"], ne, qs, nlev, args["for_get"])
+    build_view("qdp", FakeDeviceArray(ok, readonly=True), "eqkji", ne, qs, nlev)   # a read-only source is fine
+    assert not re.search(r"^\s*(import|from)\s+torch", open(hip_mod.__file__).read(), re.M)   # hip_mod itself stays free of torch
+
+
+def test_stream_argument_forms():
+    class S:
+        cuda_stream = 0x1234
+    assert hip_mod._stream_handle(None) is None
+    assert hip_mod._stream_handle(0x55).value == 0x55 and hip_mod._stream_handle(S()).value == 0x1234
+
+
+# ---- no device ---------------------------------------------------------------------------------------------------------------
+def test_view_entries_without_a_context_fail_with_a_message():
+    L = _lib.lib()
+    v = _lib.View(None, (C.c_longlong * 5)(1152, 0, 16, 4, 1))
+    for fn, who in ((L.tse_view_put, b"tse_view_put"), (L.tse_view_get, b"tse_view_get")):
+        assert fn(None, b"omega_p", 1, C.byref(v), None) != 0
+        assert who in L.tse_last_error() and b"null context" in L.tse_last_error()
+        assert fn(None, None, 1, None, None) != 0

@@ -10,11 +10,12 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libtransport_se_hip.so")
-SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_tables.cpp", "tse_kernels.h", "tse_device.h", "tse_layout.h",
-                                             "tse_tables.h")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_tables.cpp", "tse_views.cpp", "tse_kernels.h", "tse_device.h",
+                                             "tse_layout.h", "tse_tables.h", "tse_views.h")]
 # the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own;
-# tse_tables.cpp is host C++, which hipcc would otherwise compile as HIP)
-UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_tables.cpp", ["-x", "c++"])]
+# tse_tables.cpp and tse_views.cpp are host C++, which hipcc would otherwise compile as HIP)
+UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_tables.cpp", ["-x", "c++"]),
+         ("tse_views.cpp", ["-x", "c++"])]
 # -fno-honor-nans: value-preserving (no reassociation, no reciprocal tricks); it only lets the compiler drop the
 # v_max_f64 x,x "canonicalize" it otherwise puts in front of every fmin/fmax operand (6 per limiter iteration)
 CFLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-honor-nans", "-fPIC"]
@@ -37,6 +38,11 @@ class InitArgs(C.Structure):
         ("exchange", EXCHANGE_FN), ("exchange_user", C.c_void_p),
         ("vert_remap_q_alg", C.c_int),
     ]
+
+
+class View(C.Structure):
+    """tse_view: a strided device view (strides in doubles: element, q, level, j, i)"""
+    _fields_ = [("ptr", C.c_void_p), ("stride", C.c_longlong * 5)]
 
 
 HOOKS_SO = os.path.join(HERE, "libtransport_se_hip_hooks.so")
@@ -138,7 +144,8 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchr
            "tse_dcmip_step_inputs", "tse_prim_run_subcycle", "tse_device_ptr", "tse_kernel_time", "tse_timing", "tse_comm_timing",
            "tse_halo_layout", "tse_halo_minmax_layout", "tse_comm_unique_id", "tse_comm_init", "tse_comm_precheck", "tse_comm_version", "tse_comm_info", "tse_comm_abort",
            "tse_boundary_layout", "tse_patch_layout", "tse_placement", "tse_invalidate_cache", "tse_divergence_sphere", "tse_laplace_sphere_wk", "tse_remap_q_ppm", "tse_host_register", "tse_element_mass", "tse_element_qdiag",
-           "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h", "tse_norm_setup", "tse_norm_reference", "tse_norm_partials", "tse_mix_partials"]
+           "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h", "tse_norm_setup", "tse_norm_reference", "tse_norm_partials", "tse_mix_partials",
+           "tse_view_put", "tse_view_get", "tse_view_plan"]
 COMM_ID_BYTES = 128
 
 
@@ -219,6 +226,9 @@ def lib(path=None, nlev=None):
     L.tse_norm_reference.argtypes = [vp, i, i, vp]
     L.tse_norm_partials.argtypes = [vp, i, i, d, vp]
     L.tse_mix_partials.argtypes = [vp, i, i, i, d, d, d, d, vp, i, vp]
+    L.tse_view_put.argtypes = [vp, C.c_char_p, i, C.POINTER(View), vp]
+    L.tse_view_get.argtypes = [vp, C.c_char_p, i, C.POINTER(View), vp]
+    L.tse_view_plan.argtypes = [C.c_char_p, i, i, C.POINTER(View), i, C.POINTER(i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     _libs[path] = L
     _check_nlev(L, path, nlev)
     return L

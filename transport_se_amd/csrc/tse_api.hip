@@ -24,6 +24,7 @@
 #include "../../include/transport_se_hip.h"
 #include "tse_kernels.h"
 #include "tse_tables.h"
+#include "tse_views.h"
 
 using namespace tse;
 
@@ -52,6 +53,7 @@ static int fail(const char* fmt, ...) {
   va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
   return 1;
 }
+namespace tse { int set_last_error(const char* msg) { return fail("%s", msg); } }   // (tse_views.cpp: tse_view_plan)
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s:%d %s: %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); } while (0)
 #define NCCLCHK(x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) return fail("%s:%d %s: %s", __FILE__, __LINE__, #x, ncclGetErrorString(r_)); } while (0)
 
@@ -106,6 +108,7 @@ struct tse_ctx {
   int mm_valid = 0;   // time level (1|2) whose element min/max of Q sit in qmin2/qmax2 (emitted by the previous step), 0 = none
   int mm_halo = 0;    // == mm_valid: the neighbour ranks' share of those bounds is already in recvbuf_mm (or on its way: ev_mm)
   hipEvent_t ev_mm = nullptr;   // completion of that prefetched exchange on the communication stream
+  hipEvent_t view_ev[2] = {nullptr, nullptr};   // tse_view_put / tse_view_get: the caller's stream -> compute stream -> the caller's stream (created by the first such call)
   // halo: one slot per neighbour rank (Schedule(1)%SendCycle/RecvCycle), entries per slot for the two exchange kinds
   int ncol_send = 0, ncol_recv = 0, nlyr_halo = 0;
   int nmm_send = 0, nmm_recv = 0;              // entries of the compact min/max exchange
@@ -483,6 +486,7 @@ void tse_finalize(tse_ctx* c) {
   for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->sync_events) if (e) (void)hipEventDestroy(e);
   if (c->ev_mm) (void)hipEventDestroy(c->ev_mm);
+  for (hipEvent_t e : c->view_ev) if (e) (void)hipEventDestroy(e);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
   if (c->int_stream) { (void)hipStreamSynchronize(c->int_stream); (void)hipStreamDestroy(c->int_stream); }
   if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
@@ -1651,6 +1655,102 @@ int tse_prim_run_subcycle(tse_ctx* c, double tstep, int nsub, int* nstep_io) {
   }
   return 0;
 }
+
+// ---- strided device views: state exchange with a GPU-resident host ------------------------------------
+// tse_view_put / tse_view_get (include/transport_se_hip.h).  The descriptor logic -- fields, extents, path, footprint, overlap -- is
+// host code (tse_views.cpp); here: the checks that need the runtime, the stream ordering and the launch of one conversion kernel
+// (tse_kernels.h: k_view_lines, k_view_levels, k_view_generic) on the compute stream.  Nothing is enqueued before every check has passed.
+template <bool PUT>
+static void launch_view(tse_ctx* c, const ViewPlan& p, const tse_view* v, double* lib) {
+  double* view = (double*)v->ptr;
+  const long long* s = v->stride;
+  ViewDims d;
+  for (int a = 0; a < 5; a++) { d.ext[a] = p.ext[a]; d.lib[a] = p.lib[a]; d.vs[a] = s[a]; }
+  const size_t slabs = (size_t)p.ext[0] * p.ext[1] * p.ext[2];
+  const bool base16 = ((uintptr_t)view & 15) == 0;
+  auto blocks = [](size_t items) { return dim3((unsigned)((items + VIEW_THREADS - 1) / VIEW_THREADS)); };
+  if (p.path == 0) {
+    if (base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0) hipLaunchKernelGGL((k_view_lines<PUT, 2>), blocks(slabs * 8), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
+    else hipLaunchKernelGGL((k_view_lines<PUT, 1>), blocks(slabs * 16), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
+  } else if (p.path == 1) {
+    const bool wide = base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
+    const dim3 grid((unsigned)((size_t)p.ext[0] * p.ext[1]));
+#define TSE_VIEW_LEVELS(W, K) hipLaunchKernelGGL((k_view_levels<PUT, W, K>), grid, dim3(VIEW_THREADS), 0, c->stream, p.ext[1], p.lib[0], p.lib[1], p.lib[2], s[0], s[1], s[4], lib, view)
+    if (p.ext[2] == NLEV) { if (wide) TSE_VIEW_LEVELS(true, NLEV); else TSE_VIEW_LEVELS(false, NLEV); }
+    else { if (wide) TSE_VIEW_LEVELS(true, NLEVP); else TSE_VIEW_LEVELS(false, NLEVP); }
+#undef TSE_VIEW_LEVELS
+  } else hipLaunchKernelGGL((k_view_generic<PUT>), blocks(slabs * 16), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
+}
+
+static int view_io(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream, bool get) {
+  const char* who = get ? "tse_view_get" : "tse_view_put";
+  if (!c) return fail("%s: null context", who);
+  ViewPlan p;
+  std::string err;
+  if (view_plan(field, c->nelemd, c->qsize, v, get, &p, &err)) return fail("%s", err.c_str());
+  if (p.field == VF_QDP && (nt < 1 || nt > 2)) return fail("%s: nt=%d", who, nt);
+  if (!v->ptr) return fail("%s: null view pointer", who);
+  if ((uintptr_t)v->ptr & 7) return fail("%s: the view pointer %p is not 8-byte aligned", who, v->ptr);
+  if ((size_t)p.ext[0] * p.ext[1] >= ((size_t)1 << 31)) return fail("%s: %d elements x %d", who, p.ext[0], p.ext[1]);
+  if ((p.field == VF_Q || p.field == VF_LNPS) && !c->qmix_valid)
+    return fail("%s: %s is stale (the state changed since the last tse_state_q, or there was none)", who, field);
+  // the caller's stream first: while it is being captured no other runtime call of this thread is safe
+  hipStream_t us = (hipStream_t)stream;
+  if (us) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(us, &cs) != hipSuccess) { (void)hipGetLastError(); return fail("%s: stream %p is not a stream of this process", who, stream); }
+    if (cs != hipStreamCaptureStatusNone) return fail("%s: stream %p is being captured; views are not recorded into graphs", who, stream);
+    hipDevice_t sd = 0;
+    if (hipStreamGetDevice(us, &sd) != hipSuccess) (void)hipGetLastError();   // (the runtime cannot tell)
+    else if ((int)sd != c->device) return fail("%s: stream %p belongs to device %d, the context to device %d", who, stream, (int)sd, c->device);
+  }
+  // the view's memory: device memory of this device, and every address of the view inside the allocation that holds ptr
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, v->ptr) != hipSuccess) { (void)hipGetLastError(); return fail("%s: %p is not a device address (host memory cannot be viewed)", who, v->ptr); }
+  if (at.type != hipMemoryTypeDevice) return fail("%s: %p is not device memory (host memory cannot be viewed)", who, v->ptr);
+  if (at.device != c->device) return fail("%s: %p lies on device %d, the context on device %d", who, v->ptr, at.device, c->device);
+  hipDeviceptr_t abase = nullptr; size_t asize = 0;
+  if (hipMemGetAddressRange(&abase, &asize, (hipDeviceptr_t)v->ptr) != hipSuccess) { (void)hipGetLastError(); return fail("%s: no allocation holds %p", who, v->ptr); }
+  const __int128 a0 = (__int128)(uintptr_t)abase, a1 = a0 + (__int128)asize, p0 = (__int128)(uintptr_t)v->ptr;
+  if (p0 + (__int128)p.lo * 8 < a0 || p0 + (__int128)p.hi * 8 > a1)
+    return fail("%s: the view reaches doubles [%lld, %lld) around %p, outside its allocation [%p, +%zu bytes)", who, p.lo, p.hi, v->ptr, (void*)abase, asize);
+
+  double* lib = nullptr;
+  switch (p.field) {
+    case VF_QDP: lib = c->q(nt); break;
+    case VF_VN0: lib = c->vn0; break;
+    case VF_DP: lib = c->dp; break;
+    case VF_ETA: lib = c->eta; break;
+    case VF_OMEGA_P: lib = c->omega_p; break;
+    case VF_DIVDP: lib = c->divdp; break;
+    case VF_DIVDP_PROJ: lib = c->divdp_proj; break;
+    case VF_DP3D: lib = c->dp3d; break;
+    case VF_PS_V: lib = c->ps_v; break;
+    case VF_Q: lib = c->qmix; break;
+    case VF_LNPS: lib = c->lnps; break;
+  }
+  if (!lib) return fail("%s: the library holds no field \"%s\"", who, field);
+  if (us && !c->view_ev[0])
+    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+
+  // the side effects of the host entry that writes the same field (tse_copy_qdp_h2d; tse_set_derived)
+  if (!get) {
+    if (p.field == VF_QDP || p.field == VF_DP) set_bounds_cache(c, 0);
+    if (p.field == VF_DP || p.field == VF_OMEGA_P) c->dcmip_static = false;
+  }
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
+  {
+    Scope s(c, "view");
+    if (get) launch_view<false>(c, p, v, lib); else launch_view<true>(c, p, v, lib);
+    LAUNCH_CHECK();
+  }
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
+  else HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int tse_view_put(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream) { return view_io(c, field, nt, v, stream, false); }
+int tse_view_get(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream) { return view_io(c, field, nt, v, stream, true); }
 
 // ---- introspection ------------------------------------------------------------------------------
 void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {

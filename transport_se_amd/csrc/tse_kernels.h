@@ -2308,4 +2308,137 @@ __global__ void k_dcmip_init(int nelemd, int qsize, int test, const double* __re
   if (k == 0) ps_v[(size_t)e * 16 + p] = pint[NLEV];
 }
 
+// ---- strided device views (tse_view_put / tse_view_get): bit copies between a host's own device array and the library's dense one ----
+// ext: extents of (element, q, level, j, i); lib / vs: the strides in doubles of the library's array and of the view (tse_views.h).
+// PUT: view -> library, otherwise library -> view.  The host side has checked that every address of the view lies inside one allocation
+// and, for a destination view, that no two index tuples share an address (tse_views.cpp).
+struct ViewDims { int ext[5]; long long lib[5]; long long vs[5]; };
+constexpr int VIEW_THREADS = 256;
+
+// path 2, any strides: one address computation per entry
+template <bool PUT>
+__global__ __launch_bounds__(VIEW_THREADS) void k_view_generic(ViewDims d, double* __restrict__ lib, double* __restrict__ view) {
+  const size_t t = (size_t)blockIdx.x * VIEW_THREADS + threadIdx.x;
+  if (t >= (size_t)d.ext[0] * d.ext[1] * d.ext[2] * 16) return;
+  const int i = (int)(t & 3), j = (int)((t >> 2) & 3);
+  size_t r = t >> 4;
+  const int k = (int)(r % d.ext[2]); r /= d.ext[2];
+  const int q = (int)(r % d.ext[1]);
+  const long long e = (long long)(r / d.ext[1]);
+  const long long lo = e * d.lib[0] + q * d.lib[1] + k * d.lib[2] + j * 4 + i;
+  const long long vo = e * d.vs[0] + q * d.vs[1] + k * d.vs[2] + j * d.vs[3] + i * d.vs[4];
+  if (PUT) lib[lo] = view[vo]; else view[vo] = lib[lo];
+}
+
+// path 0, point-fastest (stride i = 1, j = 4): every (element, q, level) slab is one 128-byte line on both sides.  W = 2: 16 bytes per lane
+// (view base 16-byte aligned, even element / q / level strides), W = 1: 8 bytes per lane.
+template <bool PUT, int W>
+__global__ __launch_bounds__(VIEW_THREADS) void k_view_lines(ViewDims d, double* __restrict__ lib, double* __restrict__ view) {
+  constexpr int PARTS = 16 / W;
+  const size_t t = (size_t)blockIdx.x * VIEW_THREADS + threadIdx.x;
+  if (t >= (size_t)d.ext[0] * d.ext[1] * d.ext[2] * PARTS) return;
+  const int part = (int)(t % PARTS);
+  size_t r = t / PARTS;
+  const int k = (int)(r % d.ext[2]); r /= d.ext[2];
+  const int q = (int)(r % d.ext[1]);
+  const long long e = (long long)(r / d.ext[1]);
+  double* L = lib + e * d.lib[0] + q * d.lib[1] + k * d.lib[2] + part * W;
+  double* V = view + e * d.vs[0] + q * d.vs[1] + k * d.vs[2] + part * W;
+  if (W == 2) { if (PUT) *(double2*)L = *(const double2*)V; else *(double2*)V = *(const double2*)L; }
+  else { if (PUT) *L = *V; else *V = *L; }
+}
+
+// path 1, level-fastest (stride level = 1, i = S, j = 4S, S >= K): the view holds, per (element, q), 16 rows of K consecutive levels at
+// pitch S; the library holds K lines of its 16 points at pitch lib_k (16; vn0, [k][c][p]: 32 -- a component is a tile of its own).  One
+// block moves one tile: it reads the source with whole-line accesses (along the levels of the view's rows, or the library's 128-byte
+// lines), passes it through an LDS image tile[p][k] and writes whole lines on the other side.
+// The image's row pitch is VIEW_PITCH = NLEV + 2 doubles: even, so that a level pair of the view side is 16-byte aligned in the image and
+// moves as one conflict-free ds_read_b128 / ds_write_b128 per lane, and NOT a multiple of 8.  The library side touches the image 16 bytes
+// of points per lane, the two doubles at (2h) * PITCH + k and (2h + 1) * PITCH + k with h = lane % 8, k = lane / 8 + const (the compiler
+// pairs them into one ds_read2_b64 / ds_write2_b64: 16-lane groups over 32 four-byte banks, i.e. 16 eight-byte ones).  With a pitch of
+// K = 72 all eight h of a group would sit on the same bank (2 * 72 = 0 mod 16): 8-way.  With 2 * PITCH = 4 (mod 8) (NLEV is a multiple of
+// 8) they spread over four banks, the two k of the group over the neighbours: 2-way.  An odd pitch would make that side conflict-free and
+// give the conflict to the view side instead (no 16-byte LDS access; pairs of consecutive doubles at stride 2).  Either way the LDS work of
+// a tile is a few hundred cycles against the ~2000 its 2 x 9 KB take at a CU's share of the HBM rate: the 2-way side is left as it is.
+// WIDE: 16 bytes per lane on the view side too (view base 16-byte aligned, S and the element and q strides even); otherwise the view side
+// moves 8 bytes per lane -- a row of 73 levels at an odd pitch cannot be 16-byte aligned.
+constexpr int VIEW_PITCH = NLEV + 2;
+// An empty statement that uses the loaded value where it stands: without it the compiler sinks each load of a lane next to the (guarded)
+// image store that consumes it and the lane waits for its loads one after the other.
+__device__ __forceinline__ void view_keep(double& x) { asm volatile("" : "+v"(x)); }
+__device__ __forceinline__ void view_keep(double2& x) { asm volatile("" : "+v"(x.x), "+v"(x.y)); }
+static_assert(VIEW_PITCH >= NLEVP && VIEW_PITCH % 4 == 2, "rows of up to NLEVP levels; an even pitch with 2 * pitch = 4 (mod 8)");
+template <bool PUT, bool WIDE, int K>
+__global__ __launch_bounds__(VIEW_THREADS) void k_view_levels(int nq, long long lib_e, long long lib_q, long long lib_k, long long vs_e, long long vs_q,
+                                                              long long S, double* __restrict__ lib, double* __restrict__ view) {
+  __shared__ __attribute__((aligned(16))) double tile[16 * VIEW_PITCH];
+  const int q = (int)(blockIdx.x % (unsigned)nq);
+  const long long e = (long long)(blockIdx.x / (unsigned)nq);
+  double* L = lib + e * lib_e + q * lib_q;
+  double* V = view + e * vs_e + q * vs_q;
+  const int tid = threadIdx.x;
+  constexpr int KP = K / 2;   // whole level pairs of a row; an odd K leaves the last level to 16 lanes
+  // Every lane issues all its global loads before it touches the image, so that a wave has its whole share of the tile in flight at once.
+  constexpr int NV = WIDE ? (16 * KP + VIEW_THREADS - 1) / VIEW_THREADS : (16 * K + VIEW_THREADS - 1) / VIEW_THREADS;
+  constexpr int NL = (8 * K + VIEW_THREADS - 1) / VIEW_THREADS;
+  auto view_side = [&]() {   // PUT: view -> image, else image -> view
+    constexpr bool load = PUT;
+    if (WIDE) {
+      double2 r[NV];
+      double tail = 0;
+      const bool has_tail = (K & 1) && tid < 16;
+      if (load) {
+#pragma unroll
+        for (int u = 0; u < NV; u++) { const int it = min(u * VIEW_THREADS + tid, 16 * KP - 1); r[u] = *(const double2*)(V + (it / KP) * S + 2 * (it % KP)); }   // (a lane past the end reloads the last item)
+        if (has_tail) tail = V[tid * S + K - 1];
+#pragma unroll
+        for (int u = 0; u < NV; u++) view_keep(r[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int it = u * VIEW_THREADS + tid;
+        if (it < 16 * KP) {
+          double2* s = (double2*)(tile + (it / KP) * VIEW_PITCH + 2 * (it % KP));
+          if (load) *s = r[u]; else *(double2*)(V + (it / KP) * S + 2 * (it % KP)) = *s;
+        }
+      }
+      if (has_tail) { if (load) tile[tid * VIEW_PITCH + K - 1] = tail; else V[tid * S + K - 1] = tile[tid * VIEW_PITCH + K - 1]; }
+    } else {
+      double r[NV];
+      if (load) {
+#pragma unroll
+        for (int u = 0; u < NV; u++) { const int it = min(u * VIEW_THREADS + tid, 16 * K - 1); r[u] = V[(it / K) * S + it % K]; }
+#pragma unroll
+        for (int u = 0; u < NV; u++) view_keep(r[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int it = u * VIEW_THREADS + tid;
+        if (it < 16 * K) { if (load) tile[(it / K) * VIEW_PITCH + it % K] = r[u]; else V[(it / K) * S + it % K] = tile[(it / K) * VIEW_PITCH + it % K]; }
+      }
+    }
+  };
+  auto lib_side = [&]() {    // PUT: image -> library, else library -> image
+    constexpr bool load = !PUT;
+    double2 r[NL];
+    if (load) {
+#pragma unroll
+      for (int u = 0; u < NL; u++) { const int it = min(u * VIEW_THREADS + tid, 8 * K - 1); r[u] = *(const double2*)(L + (it >> 3) * lib_k + 2 * (it & 7)); }
+#pragma unroll
+      for (int u = 0; u < NL; u++) view_keep(r[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+      const int it = u * VIEW_THREADS + tid;
+      if (it < 8 * K) {
+        double* s = tile + 2 * (it & 7) * VIEW_PITCH + (it >> 3);
+        if (load) { s[0] = r[u].x; s[VIEW_PITCH] = r[u].y; }
+        else *(double2*)(L + (it >> 3) * lib_k + 2 * (it & 7)) = make_double2(s[0], s[VIEW_PITCH]);
+      }
+    }
+  };
+  if (PUT) { view_side(); __syncthreads(); lib_side(); }
+  else { lib_side(); __syncthreads(); view_side(); }
+}
+
 }  // namespace tse

@@ -1,0 +1,113 @@
+// tse_views.cpp -- descriptor logic of the strided device views (tse_views.h), and tse_view_plan.  Plain host C++17: no HIP header,
+// no device; tests/test_views_cpu.py holds it to a brute-force model (tests/view_model.py).
+#include "tse_views.h"
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+namespace tse {
+
+namespace {
+
+const char* const AXIS[5] = {"element", "q", "level", "j", "i"};
+
+// qkind: 0 no q axis, 1 the tracers, 2 the two wind components.  Level extents of the view per direction (0: no level axis; -1: the
+// field is not served in that direction).  liblev: levels per element of the library's array.
+struct FieldDesc { const char* name; int field; int qkind; int lev_put, lev_get, liblev; };
+const FieldDesc FIELDS[] = {
+    {"qdp", VF_QDP, 1, NLEV, NLEV, NLEV},
+    {"vn0", VF_VN0, 2, NLEV, -1, NLEV},
+    {"dp", VF_DP, 0, NLEV, -1, NLEV},
+    {"eta_dot_dpdn", VF_ETA, 0, NLEVP, NLEV, NLEVP},   // get: levels 1..nlev only, as tse_get_derived
+    {"omega_p", VF_OMEGA_P, 0, NLEV, NLEV, NLEV},
+    {"divdp", VF_DIVDP, 0, NLEV, NLEV, NLEV},
+    {"divdp_proj", VF_DIVDP_PROJ, 0, NLEV, NLEV, NLEV},
+    {"dp3d", VF_DP3D, 0, -1, NLEV, NLEV},
+    {"ps_v", VF_PS_V, 0, -1, 0, 0},
+    {"q", VF_Q, 1, -1, NLEV, NLEV},
+    {"lnps", VF_LNPS, 0, -1, 0, 0},
+};
+
+int refuse(std::string* err, const char* fmt, ...) {
+  char buf[384];
+  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+  if (err) *err = buf;
+  return 1;
+}
+
+}  // namespace
+
+int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool for_get, ViewPlan* out, std::string* err) {
+  const char* who = for_get ? "tse_view_get" : "tse_view_put";
+  if (!field || !v || !out) return refuse(err, "%s: null %s", who, !field ? "field name" : !v ? "view" : "plan");
+  if (nelemd <= 0 || qsize <= 0) return refuse(err, "%s: nelemd = %d, qsize = %d", who, nelemd, qsize);
+  const FieldDesc* f = nullptr;
+  for (const FieldDesc& d : FIELDS) if (!strcmp(d.name, field)) f = &d;
+  if (!f) return refuse(err, "%s: unknown field \"%s\"", who, field);
+  const int lev = for_get ? f->lev_get : f->lev_put;
+  if (lev < 0) return refuse(err, for_get ? "%s: field \"%s\" cannot be read through a view" : "%s: field \"%s\" cannot be written through a view", who, field);
+
+  ViewPlan p;
+  p.field = f->field;
+  const bool has[5] = {true, f->qkind != 0, lev > 0, true, true};
+  p.ext[0] = nelemd; p.ext[1] = f->qkind == 1 ? qsize : f->qkind == 2 ? 2 : 1; p.ext[2] = lev > 0 ? lev : 1; p.ext[3] = NP; p.ext[4] = NP;
+  // the library's dense array: [e][q][k][16], vn0 [e][k][c][16], level fields [e][k][16], ps_v / lnps [e][16]
+  const long long slab = NP * NP;
+  p.lib[4] = 1; p.lib[3] = NP;
+  if (f->qkind == 2) { p.lib[1] = slab; p.lib[2] = 2 * slab; p.lib[0] = 2 * slab * f->liblev; }
+  else {
+    p.lib[2] = has[2] ? slab : 0;
+    p.lib[1] = has[1] ? slab * f->liblev : 0;
+    p.lib[0] = slab * (has[2] ? f->liblev : 1) * (has[1] ? qsize : 1);
+  }
+
+  const long long* s = v->stride;
+  for (int a = 0; a < 5; a++) {
+    if (!has[a] && s[a] != 0) return refuse(err, "%s: field \"%s\" has no %s axis: its stride must be 0 (got %lld)", who, field, AXIS[a], s[a]);
+    if (has[a] && for_get && s[a] == 0) return refuse(err, "%s: stride 0 on the %s axis: a destination view may not broadcast", who, AXIS[a]);
+  }
+
+  // footprint; every product in 128 bits, refused beyond 2^60 doubles
+  const __int128 LIMIT = (__int128)1 << 60;
+  __int128 lo = 0, hi = 0;
+  for (int a = 0; a < 5; a++) {
+    const __int128 span = (__int128)s[a] * (p.ext[a] - 1);
+    if (span > LIMIT || span < -LIMIT) return refuse(err, "%s: the %s stride %lld is out of range", who, AXIS[a], s[a]);
+    if (span < 0) lo += span; else hi += span;
+  }
+  p.lo = (long long)lo; p.hi = (long long)hi + 1;
+
+  if (for_get) {
+    // no two index tuples on one address: the axes that move (extent > 1) sorted by |stride|, each at least the previous one's stride
+    // times its extent.  Sufficient, not necessary: an interleaved but disjoint view is refused too.
+    int idx[5], n = 0;
+    for (int a = 0; a < 5; a++) if (p.ext[a] > 1) idx[n++] = a;
+    auto mag = [&](int a) { return s[a] < 0 ? -(__int128)s[a] : (__int128)s[a]; };
+    std::stable_sort(idx, idx + n, [&](int x, int y) { return mag(x) < mag(y); });
+    for (int i = 1; i < n; i++)
+      if (mag(idx[i]) < mag(idx[i - 1]) * p.ext[idx[i - 1]])
+        return refuse(err, "%s: the view may overlap itself: the %s stride (%lld) is smaller than the %s stride (%lld) times its extent %d", who,
+                      AXIS[idx[i]], s[idx[i]], AXIS[idx[i - 1]], s[idx[i - 1]], p.ext[idx[i - 1]]);
+  }
+
+  const long long S = s[4];
+  if (s[4] == 1 && s[3] == NP) p.path = 0;
+  else if (has[2] && s[2] == 1 && S >= p.ext[2] && s[3] == NP * S) p.path = 1;
+  else p.path = 2;
+  *out = p;
+  return 0;
+}
+
+}  // namespace tse
+
+extern "C" int tse_view_plan(const char* field, int nelemd, int qsize, const tse_view* v, int for_get, int* path, long long* lo, long long* hi) {
+  tse::ViewPlan p;
+  std::string err;
+  if (tse::view_plan(field, nelemd, qsize, v, for_get != 0, &p, &err)) return tse::set_last_error(err.c_str());
+  if (path) *path = p.path;
+  if (lo) *lo = p.lo;
+  if (hi) *hi = p.hi;
+  return 0;
+}

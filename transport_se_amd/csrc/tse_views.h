@@ -1,0 +1,30 @@
+// tse_views.h -- the descriptor logic of the strided device views (tse_view_put / tse_view_get / tse_view_plan): which fields a view may
+// name in which direction, their extents and their dense internal layout, the conversion path a set of strides takes, its footprint and
+// the overlap test of a destination view.  Plain host C++ (tse_views.cpp: no HIP header); tse_api.hip adds the checks that need the
+// device and launches the kernels of tse_kernels.h.
+#pragma once
+#include <string>
+
+#include "../../include/transport_se_hip.h"
+#include "tse_layout.h"
+
+namespace tse {
+
+enum ViewField { VF_QDP, VF_VN0, VF_DP, VF_ETA, VF_OMEGA_P, VF_DIVDP, VF_DIVDP_PROJ, VF_DP3D, VF_PS_V, VF_Q, VF_LNPS };
+
+// axes in the order of tse_view::stride: element, q, level, j, i
+struct ViewPlan {
+  int field = 0;          // ViewField
+  int path = 0;           // 0 point-fastest, 1 level-fastest, 2 generic
+  int ext[5] = {0};       // extent of every axis of the view (1 for an axis the field does not have)
+  long long lib[5] = {0}; // strides (doubles) of the library's dense array: vn0 is [e][k][c][p], eta_dot_dpdn has NLEVP levels per element
+  long long lo = 0, hi = 0;   // footprint [lo, hi) of the view in doubles relative to ptr
+};
+
+// Returns 0, or 1 with the reason in *err (a refused axis is named).
+int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool for_get, ViewPlan* out, std::string* err);
+
+// the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
+int set_last_error(const char* msg);
+
+}  // namespace tse

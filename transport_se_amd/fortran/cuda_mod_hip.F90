@@ -45,6 +45,9 @@ module cuda_mod
   public :: norm_setup_hip, norm_reference_hip, norm_partials_hip
   ! the numerical-mixing and filament diagnostics of two correlated tracers from element partials (INTEGRATION.md section 2d)
   public :: mix_partials_hip
+  ! state exchange with a GPU-resident host (INTEGRATION.md section 2e): fields move between the host's own DEVICE arrays and the library
+  ! on the device, through strided views; nothing crosses the host link
+  public :: tse_view, view_put_hip, view_get_hip
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
   integer(c_int), save :: res_nstep = 0   ! the library's step count after the last prim_run_subcycle_hip
   integer(kind=8), save :: t_c0
@@ -67,6 +70,13 @@ module cuda_mod
      type(c_funptr) :: exchange; type(c_ptr) :: exchange_user
      integer(c_int) :: vert_remap_q_alg
   end type tse_init_args
+
+  ! mirror of tse_view (include/transport_se_hip.h): the DEVICE address of the entry (element 1, q 1, level 1, j 1, i 1) and the strides, in
+  ! doubles, of the axes element, q (tracer; wind component for 'vn0'), level, j, i; 0 for an axis the field does not have
+  type, bind(C) :: tse_view
+     type(c_ptr)          :: ptr
+     integer(c_long_long) :: stride(5)
+  end type tse_view
 
   interface
      integer(c_int) function tse_init(ctx, args) bind(C, name='tse_init')
@@ -156,6 +166,14 @@ module cuda_mod
      end function
      integer(c_int) function tse_mix_partials(ctx, nt, qa, qb, xmin, xmax, c0, c2, tau, ntau, out) bind(C, name='tse_mix_partials')
        import; type(c_ptr), value :: ctx, tau, out; integer(c_int), value :: nt, qa, qb, ntau; real(c_double), value :: xmin, xmax, c0, c2
+     end function
+     integer(c_int) function tse_view_put(ctx, field, nt, v, stream) bind(C, name='tse_view_put')
+       import; type(c_ptr), value :: ctx, stream; character(kind=c_char), intent(in) :: field(*); integer(c_int), value :: nt
+       type(tse_view), intent(in) :: v
+     end function
+     integer(c_int) function tse_view_get(ctx, field, nt, v, stream) bind(C, name='tse_view_get')
+       import; type(c_ptr), value :: ctx, stream; character(kind=c_char), intent(in) :: field(*); integer(c_int), value :: nt
+       type(tse_view), intent(in) :: v
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -715,5 +733,39 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine mix_partials_hip
+
+  ! field (the names of tse_view_put: 'qdp', 'vn0', 'dp', 'eta_dot_dpdn', 'omega_p', 'divdp', 'divdp_proj') <- the host's device array at
+  ! ptr (a DEVICE address: c_loc of an OpenMP-target / OpenACC device pointer, a hipMalloc'ed buffer), strides(1:5) in doubles for the axes
+  ! element, q, level, j, i (0 for an axis the field does not have); nt: time level of 'qdp' (1|2), ignored otherwise.  stream: the host's
+  ! hipStream_t (the copy is ordered behind its work and it behind the copy, nothing waits on the host), or c_null_ptr: complete on return.
+  subroutine view_put_hip(field, nt, ptr, strides, stream)
+    character(len=*),     intent(in) :: field
+    integer,              intent(in) :: nt
+    type(c_ptr),          intent(in) :: ptr, stream
+    integer(c_long_long), intent(in) :: strides(5)
+    type(tse_view) :: v
+    v%ptr = ptr; v%stride = strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_view_put(ctx, trim(field)//c_null_char, int(nt,c_int), v, stream), 'view_put_hip('//trim(field)//')')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine view_put_hip
+
+  ! the host's device array <- field ('qdp', 'q', 'lnps', 'divdp_proj', 'eta_dot_dpdn' (levels 1:nlev), 'omega_p', 'divdp', 'dp3d', 'ps_v');
+  ! only the addresses the view names are written, and the view may not overlap itself
+  subroutine view_get_hip(field, nt, ptr, strides, stream)
+    character(len=*),     intent(in) :: field
+    integer,              intent(in) :: nt
+    type(c_ptr),          intent(in) :: ptr, stream
+    integer(c_long_long), intent(in) :: strides(5)
+    type(tse_view) :: v
+    v%ptr = ptr; v%stride = strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_view_get(ctx, trim(field)//c_null_char, int(nt,c_int), v, stream), 'view_get_hip('//trim(field)//')')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine view_get_hip
 
 end module cuda_mod

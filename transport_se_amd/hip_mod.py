@@ -36,6 +36,85 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+# ---- strided device views (tse_view_put / tse_view_get / tse_view_plan) ----
+VIEW_AXES = "eqkji"   # the axis letters, in the order of tse_view.stride: element, q (tracer / wind component), level, j, i
+# field: (its axes, extent of q, level extent for put, for get) -- "q": qsize, "n": nlev, "p": nlev + 1, None: not served in that direction;
+# the extents csrc/tse_views.cpp holds a view to
+VIEW_FIELDS = {
+    "qdp": ("eqkji", "q", "n", "n"), "vn0": ("eqkji", 2, "n", None), "dp": ("ekji", 1, "n", None),
+    "eta_dot_dpdn": ("ekji", 1, "p", "n"), "omega_p": ("ekji", 1, "n", "n"), "divdp": ("ekji", 1, "n", "n"),
+    "divdp_proj": ("ekji", 1, "n", "n"), "dp3d": ("ekji", 1, None, "n"), "ps_v": ("eji", 1, None, 1), "q": ("eqkji", "q", None, "n"),
+    "lnps": ("eji", 1, None, 1),
+}
+
+
+def build_view(field, array, axes, nelemd, qsize, nlev, for_get=False):
+    """_lib.View of `array` -- anything with __cuda_array_interface__, e.g. a torch tensor on the device -- whose dimensions are named, in
+    order, by the letters of `axes` ("eqjik": a level-fastest tracer array; "ekji": a level field).  Raises TseError for an unknown field
+    or direction, axes that are not exactly the field's, an element type other than <f8, a byte stride that is not a multiple of 8, an
+    extent that is not the field's, and a read-only array as the destination of a get.  The device is not touched."""
+    who = "get" if for_get else "put"
+    if field not in VIEW_FIELDS:
+        raise TseError("%s: unknown field %r" % (who, field))
+    f_axes, qext, lev_put, lev_get = VIEW_FIELDS[field]
+    lev = lev_get if for_get else lev_put
+    if lev is None:
+        raise TseError("%s: field %r cannot be %s through a view" % (who, field, "read" if for_get else "written"))
+    cai = getattr(array, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TseError("%s: the array has no __cuda_array_interface__ (a device array is needed; host arrays go through the copy entries)" % who)
+    axes = str(axes)
+    for a in axes:
+        if a not in VIEW_AXES:
+            raise TseError("%s: unknown axis letter %r in %r (the letters are %s)" % (who, a, axes, " ".join(VIEW_AXES)))
+        if axes.count(a) > 1:
+            raise TseError("%s: axis %r appears twice in %r" % (who, a, axes))
+    if sorted(axes) != sorted(f_axes):
+        raise TseError("%s: field %r has the axes %r, the array is described as %r" % (who, field, f_axes, axes))
+    if cai["typestr"] != "<f8":
+        raise TseError("%s: element type %s, the library moves <f8 only" % (who, cai["typestr"]))
+    shape = tuple(int(x) for x in cai["shape"])
+    if len(shape) != len(axes):
+        raise TseError("%s: %d axes named for an array of %d dimensions" % (who, len(axes), len(shape)))
+    ptr, readonly = cai["data"]
+    if for_get and readonly:
+        raise TseError("get: the destination array is read-only")
+    strides = cai.get("strides")
+    if strides is None:   # C-contiguous
+        strides, acc = [], 8
+        for n in reversed(shape):
+            strides.insert(0, acc); acc *= n
+    want = dict(e=nelemd, q=qsize if qext == "q" else qext, k={"n": nlev, "p": nlev + 1, 1: 1}[lev], j=NP, i=NP)
+    v = _lib.View()
+    v.ptr = int(ptr)
+    for a, n, sb in zip(axes, shape, strides):
+        if n != want[a]:
+            raise TseError("%s: axis %r of field %r has extent %d, the array has %d" % (who, a, field, want[a], n))
+        if int(sb) % 8:
+            raise TseError("%s: the byte stride %d of axis %r is not a multiple of 8" % (who, sb, a))
+        v.stride[VIEW_AXES.index(a)] = int(sb) // 8
+    return v
+
+
+def view_plan(field, nelemd, qsize, strides, for_get=False, nlev=None):
+    """tse_view_plan: dict(path=, lo=, hi=) of a view with `strides` (doubles, in the order of VIEW_AXES) -- the conversion path
+    (0 point-fastest, 1 level-fastest, 2 generic) and its footprint [lo, hi) in doubles relative to the view's pointer.  Needs no device.
+    Raises TseError for a view put / get would refuse."""
+    L = _lib.lib(nlev=nlev)
+    v = strides if isinstance(strides, _lib.View) else _lib.View(None, (C.c_longlong * 5)(*[int(x) for x in strides]))
+    path, lo, hi = C.c_int(), C.c_longlong(), C.c_longlong()
+    if L.tse_view_plan(field.encode(), int(nelemd), int(qsize), C.byref(v), int(bool(for_get)), C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return dict(path=path.value, lo=lo.value, hi=hi.value)
+
+
+def _stream_handle(stream):
+    """None, an integer hipStream_t, or an object with .cuda_stream (a torch stream)"""
+    if stream is None:
+        return None
+    return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -330,6 +409,24 @@ class HipMod:
             err.rc, err.nstep = rc, ns.value
             raise err
         return ns.value
+
+    # ---- state exchange with a GPU-resident host: strided device views (tse_view_put / tse_view_get) ----
+    def put(self, field, array, axes, nt=None, stream=None):
+        """device array -> library field, on the device (build_view names the arguments; nt: the time level of "qdp").  With a stream
+        (an integer handle or an object with .cuda_stream) the copy is ordered behind that stream's work and the stream behind the copy,
+        with no host synchronisation; without one the call is complete on return."""
+        v = build_view(field, array, axes, self.nelemd, self.qsize, self.nlev, False)
+        self._chk(self.L.tse_view_put(self.h, field.encode(), int(nt or 0), C.byref(v), _stream_handle(stream)))
+
+    def get(self, field, out, axes, nt=None, stream=None):
+        """library field -> device array `out`; only the entries the axes address are written"""
+        v = build_view(field, out, axes, self.nelemd, self.qsize, self.nlev, True)
+        self._chk(self.L.tse_view_get(self.h, field.encode(), int(nt or 0), C.byref(v), _stream_handle(stream)))
+
+    def view_plan(self, field, array, axes, for_get=False):
+        """dict(path=, lo=, hi=) that put / get would take for this array (module-level view_plan)"""
+        v = build_view(field, array, axes, self.nelemd, self.qsize, self.nlev, for_get)
+        return view_plan(field, self.nelemd, self.qsize, v, for_get, nlev=self.nlev)
 
     def synchronize(self):
         self._chk(self.L.tse_synchronize(self.h))
