@@ -11,7 +11,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libtransport_se_hip.so")
 SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_tables.cpp", "tse_views.cpp", "tse_kernels.h", "tse_device.h",
-                                             "tse_layout.h", "tse_tables.h", "tse_views.h")]
+                                             "tse_launch.h", "tse_layout.h", "tse_tables.h", "tse_views.h")]
 # the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own;
 # tse_tables.cpp and tse_views.cpp are host C++, which hipcc would otherwise compile as HIP)
 UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_tables.cpp", ["-x", "c++"]),

@@ -22,22 +22,11 @@
 #include <vector>
 
 #include "../../include/transport_se_hip.h"
-#include "tse_kernels.h"
+#include "tse_launch.h"
 #include "tse_tables.h"
 #include "tse_views.h"
 
 using namespace tse;
-
-namespace tse {   // tse_stage3.hip: k_advance<2,3> lives in a translation unit of its own (another scheduler strategy)
-void launch_advance23(unsigned blocks, hipStream_t stream, int nelemd, const Dvv_t& D, const GeoPtrs& G, int qsize, double dt, double nu_q,
-                      const double* B, const double* lapT, double* C, const double* vn0, const double* dp, const double* divdp,
-                      const double* divdp_proj, double* qmin, double* qmax, const double* dp0, const GatherArgs& ga, int limiter_option);
-}
-
-// TSE_DSS_ON_READ=0 falls back to one DSS pass per stage in the whole-step call (the per-stage API always does that)
-static bool dss_on_read() { const char* e = getenv("TSE_DSS_ON_READ"); return !(e && e[0] == '0'); }
-// TSE_REMAP_FUSED=0: inside tse_prim_run_subcycle the last step of a cycle runs its own final DSS pass and the remap works in place
-static bool remap_fused() { const char* e = getenv("TSE_REMAP_FUSED"); return !(e && e[0] == '0'); }
 
 // Experiment and fault-injection switches (TSE_AB_*: A/B variants; TSE_TEST_*: failures on request for the tests) exist only in a build
 // with -DTSE_AB_HOOKS
@@ -171,6 +160,9 @@ struct tse_ctx {
                       nullptr, pset.pering, pset.pnb, pperm, nullptr};
   }
   int mm_m() const { return mm_qpad(qsize) * NLEV; }   // entries per element of the bounds arrays (tse_kernels.h: mm_idx)
+  // where the kernel that leaves Qdp(np1) (final DSS, remap) emits the element bounds of the next step; null: none are emitted, unlimited
+  struct Bounds { double *mn, *mx; };
+  Bounds emitted() const { return lim ? Bounds{qmin2, qmax2} : Bounds{nullptr, nullptr}; }
   size_t lev() const { return (size_t)nelemd * NLEV * 16; }
   size_t trc() const { return lev() * qsize; }
   DcmipTab* dcmip_tab = nullptr;   // level-only factors of the prescribed fields
@@ -184,6 +176,33 @@ int tse_nlev(void) { return NLEV; }
 // the element bounds of Qdp(tl)/dp now sit in qmin2/qmax2 (tl = 0: nothing cached); any halo of older bounds is stale.  Every entry that
 // changes Qdp or ps_v passes here, so the Q / lnps of tse_state_q go stale here too.
 static void set_bounds_cache(tse_ctx* c, int tl) { c->mm_valid = c->lim ? tl : 0; c->mm_halo = 0; c->qmix_valid = false; }
+
+// The route switches of a call.  Read from the environment by every call that asks, never kept in the context: tests flip them between
+// calls on a live context.
+struct Route {
+  // the whole-step call assembles the DSS on read.  false: one DSS pass per stage, as the per-stage API always does -- TSE_DSS_ON_READ=0,
+  // or a scratch plane of plane_limit bytes or more (plane_over): gather offsets are 32-bit bytes within a plane, and
+  // TSE_TEST_PLANE_LIMIT lowers the 4 GiB limit so that tests reach the fallback
+  bool dss_on_read, plane_over;
+  size_t plane_limit;
+  int remap_nt;        // TSE_REMAP_NT: tracers per thread in the remap's lockstep column loop
+  int remap_generic;   // TSE_REMAP_GENERIC=1: the remap always takes the generic loop (tests)
+  // the remap that closes a cycle of tse_prim_run_subcycle assembles the last step's final DSS + time average on read; false
+  // (TSE_REMAP_FUSED=0, no DSS on read, or TSE_REMAP_NT != 1): that step runs its own final DSS pass and the remap works in place
+  bool remap_fused;
+};
+static Route route(const tse_ctx* c) {
+  auto on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
+  auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  Route r;
+  r.plane_limit = hook_env("TSE_TEST_PLANE_LIMIT") ? (size_t)strtoull(hook_env("TSE_TEST_PLANE_LIMIT"), nullptr, 10) : ((size_t)1 << 32);
+  r.plane_over = on("TSE_DSS_ON_READ") && c->tps * 8 >= r.plane_limit;
+  r.dss_on_read = on("TSE_DSS_ON_READ") && !r.plane_over;
+  r.remap_nt = num("TSE_REMAP_NT", 1);
+  r.remap_generic = num("TSE_REMAP_GENERIC", 0);
+  r.remap_fused = on("TSE_REMAP_FUSED") && r.dss_on_read && r.remap_nt == 1;
+  return r;
+}
 
 template <class T>
 static int dalloc(T** p, size_t n) {
@@ -431,12 +450,10 @@ static int init_impl(tse_ctx* c, const tse_init_args* a) {
     for (hipEvent_t& e : c->sync_events) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_mm, hipEventDisableTiming));
   }
-  HIPCHK(hipFuncSetAttribute((const void*)k_remap<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RemapLds)));
-  HIPCHK(hipFuncSetAttribute((const void*)k_remap<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RemapLds)));
-  HIPCHK(hipFuncSetAttribute((const void*)k_remap<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RemapLds)));
-  HIPCHK(hipFuncSetAttribute((const void*)k_remap<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RemapLds)));
-  HIPCHK(hipFuncSetAttribute((const void*)k_remap<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RemapLds)));
-  HIPCHK(hipFuncSetAttribute((const void*)k_remap<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RemapLds)));
+  if (with_every_remap([](auto kern, int) -> int {
+        HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RemapLds)));
+        return 0;
+      })) return 1;
   HIPCHK(hipDeviceSynchronize());
   return 0;
 }
@@ -874,6 +891,18 @@ static int unpack_minmax(tse_ctx* c, hipStream_t st) {
   return 0;
 }
 
+// ---- the two exchanges, pack to unpack, on stream st ----
+// a scratch field's rank-boundary columns: nlyr_halo layers per column in the buffers, of which nlyr are the field's (0: the tracer
+// planes alone) and, where the stage's extra variable travels from its own array, the last NLEV are spheremp*var
+static int exchange_halo(tse_ctx* c, hipStream_t st, double* field, int nlyr_halo, int nlyr = 0, const double* var = nullptr, int var_levels = 0) {
+  return pack_tracers(c, st, field, nlyr_halo, nlyr) || pack_var(c, st, var, var_levels) || halo_exchange(c, nlyr_halo, 0, st) ||
+         unpack_halo(c, st, field, nlyr_halo, nlyr);
+}
+// the element bounds into recvbuf_mm: qmin/qmax, or those in `from` (tse_ctx::emitted)
+static int exchange_bounds(tse_ctx* c, hipStream_t st, tse_ctx::Bounds from = {nullptr, nullptr}) {
+  return pack_minmax(c, st, from.mn, from.mx) || halo_exchange(c, 2 * c->mm_m(), 1, st);
+}
+
 // min/max over the <= 8 neighbours of qmin/qmax (double-buffered on the device); the halo part must have arrived
 static int nbr_minmax_kernel(tse_ctx* c) {
   const int m = c->mm_m();
@@ -890,10 +919,19 @@ static int nbr_minmax_kernel(tse_ctx* c) {
 static int neighbor_minmax(tse_ctx* c) {
   {
     CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
-    if (pack_minmax(c, c->stream)) return 1;
-    if (halo_exchange(c, 2 * c->mm_m(), 1, c->stream)) return 1;
+    if (exchange_bounds(c, c->stream)) return 1;
   }
   return nbr_minmax_kernel(c);
+}
+// the element bounds of Qdp(n0)/dp into qmin/qmax: those the previous step's last kernel (final DSS or remap) left in qmin2/qmax2
+// (cached), else formed here
+static int own_bounds(tse_ctx* c, const double* Qn0, bool cached) {
+  if (cached) { std::swap(c->qmin, c->qmin2); std::swap(c->qmax, c->qmax2); return 0; }
+  Scope s(c, "minmax");
+  hipLaunchKernelGGL(k_qminmax<>, dim3(flat_blocks(c->nelemd)), dim3(FLAT_THREADS), 0, c->stream, c->nelemd, c->qsize, 0.0, Qn0, c->dp, c->divdp_proj,
+                     c->qmin, c->qmax);
+  LAUNCH_CHECK();
+  return 0;
 }
 
 // DSS of the extra level variable of a stage (divdp_proj / eta_dot_dpdn / omega_p): rspheremp*DSS(spheremp*var), remote
@@ -918,8 +956,8 @@ static int dss_tracer_launch(tse_ctx* c, const double* src, double* dst, const d
   const GatherArgs ga = c->gargs(nullptr, c->nelemd, plist, npwork, nullptr, 0, var_out, var_out_lev);
   const dim3 grid(patch_blocks(npwork));
   if (Qn0_avg)
-    hipLaunchKernelGGL(k_dss_patch<1>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, Qn0_avg, (const double*)c->dp,
-                       c->lim ? c->qmin2 : nullptr, c->lim ? c->qmax2 : nullptr, ga);   // (null: no bounds emitted, unlimited)
+    hipLaunchKernelGGL(k_dss_patch<1>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, Qn0_avg, (const double*)c->dp, c->emitted().mn,
+                       c->emitted().mx, ga);
   else
     hipLaunchKernelGGL(k_dss_patch<0>, grid, dim3(Patch::THREADS), 0, c->stream, c->qsize, src, dst, (const double*)nullptr, (const double*)nullptr,
                        (double*)nullptr, (double*)nullptr, ga);
@@ -929,6 +967,13 @@ static int dss_tracer_launch(tse_ctx* c, const double* src, double* dst, const d
 static int dss_tracer_pass(tse_ctx* c, const double* src, double* dst, const double* Qn0_avg, double* var_out = nullptr, int var_out_lev = 0) {
   Scope s(c, "dss");
   return dss_tracer_launch(c, src, dst, Qn0_avg, nullptr, c->pset.npatch, var_out, var_out_lev);
+}
+
+// one launch of a stage's slab kernel on the compute stream (tse_launch.h): the context's share of the arguments, and what the stages
+// and the launches of a split stage differ in
+static StageArgs stage_args(const tse_ctx* c, dim3 grid, dim3 block, double dt, const double* Qn0, const double* lap, double* out, const GatherArgs& ga) {
+  return StageArgs{c->stream, grid, block, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, lap, out, c->vn0, c->dp, c->divdp, c->divdp_proj,
+                   c->qmin, c->qmax, c->dp0, ga, c->lim, c->limiter_option};
 }
 
 // One euler_step of the per-stage API (prim_advection_mod.F90:667-970): every stage ends with a tracer DSS pass, because
@@ -943,75 +988,36 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
   const int nq = c->qsize * NLEV;
   const dim3 grid(flat_blocks(c->nelemd)), blk(FLAT_THREADS);
   const GatherArgs plain = c->gargs(nullptr, c->nelemd, nullptr, 0);
-  if (rhs == 0 && !c->lim) {
-    Scope s(c, "advance0");
-    hipLaunchKernelGGL((k_advance<0, 0, false, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
-                       c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr, c->dp0, plain);
-    LAUNCH_CHECK();
-  } else if (rhs == 1 && !c->lim) {
-    Scope s(c, "advance1");
-    hipLaunchKernelGGL((k_advance<1, 0, false, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
-                       c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr, c->dp0, plain);
-    LAUNCH_CHECK();
-  } else if (rhs == 0) {
-    if (fused_mm && c->mm_valid == n0_qdp) {
-      // the previous step's last kernel (final DSS or remap) already left the element min/max of Qdp(n0)/dp in qmin2/qmax2
-      std::swap(c->qmin, c->qmin2); std::swap(c->qmax, c->qmax2);
-    } else {
-      Scope s(c, "minmax");
-      hipLaunchKernelGGL(k_qminmax<>, grid, blk, 0, c->stream, c->nelemd, c->qsize, 0.0, Qn0, c->dp, c->divdp_proj, c->qmin, c->qmax);
-      LAUNCH_CHECK();
+  if (rhs == 0) {
+    if (c->lim) {
+      if (own_bounds(c, Qn0, fused_mm && c->mm_valid == n0_qdp)) return 1;
+      set_bounds_cache(c, 0);
+      if (neighbor_minmax(c)) return 1;
     }
-    set_bounds_cache(c, 0);
-    if (neighbor_minmax(c)) return 1;
     Scope s(c, "advance0");
-    if (c->limiter_option == 9)
-      hipLaunchKernelGGL((k_advance<0, 0, false, true, 9>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
-                         c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
-    else
-      hipLaunchKernelGGL(k_advance<0>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr, c->T, c->vn0,
-                         c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    launch_advance<0, 0, false>(stage_args(c, grid, blk, dt, Qn0, nullptr, c->T, plain));
     LAUNCH_CHECK();
   } else if (rhs == 1) {
     Scope s(c, "advance1");
-    if (c->limiter_option == 9)
-      hipLaunchKernelGGL((k_advance<1, 0, false, true, 9>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr,
-                         c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
-    else
-      hipLaunchKernelGGL(k_advance<1>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, (const double*)nullptr, c->T, c->vn0,
-                         c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
+    launch_advance<1, 0, false>(stage_args(c, grid, blk, dt, Qn0, nullptr, c->T, plain));
     LAUNCH_CHECK();
   } else {
     c->t_zero_dirty = true;   // below, T receives rspheremp*DSS(lap) in the plain tracer layout
     {
       Scope s(c, "lap");
-      if (c->lim)
-        hipLaunchKernelGGL(k_lap1<0>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dt, Qn0, c->B, c->dp, c->divdp_proj, c->qmin, c->qmax, plain);
-      else
-        hipLaunchKernelGGL((k_lap1<0, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dt, Qn0, c->B, c->dp, c->divdp_proj,
-                           (double*)nullptr, (double*)nullptr, plain);
+      launch_lap1<0>(stage_args(c, grid, blk, 2 * dt, Qn0, nullptr, c->B, plain));
       LAUNCH_CHECK();
     }
     // biharmonic_wk_scalar_minmax: DSS(lap1) (+ min/max exchange) -> T = rspheremp*DSS(lap1).  The reference's message is
     // (lap, Qmin, Qmax) = 3*qsize*nlev layers (viscosity_mod.F90:389-391); here the Laplacian and the bounds travel separately.
     {
       CommScope w(c, "comm_wait", c->stream);
-      if (pack_tracers(c, c->stream, c->B, nq)) return 1;
-      if (halo_exchange(c, nq, 0, c->stream)) return 1;
-      if (unpack_halo(c, c->stream, c->B, nq)) return 1;
+      if (exchange_halo(c, c->stream, c->B, nq)) return 1;
     }
     if (dss_tracer_pass(c, c->B, c->T, nullptr)) return 1;
     if (c->lim && neighbor_minmax(c)) return 1;
     Scope s(c, "advance2");
-    if (c->limiter_option == 9)
-      hipLaunchKernelGGL((k_advance<2, 0, false, true, 9>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0, c->dp,
-                         c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
-    else if (c->lim)
-      hipLaunchKernelGGL(k_advance<2>, grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0, c->dp, c->divdp,
-                         c->divdp_proj, c->qmin, c->qmax, c->dp0, plain);
-    else
-      hipLaunchKernelGGL((k_advance<2, 0, false, false>), grid, blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dt, c->nu_q, Qn0, c->T, c->B, c->vn0,
-                         c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr, c->dp0, plain);
+    launch_advance<2, 0, false>(stage_args(c, grid, blk, dt, Qn0, c->T, c->B, plain));
     LAUNCH_CHECK();
   }
   double* pre = rhs == 2 ? c->B : c->T;
@@ -1019,10 +1025,7 @@ static int euler_step_impl(tse_ctx* c, int np1_qdp, int n0_qdp, double dt, int D
   // edgeVpack(Qdp) + edgeVpack(spheremp*DSSvar) -> bndry_exchangeV -> edgeVunpack + rspheremp  (:911-960)
   {
     CommScope w(c, "comm_wait", c->stream);
-    if (pack_tracers(c, c->stream, pre, nq + NLEV)) return 1;
-    if (var && pack_var(c, c->stream, *var, var_levels)) return 1;
-    if (halo_exchange(c, nq + NLEV, 0, c->stream)) return 1;
-    if (unpack_halo(c, c->stream, pre, nq + NLEV)) return 1;
+    if (exchange_halo(c, c->stream, pre, nq + NLEV, 0, var ? *var : nullptr, var_levels)) return 1;
   }
   if (dss_tracer_pass(c, pre, Qnp1, avg)) return 1;
   return dss_level_var(c, var, var_levels);
@@ -1106,8 +1109,24 @@ static int split_stage(tse_ctx* c, const char* timer, Launch launch /* (Work) */
   return 0;
 }
 
+// The launch that leaves Qdp(np1) and emits its element bounds for the next step (final DSS, remap), under the timer `timer`.
 // prefetch: the caller knows that the next thing to happen to Qdp(np1) is the next tracer step (no remap in between), so the
-// bounds exchange that step would start with is started here, under the interior part of the last kernel
+// bounds exchange that step would start with is started here, under the interior part of this launch
+template <class Launch>
+static int launch_emitting_bounds(tse_ctx* c, const char* timer, int np1_qdp, bool prefetch, Launch launch /* (Work) */) {
+  if (prefetch && c->halo() && c->lim) {
+    hipEvent_t done = nullptr;
+    if (split_stage(c, timer, launch, [&]() -> int { return exchange_bounds(c, c->comm_stream, c->emitted()); }, &done)) return 1;
+    set_bounds_cache(c, np1_qdp);
+    c->mm_halo = np1_qdp;
+  } else {
+    Scope s(c, timer);
+    if (launch(work_of(c, 0))) return 1;
+    set_bounds_cache(c, np1_qdp);
+  }
+  return 0;
+}
+
 // the step's inputs (vn0, eta_dot_dpdn; dp, omega_p on the first step) are being written on the auxiliary stream: wait for them
 static int join_inputs(tse_ctx* c) {
   if (!c->inputs_pending) return 0;
@@ -1121,7 +1140,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   double* Qn0 = c->q(n0_qdp);
   double* Qnp1 = c->q(np1_qdp);
   const int nq = c->qsize * NLEV;
-  const dim3 blk(FLAT_THREADS);
+  const dim3 blk(FLAT_THREADS), pblk(Patch::THREADS);
   hipStream_t cs = c->comm_stream;
   // the stage's extra DSS variable travels as plane qsize of the stage's scratch output and is assembled on read by the next
   // kernel (var_in / var_out of GatherArgs): divdp_proj with stage 1, eta_dot_dpdn with stage 2, omega_p with stage 3
@@ -1135,14 +1154,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
   if (c->lim) {
     const bool halo_ready = c->halo() && c->mm_valid == n0_qdp && c->mm_halo == n0_qdp;   // prefetched by the previous step / remap
     if (c->mm_valid != n0_qdp && join_inputs(c)) return 1;   // k_qminmax reads dp
-    if (c->mm_valid == n0_qdp) {
-      // the previous step's last kernel (final DSS or remap) already left the element min/max of Qdp(n0)/dp in qmin2/qmax2
-      std::swap(c->qmin, c->qmin2); std::swap(c->qmax, c->qmax2);
-    } else {
-      Scope s(c, "minmax");
-      hipLaunchKernelGGL(k_qminmax<>, dim3(flat_blocks(c->nelemd)), blk, 0, c->stream, c->nelemd, c->qsize, 0.0, Qn0, c->dp, c->divdp_proj, c->qmin, c->qmax);
-      LAUNCH_CHECK();
-    }
+    if (own_bounds(c, Qn0, c->mm_valid == n0_qdp)) return 1;
     if (halo_ready) {
       CommScope w(c, "comm_wait", c->stream);
       HIPCHK(hipStreamWaitEvent(c->stream, c->ev_mm, 0));
@@ -1150,7 +1162,7 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
       hipEvent_t ev0 = next_sync_event(c), evM = next_sync_event(c);
       HIPCHK(hipEventRecord(ev0, c->stream));
       HIPCHK(hipStreamWaitEvent(cs, ev0, 0));
-      if (pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs)) return 1;
+      if (exchange_bounds(c, cs)) return 1;
       HIPCHK(hipEventRecord(evM, cs));
       CommScope w(c, "comm_wait", c->stream);
       HIPCHK(hipStreamWaitEvent(c->stream, evM, 0));
@@ -1165,37 +1177,17 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
           if (!w.nwork) return 0;
           GatherArgs ga = gargs(w, c->divdp_proj, NLEV);
           ga.divdp_out = c->divdp;
-          if (c->limiter_option == 9)
-            hipLaunchKernelGGL((k_advance<0, 0, false, true, 9>), dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q,
-                               (const double*)Qn0, (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, ga);
-          else if (c->lim)
-            hipLaunchKernelGGL(k_advance<0>, dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, (const double*)Qn0,
-                               (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, ga);
-          else
-            hipLaunchKernelGGL((k_advance<0, 0, false, false>), dim3(flat_blocks(w.nwork)), blk, 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q,
-                               (const double*)Qn0, (const double*)nullptr, c->T, c->vn0, c->dp, c->divdp, c->divdp_proj, (double*)nullptr, (double*)nullptr,
-                               c->dp0, ga);
+          launch_advance<0, 0, false>(stage_args(c, dim3(flat_blocks(w.nwork)), blk, dts, Qn0, nullptr, c->T, ga));
           LAUNCH_CHECK(); return 0; },
-        [&]() -> int { return pack_tracers(c, cs, c->T, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->T, nqv, nqv); })) return 1;
+        [&]() -> int { return exchange_halo(c, cs, c->T, nqv, nqv); })) return 1;
 
   // ---- stage 2 (rhs_multiplier 1, DSS extra = eta_dot_dpdn): T (+) edges -> B
   if (split_stage(c, "advance1",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
-          if (c->limiter_option == 9)
-            hipLaunchKernelGGL((k_advance<1, 1, true, true, 9>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(),
-                               c->qsize, dts, c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin,
-                               c->qmax, c->dp0, gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
-          else if (c->lim)
-            hipLaunchKernelGGL((k_advance<1, 1, true>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts,
-                               c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0,
-                               gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
-          else
-            hipLaunchKernelGGL((k_advance<1, 1, true, false>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(),
-                               c->qsize, dts, c->nu_q, (const double*)c->T, (const double*)nullptr, c->B, c->vn0, c->dp, c->divdp, c->divdp_proj,
-                               (double*)nullptr, (double*)nullptr, c->dp0, gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV));
+          launch_advance<1, 1, true>(stage_args(c, dim3(patch_blocks(w.npwork)), pblk, dts, c->T, nullptr, c->B, gargs(w, c->eta, NLEVP, c->divdp_proj, NLEV)));
           LAUNCH_CHECK(); return 0; },
-        [&]() -> int { return pack_tracers(c, cs, c->B, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->B, nqv, nqv); })) return 1;
+        [&]() -> int { return exchange_halo(c, cs, c->B, nqv, nqv); })) return 1;
 
   // ---- stage 3 (rhs_multiplier 2, DSS extra = omega_p)
   // 3a: B (+) edges -> first Laplacian (pre-DSS) of the stage-2 tracers in T, element min/max (the DSS'd tracers themselves are
@@ -1205,61 +1197,40 @@ static int advec_dss_on_read(tse_ctx* c, double dts /* stage dt = dt/2 */, int n
           if (!w.npwork) return 0;
           GatherArgs ga = gargs(w, nullptr, 0, c->eta, NLEVP);
           ga.pexp = c->pexp;   // only what other patches and ranks read of the first Laplacian is stored: stage 3b forms its own slots' itself
-          if (c->lim)
-            hipLaunchKernelGGL(k_lap1<1>, dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dts,
-                               (const double*)c->B, c->T, c->dp, c->divdp_proj, c->qmin, c->qmax, ga);
-          else
-            hipLaunchKernelGGL((k_lap1<1, false>), dim3(patch_blocks(w.npwork)), dim3(Patch::THREADS), 0, c->stream, c->nelemd, c->D, c->geo(), c->qsize, 2 * dts,
-                               (const double*)c->B, c->T, c->dp, c->divdp_proj, (double*)nullptr, (double*)nullptr, ga);
+          launch_lap1<1>(stage_args(c, dim3(patch_blocks(w.npwork)), pblk, 2 * dts, c->B, nullptr, c->T, ga));
           LAUNCH_CHECK(); return 0; },
-        [&]() -> int { return (c->lim && (pack_minmax(c, cs) || halo_exchange(c, 2 * c->mm_m(), 1, cs) || unpack_minmax(c, cs))) ||
-                              pack_tracers(c, cs, c->T, nq) || halo_exchange(c, nq, 0, cs) || unpack_halo(c, cs, c->T, nq); })) return 1;
+        [&]() -> int { return (c->lim && (exchange_bounds(c, cs) || unpack_minmax(c, cs))) || exchange_halo(c, cs, c->T, nq); })) return 1;
   // (no neighbour min/max pass here: 3b forms it from the element bounds -- its patch's and the element ring's -- while it runs)
   // 3b: B (+) edges, T (+) edges -> C (2nd Laplacian + biharmonic scaling + advance + limiter)
   if (split_stage(c, "advance2",
         [&](Work w) -> int {
           if (!w.npwork) return 0;
-          launch_advance23(patch_blocks(w.npwork), c->stream, c->nelemd, c->D, c->geo(), c->qsize, dts, c->nu_q, c->B, c->T, c->C, c->vn0, c->dp,
-                           c->divdp, c->divdp_proj, c->qmin, c->qmax, c->dp0, gargs(w, c->omega_p, NLEV), c->limiter_option);   // (tse_stage3.hip)
+          launch_advance23(stage_args(c, dim3(patch_blocks(w.npwork)), pblk, dts, c->B, c->T, c->C, gargs(w, c->omega_p, NLEV)));   // (tse_stage3.hip)
           LAUNCH_CHECK(); return 0; },
-        [&]() -> int { return pack_tracers(c, cs, c->C, nqv, nqv) || halo_exchange(c, nqv, 0, cs) || unpack_halo(c, cs, c->C, nqv, nqv); })) return 1;
+        [&]() -> int { return exchange_halo(c, cs, c->C, nqv, nqv); })) return 1;
   if (defer_dss) {   // C (halo columns filled: the stage's exchange is ordered before the next launch on the compute stream) waits for the remap
     c->dss_deferred_n0 = n0_qdp;
     set_bounds_cache(c, 0);
     return 0;
   }
   // final DSS fused with qdp_time_avg (:645-662) and with the next step's element min/max
-  if (prefetch && c->halo() && c->lim) {
-    hipEvent_t done = nullptr;
-    if (split_stage(c, "dss",
-          [&](Work w) -> int { return dss_tracer_launch(c, c->C, Qnp1, Qn0, w.plist, w.npwork, c->omega_p, NLEV); },
-          [&]() -> int { return pack_minmax(c, cs, c->qmin2, c->qmax2) || halo_exchange(c, 2 * c->mm_m(), 1, cs); }, &done)) return 1;
-    set_bounds_cache(c, np1_qdp);
-    c->mm_halo = np1_qdp;
-  } else {
-    if (dss_tracer_pass(c, c->C, Qnp1, Qn0, c->omega_p, NLEV)) return 1;
-    set_bounds_cache(c, np1_qdp);
-  }
-  return 0;
+  return launch_emitting_bounds(c, "dss", np1_qdp, prefetch,
+                                [&](Work w) -> int { return dss_tracer_launch(c, c->C, Qnp1, Qn0, w.plist, w.npwork, c->omega_p, NLEV); });
 }
 
 static int advec_step(tse_ctx* c, double dt, int n0_qdp, int np1_qdp, bool prefetch, bool defer_dss = false) {
   if (n0_qdp == np1_qdp || n0_qdp < 1 || n0_qdp > 2 || np1_qdp < 1 || np1_qdp > 2)
     return fail("advec_tracers_remap_rk2: time levels n0_qdp=%d np1_qdp=%d", n0_qdp, np1_qdp);
-  bool gor = dss_on_read();
-  if (!gor && join_inputs(c)) return 1;
-  // gather offsets are 32-bit bytes within a plane; TSE_TEST_PLANE_LIMIT lowers the 4 GiB limit so that tests reach the fallback
-  const size_t plane_limit = hook_env("TSE_TEST_PLANE_LIMIT") ? (size_t)strtoull(hook_env("TSE_TEST_PLANE_LIMIT"), nullptr, 10) : ((size_t)1 << 32);
-  if (gor && c->tps * 8 >= plane_limit) {
+  const Route rt = route(c);
+  if (rt.plane_over) {
     static bool said = false;
     if (!said) {
-      fprintf(stderr, "transport_se_hip: a scratch plane is %zu bytes (>= %zu): DSS on read disabled, one DSS pass per stage\n", c->tps * 8, plane_limit);
+      fprintf(stderr, "transport_se_hip: a scratch plane is %zu bytes (>= %zu): DSS on read disabled, one DSS pass per stage\n", c->tps * 8, rt.plane_limit);
       said = true;
     }
-    gor = false;
-    if (join_inputs(c)) return 1;
   }
-  if (gor) {
+  if (!rt.dss_on_read && join_inputs(c)) return 1;
+  if (rt.dss_on_read) {
     if (c->t_zero_dirty) {   // restore the all-zero slots of T
       const int tot = c->qsize * NCHUNK * 16 * CL;
       hipLaunchKernelGGL(k_zero_slot<>, dim3((tot + 255) / 256), dim3(256), 0, c->stream, c->qsize, c->T, c->scr(), c->zero0());
@@ -1279,12 +1250,11 @@ static int advec_step(tse_ctx* c, double dt, int n0_qdp, int np1_qdp, bool prefe
 
 int tse_advec_tracers_remap_rk2(tse_ctx* c, double dt, int n0_qdp, int np1_qdp) { return advec_step(c, dt, n0_qdp, np1_qdp, false); }
 
-// prefetch: as in advec_dss_on_read -- the next tracer step's bounds exchange starts under the interior elements of the remap
+// prefetch: as in launch_emitting_bounds -- the next tracer step's bounds exchange starts under the interior elements of the remap
 static int remap_launch(tse_ctx* c, double dt, int np1_qdp, bool prefetch) {
   if (np1_qdp < 1 || np1_qdp > 2) return fail("vertical_remap: np1_qdp=%d", np1_qdp);
-  // TSE_REMAP_NT: tracers per thread in the lockstep column loop; TSE_REMAP_GENERIC=1: always take the generic loop (tests)
-  const int nt = getenv("TSE_REMAP_NT") ? atoi(getenv("TSE_REMAP_NT")) : 1;
-  const int generic = getenv("TSE_REMAP_GENERIC") ? atoi(getenv("TSE_REMAP_GENERIC")) : 0;
+  const Route rt = route(c);
+  const int nt = rt.remap_nt;
   double* Qr = c->q(np1_qdp);
   // the tracer step before left its final DSS + time average to this launch (advec_dss_on_read, defer_dss): Qr is written only
   const int fused_n0 = c->dss_deferred_n0;
@@ -1295,35 +1265,19 @@ static int remap_launch(tse_ctx* c, double dt, int np1_qdp, bool prefetch) {
   auto launch = [&](Work w) -> int {   // block = element
     if (!w.nwork) return 0;
     const int* list = w.order == c->ord_bnd ? c->rl_bnd : w.order == c->ord_int ? c->rl_int : c->rl_all;   // the same elements, in slot order
-    auto go = [&](auto kern, int threads) {
+    return with_remap(nt, c->remap_alg2, fused_n0 != 0, [&](auto kern, int threads) -> int {
       hipLaunchKernelGGL(kern, dim3(8 * ((w.nwork + 7) / 8)), dim3(threads), sizeof(RemapLds), c->stream, c->qsize, dt, c->ps0, c->hyai, c->hybi,
-                         c->dp, c->divdp_proj, c->dp3d, c->ps_v, Qr, c->bad, c->lim ? c->qmin2 : nullptr, c->lim ? c->qmax2 : nullptr, generic, c->sink,
-                         (const double*)nullptr, list, w.nwork, c->lvl_tmp, F);   // (null bounds: none emitted, unlimited)
-    };
-    if (fused_n0) { if (c->remap_alg2) go(k_remap<1, true, true>, REMAP_THREADS); else go(k_remap<1, false, true>, REMAP_THREADS); }
-    else if (nt == 1) { if (c->remap_alg2) go(k_remap<1, true>, REMAP_THREADS); else go(k_remap<1, false>, REMAP_THREADS); }
-    else { if (c->remap_alg2) go(k_remap<2, true>, REMAP_THREADS / 2); else go(k_remap<2, false>, REMAP_THREADS / 2); }
-    LAUNCH_CHECK();
-    return 0;
+                         c->dp, c->divdp_proj, c->dp3d, c->ps_v, Qr, c->bad, c->emitted().mn, c->emitted().mx, rt.remap_generic, c->sink,
+                         (const double*)nullptr, list, w.nwork, c->lvl_tmp, F);
+      LAUNCH_CHECK();
+      return 0;
+    });
   };
   if (hook_env("TSE_TEST_FAIL_REMAP")) {   // tests: this process's remap reports a negative layer thickness (one rank of several failing alone)
     static const int one = 1;
     HIPCHK(hipMemcpyAsync(c->bad, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
   }
-  if (prefetch && c->halo() && c->lim) {
-    const int nq = c->qsize * NLEV;
-    hipStream_t cs = c->comm_stream;
-    hipEvent_t done = nullptr;
-    if (split_stage(c, "remap", launch, [&]() -> int { return pack_minmax(c, cs, c->qmin2, c->qmax2) || halo_exchange(c, 2 * c->mm_m(), 1, cs); }, &done))
-      return 1;
-    set_bounds_cache(c, np1_qdp);   // k_remap emitted the element min/max of the remapped field
-    c->mm_halo = np1_qdp;
-  } else {
-    Scope s(c, "remap");
-    if (launch(work_of(c, 0))) return 1;
-    set_bounds_cache(c, np1_qdp);
-  }
-  return 0;
+  return launch_emitting_bounds(c, "remap", np1_qdp, prefetch, launch);   // (k_remap emits the element min/max of the remapped field)
 }
 // the reference's abort condition (prim_advection_mod.F90:1323): the device flag every remap since the last check ORs into
 static int remap_check(tse_ctx* c) {
@@ -1380,13 +1334,16 @@ int tse_remap_q_ppm(tse_ctx* c, double* Qdp, const double* dp1, const double* dp
   do {
     if (hipMemcpy(c->q(1), Qdp, c->trc() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c->dp, dp1, lev * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d2, dp2, lev * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemset(c->divdp_proj, 0, lev * 8) != hipSuccess) { rc = fail("tse_remap_q_ppm: upload failed"); break; }
-    const int generic = getenv("TSE_REMAP_GENERIC") ? atoi(getenv("TSE_REMAP_GENERIC")) : 0;
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(8 * ((c->nelemd + 7) / 8)), dim3(REMAP_THREADS), sizeof(RemapLds), c->stream, c->qsize, 0.0, c->ps0, c->hyai, c->hybi,
-                         c->dp, c->divdp_proj, c->dp3d, c->ps_v, c->q(1), c->bad, (double*)nullptr, (double*)nullptr, generic, c->sink, (const double*)d2,
-                         (const int*)nullptr, c->nelemd, c->lvl_tmp, RemapFuse{});
-    };
-    { Scope s(c, "remap_q_ppm"); if (c->remap_alg2) go(k_remap<1, true>); else go(k_remap<1, false>); }   // (tse_kernel_time("remap") counts it)
+    const int generic = route(c).remap_generic;
+    {
+      Scope s(c, "remap_q_ppm");   // (tse_kernel_time("remap") counts it)
+      with_remap(1, c->remap_alg2, false, [&](auto kern, int threads) -> int {
+        hipLaunchKernelGGL(kern, dim3(8 * ((c->nelemd + 7) / 8)), dim3(threads), sizeof(RemapLds), c->stream, c->qsize, 0.0, c->ps0, c->hyai, c->hybi,
+                           c->dp, c->divdp_proj, c->dp3d, c->ps_v, c->q(1), c->bad, (double*)nullptr, (double*)nullptr, generic, c->sink, (const double*)d2,
+                           (const int*)nullptr, c->nelemd, c->lvl_tmp, RemapFuse{});
+        return 0;
+      });
+    }
     if (hipGetLastError() != hipSuccess) { rc = fail("tse_remap_q_ppm: kernel launch failed"); break; }
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(Qdp, c->q(1), c->trc() * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail("tse_remap_q_ppm: download failed"); break; }
     rc = remap_check(c);
@@ -1626,7 +1583,7 @@ int tse_prim_run_subcycle(tse_ctx* c, double tstep, int nsub, int* nstep_io) {
     return 2;
   };
   // the remap that closes the cycle assembles the last step's final DSS + time average on read (TSE_REMAP_FUSED=0: two kernels)
-  const bool fuse_remap = remap_fused() && dss_on_read() && c->tps * 8 < ((size_t)1 << 32) && !(getenv("TSE_REMAP_NT") && atoi(getenv("TSE_REMAP_NT")) != 1);
+  const bool fuse_remap = route(c).remap_fused;
   for (int s = 0; s < nsub; s++) {
     if (s >= 2) {
       HIPCHK(hipEventSynchronize(c->bad_ev[s & 1]));
@@ -1845,8 +1802,9 @@ extern "C" int tse_test_limiter(int option, int nslab, double* x, const double* 
     if (hipMalloc((void**)&d, npad * 34 * 8) != hipSuccess || hipMalloc((void**)&dch, npad * 4) != hipSuccess) { rc = fail("tse_test_limiter: cannot allocate"); break; }
     if (hipMemcpy(d, hx, npad * 34 * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = fail("tse_test_limiter: upload failed"); break; }
     double *dx = d, *dc = dx + npad * 16, *dmn = dc + npad * 16, *dmx = dmn + npad;
-    if (option == 9) hipLaunchKernelGGL(k_test_limiter<9>, dim3((unsigned)(npad / 16)), dim3(64), 0, 0, dx, dc, dmn, dmx, dch);
-    else hipLaunchKernelGGL(k_test_limiter<8>, dim3((unsigned)(npad / 16)), dim3(64), 0, 0, dx, dc, dmn, dmx, dch);
+    with_limiter(true, option, [&](auto, auto lopt) {
+      hipLaunchKernelGGL(k_test_limiter<decltype(lopt)::value>, dim3((unsigned)(npad / 16)), dim3(64), 0, 0, dx, dc, dmn, dmx, dch);
+    });
     if (hipGetLastError() != hipSuccess) { rc = fail("tse_test_limiter: kernel launch failed"); break; }
     if (hipDeviceSynchronize() != hipSuccess) { rc = fail("tse_test_limiter: the kernel failed"); break; }
     if (hipMemcpy(hx, d, npad * 34 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hch.data(), dch, npad * 4, hipMemcpyDeviceToHost) != hipSuccess) {
