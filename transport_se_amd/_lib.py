@@ -229,6 +229,8 @@ def lib(path=None, nlev=None):
     L.tse_view_put.argtypes = [vp, C.c_char_p, i, C.POINTER(View), vp]
     L.tse_view_get.argtypes = [vp, C.c_char_p, i, C.POINTER(View), vp]
     L.tse_view_plan.argtypes = [C.c_char_p, i, i, C.POINTER(View), i, C.POINTER(i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    if hasattr(L, "tse_test_dcmip_point"):   # the -DTSE_AB_HOOKS twin only (HipMod.test_dcmip_point)
+        L.tse_test_dcmip_point.argtypes = [vp, i, d, vp, vp]
     _libs[path] = L
     _check_nlev(L, path, nlev)
     return L

@@ -1817,6 +1817,48 @@ extern "C" int tse_test_limiter(int option, int nslab, double* x, const double* 
   (void)hipFree(d); (void)hipFree(dch);
   return rc;
 }
+// The per-step inputs without the factorisation (tests/test_gpu_dcmip_pointwise.py): dcmip_point itself at every (column, level), the
+// products u * dpr, v * dpr and (-9.80616 * rho) * w formed in k_dcmip_step's operand order.  One thread per column and interface.
+__global__ __launch_bounds__(256) void k_test_dcmip_point(int nelemd, int test, double t_wind, double t_now, const double* __restrict__ lat,
+                                                          const double* __restrict__ lon, const double* __restrict__ zm,
+                                                          const double* __restrict__ zi, const double* __restrict__ pint,
+                                                          double* __restrict__ vn0, double* __restrict__ eta) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)nelemd * NLEVP * 16) return;
+  const int p = (int)(t & 15), k = (int)((t >> 4) % NLEVP), e = (int)(t / (NLEVP * 16));
+  const double lo = lon[(size_t)e * 16 + p], la = lat[(size_t)e * 16 + p];
+  const DcmipPt i = dcmip_point(test, t_now, lo, la, zi[k]);
+  eta[((size_t)e * NLEVP + k) * 16 + p] = (-9.80616 * i.rho) * i.w;
+  if (k < NLEV) {
+    const DcmipPt m = dcmip_point(test, t_wind, lo, la, zm[k]);
+    const double dpr = pint[k + 1] - pint[k];
+    vn0[(((size_t)e * NLEV + k) * 2 + 0) * 16 + p] = m.u * dpr;
+    vn0[(((size_t)e * NLEV + k) * 2 + 1) * 16 + p] = m.v * dpr;
+  }
+}
+// vn0_out: [nelemd][NLEV][2][4][4], eta_out: [nelemd][NLEVP][4][4], host arrays: what tse_dcmip_step_inputs(nstep, tstep) leaves in vn0 and
+// eta_dot_dpdn, evaluated point by point.  Touches no field of the context (it reads the tables of tse_dcmip_init).
+extern "C" int tse_test_dcmip_point(tse_ctx* c, int nstep, double tstep, double* vn0_out, double* eta_out) {
+  if (!c || !vn0_out || !eta_out) return fail("tse_test_dcmip_point: null argument");
+  if (!c->dcmip_test) return fail("tse_test_dcmip_point: call tse_dcmip_init first");
+  const size_t nv = (size_t)c->nelemd * NLEV * 32, ne = (size_t)c->nelemd * NLEVP * 16;
+  const double t_wind = (nstep > 0 ? nstep - 1 : 0) * tstep, t_now = nstep * tstep;
+  double* d = nullptr;
+  int rc = 0;
+  do {
+    if (hipMalloc((void**)&d, (nv + ne) * 8) != hipSuccess) { rc = fail("tse_test_dcmip_point: cannot allocate"); break; }
+    hipLaunchKernelGGL(k_test_dcmip_point, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, c->stream, c->nelemd, c->dcmip_test, t_wind, t_now,
+                       (const double*)c->lat, (const double*)c->lon, (const double*)c->zm, (const double*)c->zi, (const double*)c->pint, d, d + nv);
+    if (hipGetLastError() != hipSuccess) { rc = fail("tse_test_dcmip_point: kernel launch failed"); break; }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail("tse_test_dcmip_point: the kernel failed"); break; }
+    if (hipMemcpy(vn0_out, d, nv * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(eta_out, d + nv, ne * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+      rc = fail("tse_test_dcmip_point: download failed"); break;
+    }
+  } while (0);
+  if (rc) (void)hipGetLastError();
+  (void)hipFree(d);
+  return rc;
+}
 #endif
 // the two switches reset their own groups only: the comm_* groups (tse_comm_timing) and all the others (tse_timing)
 static void reset_timers(tse_ctx* c, bool comm) {

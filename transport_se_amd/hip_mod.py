@@ -399,6 +399,15 @@ class HipMod:
     def dcmip_step_inputs(self, nstep, tstep):
         self._chk(self.L.tse_dcmip_step_inputs(self.h, nstep, tstep))
 
+    def test_dcmip_point(self, nstep, tstep):
+        """hooks library only (lib_path=_lib.HOOKS_SO): (vn0, eta_dot_dpdn) of dcmip_step_inputs(nstep, tstep) from the unfactored point
+        functions, as host arrays; the context's fields are left alone"""
+        if not hasattr(self.L, "tse_test_dcmip_point"):
+            raise TseError("tse_test_dcmip_point is an entry of the -DTSE_AB_HOOKS library only")
+        vn0 = np.empty((self.nelemd, self.nlev, 2, NP, NP)); eta = np.empty((self.nelemd, self.nlevp, NP, NP))
+        self._chk(self.L.tse_test_dcmip_point(self.h, int(nstep), float(tstep), _vp(vn0), _vp(eta)))
+        return vn0, eta
+
     def prim_run_subcycle(self, tstep, nsub, nstep):
         """nsub remap cycles from step count nstep; returns the new step count.  On "negative layer thickness" the TseError carries
         .rc = 2 and .nstep = the step count at the end of the first failing cycle (prim_advection_mod.F90:1323 aborts there)."""
