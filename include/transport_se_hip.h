@@ -262,6 +262,35 @@ int tse_view_get(tse_ctx *ctx, const char *field, int nt, const tse_view *v, voi
 int tse_view_plan(const char *field, int nelemd, int qsize, const tse_view *v, int for_get,
                   int *path, long long *lo, long long *hi);
 
+/* ---- tracer forcing: the physics step between two tse_prim_run_subcycle calls (E3SM's applyCAMforcing_tracers; the reference carries
+ * derived%FQ, element_mod.F90:69, and never applies it) ----
+ * For every element, tracer q < qsize, level and point of Qdp = Qdp(nt), these operations in this order, none contracted:
+ *   mode TSE_FORCING_TENDENCY:  v = dt * FQ
+ *   mode TSE_FORCING_ADJUST:    dpk = (hyai(k+1)-hyai(k))*ps0 + (hybi(k+1)-hybi(k))*ps_v;  Q = Qdp / dpk;  v = dpk * (FQ - Q)
+ *                               (dp and Q as tse_state_q forms them: FQ is the new mixing ratio, dt is ignored)
+ *   asked = v;  if (Qdp + v < 0 && v < 0) v = (Qdp < 0) ? 0.0 : -Qdp;  Qdp(nt) = Qdp + v
+ * so no tracer mass is made negative and a negative one (a limiter-sized undershoot) is left alone.  Inputs are finite: a NaN propagates,
+ * nothing is checked on the device.
+ * fq is a view of the shape and under the rules of a "qdp" put view (tse_view_plan("qdp", nelemd, qsize, fq, 0, ...) gives its path and
+ * footprint; the same three paths; a zero stride broadcasts) and every check tse_view_put makes before it enqueues applies unchanged.
+ * Refused besides: mode outside 0|1, a dt that is not finite, and a view whose footprint overlaps the library's Qdp(nt).  On failure:
+ * nonzero, tse_last_error(), nothing enqueued.
+ * stream orders as in tse_view_put (not null: wait for it, run on the compute stream, make it wait; null: complete on return).
+ * budget may be null; otherwise a HOST array [nelemd][qsize][2]: entry 0 = sum spheremp[p] * v, the mass applied, entry 1 =
+ * sum spheremp[p] * (asked - v), the mass the clip withheld (exactly 0 where nothing was clipped), both over the 16 points and all levels,
+ * every term formed without contraction and added in the order of k_norm_partials (csrc/tse_kernels.h), so a share depends on the
+ * element's own data alone.  With a budget the call is complete on return whatever stream is.
+ * Side effects: those of tse_copy_qdp_h2d -- the cached element bounds are dropped, Q / lnps become stale; the prescribed case's static
+ * inputs, the norm reference and the norm setup are untouched.  Timer group "forcing". */
+#define TSE_FORCING_TENDENCY 0
+#define TSE_FORCING_ADJUST   1
+int tse_apply_forcing(tse_ctx *ctx, int nt, double dt, int mode, const tse_view *fq, void *stream, double *budget);
+/* The same for a host whose elem(:) lives in host memory: fq_elem1 = the address of elem(1)%derived%FQ(1,1,1,1,tl), elem_stride the byte
+ * stride between elements, qsize_d the host array's tracer extent.  FQ crosses by the path of tse_copy_qdp_h2d (2-D DMA from a registered
+ * range, pinned staging otherwise) into the device Q field of tse_state_q, which this call leaves stale anyway (allocated here when no
+ * tse_state_q has run: a context that forms Q holds no more memory than before); then the same kernel.  Complete on return. */
+int tse_apply_forcing_host(tse_ctx *ctx, int nt, double dt, int mode, const double *fq_elem1, size_t elem_stride, int qsize_d, double *budget);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -301,11 +330,11 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
 /* ---- introspection for tests and the benchmark harness ---- */
 /* device pointers of internal fields: "qdp1", "qdp2" [nelemd][qsize][nlev][16] (the two time levels are two allocations), "vn0", "dp", "divdp", "divdp_proj",
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
- * (both null before the first tse_state_q), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference) */
+ * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

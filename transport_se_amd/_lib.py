@@ -145,7 +145,7 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchr
            "tse_halo_layout", "tse_halo_minmax_layout", "tse_comm_unique_id", "tse_comm_init", "tse_comm_precheck", "tse_comm_version", "tse_comm_info", "tse_comm_abort",
            "tse_boundary_layout", "tse_patch_layout", "tse_placement", "tse_invalidate_cache", "tse_divergence_sphere", "tse_laplace_sphere_wk", "tse_remap_q_ppm", "tse_host_register", "tse_element_mass", "tse_element_qdiag",
            "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h", "tse_norm_setup", "tse_norm_reference", "tse_norm_partials", "tse_mix_partials",
-           "tse_view_put", "tse_view_get", "tse_view_plan"]
+           "tse_view_put", "tse_view_get", "tse_view_plan", "tse_apply_forcing", "tse_apply_forcing_host"]
 COMM_ID_BYTES = 128
 
 
@@ -229,6 +229,8 @@ def lib(path=None, nlev=None):
     L.tse_view_put.argtypes = [vp, C.c_char_p, i, C.POINTER(View), vp]
     L.tse_view_get.argtypes = [vp, C.c_char_p, i, C.POINTER(View), vp]
     L.tse_view_plan.argtypes = [C.c_char_p, i, i, C.POINTER(View), i, C.POINTER(i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.tse_apply_forcing.argtypes = [vp, i, d, i, C.POINTER(View), vp, vp]
+    L.tse_apply_forcing_host.argtypes = [vp, i, d, i, vp, sz, i, vp]
     if hasattr(L, "tse_test_dcmip_point"):   # the -DTSE_AB_HOOKS twin only (HipMod.test_dcmip_point)
         L.tse_test_dcmip_point.argtypes = [vp, i, d, vp, vp]
     _libs[path] = L

@@ -1639,12 +1639,14 @@ static void launch_view(tse_ctx* c, const ViewPlan& p, const tse_view* v, double
   } else hipLaunchKernelGGL((k_view_generic<PUT>), blocks(slabs * 16), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
 }
 
-static int view_io(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream, bool get) {
-  const char* who = get ? "tse_view_get" : "tse_view_put";
+// Everything a view entry (tse_view_put, tse_view_get, tse_apply_forcing) checks before it enqueues: the plan of the view, nt, null and
+// alignment, the caller's stream (not being captured, on the context's device), the view's memory (device memory of the context's device)
+// and its footprint (inside the allocation that holds ptr).  Returns 0 with the plan in *out, or 1 with the message set, under the name `who`.
+static int view_checks(tse_ctx* c, const char* who, const char* field, int nt, const tse_view* v, void* stream, bool get, ViewPlan* out) {
   if (!c) return fail("%s: null context", who);
-  ViewPlan p;
+  ViewPlan& p = *out;
   std::string err;
-  if (view_plan(field, c->nelemd, c->qsize, v, get, &p, &err)) return fail("%s", err.c_str());
+  if (view_plan(field, c->nelemd, c->qsize, v, get, &p, &err)) return fail("%s%s", strcmp(who, "tse_apply_forcing") ? "" : "tse_apply_forcing: ", err.c_str());
   if (p.field == VF_QDP && (nt < 1 || nt > 2)) return fail("%s: nt=%d", who, nt);
   if (!v->ptr) return fail("%s: null view pointer", who);
   if ((uintptr_t)v->ptr & 7) return fail("%s: the view pointer %p is not 8-byte aligned", who, v->ptr);
@@ -1672,6 +1674,14 @@ static int view_io(tse_ctx* c, const char* field, int nt, const tse_view* v, voi
   const __int128 a0 = (__int128)(uintptr_t)abase, a1 = a0 + (__int128)asize, p0 = (__int128)(uintptr_t)v->ptr;
   if (p0 + (__int128)p.lo * 8 < a0 || p0 + (__int128)p.hi * 8 > a1)
     return fail("%s: the view reaches doubles [%lld, %lld) around %p, outside its allocation [%p, +%zu bytes)", who, p.lo, p.hi, v->ptr, (void*)abase, asize);
+  return 0;
+}
+
+static int view_io(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream, bool get) {
+  const char* who = get ? "tse_view_get" : "tse_view_put";
+  ViewPlan p;
+  if (view_checks(c, who, field, nt, v, stream, get, &p)) return 1;
+  hipStream_t us = (hipStream_t)stream;
 
   double* lib = nullptr;
   switch (p.field) {
@@ -1708,6 +1718,93 @@ static int view_io(tse_ctx* c, const char* field, int nt, const tse_view* v, voi
 }
 int tse_view_put(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream) { return view_io(c, field, nt, v, stream, false); }
 int tse_view_get(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream) { return view_io(c, field, nt, v, stream, true); }
+
+// ---- tracer forcing: Qdp(nt) += FQ of the host, on the device (k_forcing, tse_kernels.h) --------------------------
+// tse_apply_forcing reads FQ through a view held to the rules of a "qdp" put view (view_checks); tse_apply_forcing_host brings FQ of a
+// host-memory elem(:) over by the path of tse_copy_qdp_h2d into the Q field of tse_state_q -- stale after this call anyway, allocated here if
+// no tse_state_q has run, so a context that forms Q holds no field more than before -- and runs the same kernel on that dense field.
+static int forcing_args(tse_ctx* c, const char* who, int nt, double dt, int mode) {
+  if (!c) return fail("%s: null context", who);
+  if (mode != TSE_FORCING_TENDENCY && mode != TSE_FORCING_ADJUST) return fail("%s: mode=%d (0: tendency, 1: adjust)", who, mode);
+  if (!std::isfinite(dt)) return fail("%s: dt=%g is not finite", who, dt);
+  if (nt < 1 || nt > 2) return fail("%s: nt=%d", who, nt);
+  return 0;
+}
+template <int MODE, bool BUDGET>
+static void launch_forcing(tse_ctx* c, const ViewPlan& p, const tse_view* v, int nt, double dt, double* budget_d) {
+  const long long* s = v->stride;
+  const bool base16 = ((uintptr_t)v->ptr & 15) == 0;
+  const dim3 grid((unsigned)((size_t)c->nelemd * c->qsize));
+#define TSE_FORCING(PATH, W) hipLaunchKernelGGL((k_forcing<MODE, PATH, W, BUDGET>), grid, dim3(VIEW_THREADS), 0, c->stream, c->qsize, s[0], s[1], s[2], s[3], s[4], dt, \
+    (const double*)c->ps_v, (const double*)c->hyai, (const double*)c->hybi, c->ps0, (const double*)c->spheremp, c->q(nt), (const double*)v->ptr, budget_d)
+  if (p.path == 0) {
+    if (base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0) TSE_FORCING(0, true); else TSE_FORCING(0, false);
+  } else if (p.path == 1) {
+    if (base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0) TSE_FORCING(1, true); else TSE_FORCING(1, false);
+  } else TSE_FORCING(2, false);
+#undef TSE_FORCING
+}
+// every check has passed: order behind the caller's stream, launch, hand the order back; with a budget (host [nelemd][qsize][2]) the call
+// is complete on return
+static int forcing_run(tse_ctx* c, const char* who, int nt, double dt, int mode, const ViewPlan& p, const tse_view* v, hipStream_t us, double* budget) {
+  const size_t nb = (size_t)c->nelemd * c->qsize * 2;
+  double* bd = nullptr;
+  if (budget && dalloc(&bd, nb)) return 1;
+  auto give_up = [&](int rc) { if (bd) (void)hipFree(bd); return rc; };
+  if (us && !c->view_ev[0])
+    for (hipEvent_t& e : c->view_ev)
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return give_up(fail("%s: cannot create an event", who)); }
+  set_bounds_cache(c, 0);   // the side effects of tse_copy_qdp_h2d: the cached element bounds are dropped, Q / lnps are stale
+  int rc = 0;
+  if (us) rc = hipEventRecord(c->view_ev[0], us) != hipSuccess || hipStreamWaitEvent(c->stream, c->view_ev[0], 0) != hipSuccess;
+  if (!rc) {
+    Scope s(c, "forcing");
+    if (mode == TSE_FORCING_TENDENCY) { if (bd) launch_forcing<0, true>(c, p, v, nt, dt, bd); else launch_forcing<0, false>(c, p, v, nt, dt, bd); }
+    else { if (bd) launch_forcing<1, true>(c, p, v, nt, dt, bd); else launch_forcing<1, false>(c, p, v, nt, dt, bd); }
+    rc = hipGetLastError() != hipSuccess;
+  }
+  if (!rc && us) rc = hipEventRecord(c->view_ev[1], c->stream) != hipSuccess || hipStreamWaitEvent(us, c->view_ev[1], 0) != hipSuccess;
+  if (!rc && bd) rc = hipMemcpyAsync(budget, bd, nb * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess;
+  if (!rc && (bd || !us)) rc = hipStreamSynchronize(c->stream) != hipSuccess;
+  if (rc) { (void)hipGetLastError(); rc = fail("%s: launch or copy failed", who); }
+  return give_up(rc);
+}
+int tse_apply_forcing(tse_ctx* c, int nt, double dt, int mode, const tse_view* fq, void* stream, double* budget) {
+  const char* who = "tse_apply_forcing";
+  if (forcing_args(c, who, nt, dt, mode)) return 1;
+  ViewPlan p;
+  if (view_checks(c, who, "qdp", nt, fq, stream, false, &p)) return 1;
+  // FQ is read while Qdp(nt) is written in place: no address of the view may lie inside that field
+  const __int128 p0 = (__int128)(uintptr_t)fq->ptr, f0 = p0 + (__int128)p.lo * 8, f1 = p0 + (__int128)p.hi * 8;
+  const __int128 q0 = (__int128)(uintptr_t)c->q(nt), q1 = q0 + (__int128)c->trc() * 8;
+  if (f0 < q1 && q0 < f1) return fail("%s: the view [%p%+lld, %p%+lld doubles) overlaps Qdp(%d), the field it is applied to", who, fq->ptr, p.lo, fq->ptr, p.hi, nt);
+  return forcing_run(c, who, nt, dt, mode, p, fq, (hipStream_t)stream, budget);
+}
+int tse_apply_forcing_host(tse_ctx* c, int nt, double dt, int mode, const double* fq1, size_t stride, int qsize_d, double* budget) {
+  const char* who = "tse_apply_forcing_host";
+  if (forcing_args(c, who, nt, dt, mode)) return 1;
+  if (!fq1) return fail("%s: null FQ", who);
+  if (qsize_d < c->qsize) return fail("%s: qsize_d=%d < qsize=%d", who, qsize_d, c->qsize);
+  const size_t per = (size_t)c->qsize * NLEV * 16;   // FQ(np,np,nlev,qsize_d,timelevels): the caller names the time level by the address
+  if (stride < per * 8 && c->nelemd > 1) return fail("%s: element stride %zu smaller than the field (%zu bytes)", who, stride, per * 8);
+  if (!c->qmix) {
+    const hipError_t e = hipMalloc((void**)&c->qmix, c->trc() * 8);
+    if (e != hipSuccess) {
+      (void)hipGetLastError(); c->qmix = nullptr;
+      return fail("%s: cannot allocate the staging field (%.3f GB of device memory): %s", who, c->trc() * 8 / 1e9, hipGetErrorString(e));
+    }
+  }
+  c->qmix_valid = false;   // the Q field is the staging field from here on
+  if (copy_field(c, c->qmix, per, (void*)fq1, stride, per, true)) return 1;
+  tse_view v;
+  v.ptr = c->qmix;
+  const long long dense[5] = {(long long)per, (long long)NLEV * 16, 16, 4, 1};
+  for (int a = 0; a < 5; a++) v.stride[a] = dense[a];
+  ViewPlan p;
+  std::string err;
+  if (view_plan("qdp", c->nelemd, c->qsize, &v, false, &p, &err)) return fail("%s: %s", who, err.c_str());
+  return forcing_run(c, who, nt, dt, mode, p, &v, nullptr, budget);   // (null stream: complete on return, the caller may reuse FQ)
+}
 
 // ---- introspection ------------------------------------------------------------------------------
 void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {

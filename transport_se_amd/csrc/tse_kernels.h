@@ -2441,4 +2441,153 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_view_levels(int nq, long long 
   else { lib_side(); __syncthreads(); view_side(); }
 }
 
+// ---- tracer forcing (tse_apply_forcing): Qdp(nt) += the host's source term FQ, read through a strided view, never below zero ----
+// The rule of E3SM's applyCAMforcing_tracers for one value, these operations in this order, none contracted (tests/forcing_model.py
+// restates it in numpy):
+//   MODE 0 (tendency)  v = dt * FQ
+//   MODE 1 (adjust)    dpk = level_dp(k, ps_v);  Q = Qdp / dpk;  v = dpk * (FQ - Q)      (FQ is the new mixing ratio; a true division)
+//   asked = v;  if (Qdp + v < 0 && v < 0) v = (Qdp < 0) ? 0.0 : -Qdp;  Qdp = Qdp + v
+// so a tracer mass is never made negative and one that is negative already (a limiter-sized undershoot) is left alone.
+// applied = v, withheld = asked - v (bit-zero where nothing was clipped).
+template <int MODE>
+__device__ __forceinline__ void forcing_rule(double dt, double dpk, double fq, double& qdp, double& applied, double& withheld) {
+#pragma clang fp contract(off)
+  double v;
+  if (MODE == 0) v = dt * fq;
+  else { const double Q = mixing_ratio(qdp, dpk); v = dpk * (fq - Q); }
+  const double asked = v;
+  if (qdp + v < 0.0 && v < 0.0) v = (qdp < 0.0) ? 0.0 : -qdp;
+  applied = v;
+  withheld = asked - v;
+  qdp = qdp + v;
+}
+
+// One block per (element, tracer) tile of NLEV x 16 values, the shape of k_view_levels.  A lane owns FORCING_NL items (level k = item / 8,
+// point pair 2h = 2 * (item % 8)): the Qdp side is read and written in place in whole 128-byte lines, 16 bytes per lane.  The FQ side has one
+// loader per path of tse_view_plan("qdp"):
+//   PATH 0  point-fastest: the view's own 128-byte lines, 16 bytes per lane (WIDE: view base 16-byte aligned, even element / q / level
+//           strides) or two 8-byte loads;
+//   PATH 1  level-fastest: the rows of consecutive levels go through the LDS image tile[p][VIEW_PITCH] as in k_view_levels<true> (WIDE as
+//           there), the only barrier of the kernel without a budget;
+//   PATH 2  any strides: two address computations per lane and item.
+// Every lane issues all its global loads -- Qdp, FQ, ps_v, spheremp -- before the first use of any of them.
+// BUDGET: out[(e * nq + q) * 2 + {0, 1}] = sum spheremp[p] * applied, sum spheremp[p] * withheld over the tile, every term formed without
+// contraction and added in THE ORDER of k_norm_partials (lane (p, g) adds the levels of group g ascending; column p = ((s0 + s1) + s2) + s3;
+// then the points 0..15 ascending, all sixteen), so a share is a function of the element's own data alone.  The terms pass through LDS;
+// without BUDGET there is neither that work nor its two barriers.
+constexpr int FORCING_NL = (8 * NLEV + VIEW_THREADS - 1) / VIEW_THREADS;
+template <int MODE, int PATH, bool WIDE, bool BUDGET>
+__global__ __launch_bounds__(VIEW_THREADS) void k_forcing(int nq, long long vs_e, long long vs_q, long long vs_k, long long vs_j, long long vs_i, double dt,
+                                                          const double* __restrict__ ps_v, const double* __restrict__ hyai, const double* __restrict__ hybi, double ps0,
+                                                          const double* __restrict__ spheremp, double* __restrict__ Qdp, const double* __restrict__ view,
+                                                          double* __restrict__ budget) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) double tile[PATH == 1 ? 16 * VIEW_PITCH : 2];
+  __shared__ __attribute__((aligned(16))) double term[BUDGET ? 2 * NLEV * 16 : 2];
+  __shared__ double part[BUDGET ? 2 * NORM_THREADS : 2];
+  const int q = (int)(blockIdx.x % (unsigned)nq);
+  const long long e = (long long)(blockIdx.x / (unsigned)nq);
+  double* L = Qdp + ((size_t)e * nq + q) * NLEV * 16;
+  const double* V = view + e * vs_e + q * vs_q;
+  const int tid = threadIdx.x, h = tid & 7;
+  constexpr int K = NLEV, KP = K / 2, NL = FORCING_NL;
+  double2 x[NL], f[NL];
+  double2 ps = make_double2(0.0, 0.0), w = make_double2(0.0, 0.0);
+#pragma unroll
+  for (int u = 0; u < NL; u++) { const int it = min(u * VIEW_THREADS + tid, 8 * K - 1); x[u] = *(const double2*)(L + (it >> 3) * 16 + 2 * (it & 7)); }   // (a lane past the end reloads the last item)
+  if (MODE == 1) ps = *(const double2*)(ps_v + (size_t)e * 16 + 2 * h);
+  if (BUDGET) w = *(const double2*)(spheremp + (size_t)e * 16 + 2 * h);
+  if (PATH == 0) {
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+      const int it = min(u * VIEW_THREADS + tid, 8 * K - 1);
+      const double* s = V + (it >> 3) * vs_k + 2 * h;
+      if (WIDE) f[u] = *(const double2*)s; else f[u] = make_double2(s[0], s[1]);
+    }
+  } else if (PATH == 2) {
+    const long long o = (h >> 1) * vs_j + 2 * (h & 1) * vs_i;
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+      const int it = min(u * VIEW_THREADS + tid, 8 * K - 1);
+      const double* s = V + (it >> 3) * vs_k + o;
+      f[u] = make_double2(s[0], s[vs_i]);
+    }
+  } else {
+    const long long S = vs_i;
+    if (WIDE) {
+      constexpr int NV = (16 * KP + VIEW_THREADS - 1) / VIEW_THREADS;
+      double2 r[NV];
+#pragma unroll
+      for (int u = 0; u < NV; u++) { const int it = min(u * VIEW_THREADS + tid, 16 * KP - 1); r[u] = *(const double2*)(V + (it / KP) * S + 2 * (it % KP)); }
+#pragma unroll
+      for (int u = 0; u < NV; u++) view_keep(r[u]);
+#pragma unroll
+      for (int u = 0; u < NL; u++) view_keep(x[u]);
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int it = u * VIEW_THREADS + tid;
+        if (it < 16 * KP) *(double2*)(tile + (it / KP) * VIEW_PITCH + 2 * (it % KP)) = r[u];
+      }
+    } else {
+      constexpr int NV = (16 * K + VIEW_THREADS - 1) / VIEW_THREADS;
+      double r[NV];
+#pragma unroll
+      for (int u = 0; u < NV; u++) { const int it = min(u * VIEW_THREADS + tid, 16 * K - 1); r[u] = V[(it / K) * S + it % K]; }
+#pragma unroll
+      for (int u = 0; u < NV; u++) view_keep(r[u]);
+#pragma unroll
+      for (int u = 0; u < NL; u++) view_keep(x[u]);
+#pragma unroll
+      for (int u = 0; u < NV; u++) {
+        const int it = u * VIEW_THREADS + tid;
+        if (it < 16 * K) tile[(it / K) * VIEW_PITCH + it % K] = r[u];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+      const int it = min(u * VIEW_THREADS + tid, 8 * K - 1);
+      const double* s = tile + 2 * h * VIEW_PITCH + (it >> 3);
+      f[u] = make_double2(s[0], s[VIEW_PITCH]);
+    }
+  }
+  if (PATH != 1) {
+#pragma unroll
+    for (int u = 0; u < NL; u++) { view_keep(x[u]); view_keep(f[u]); }
+  }
+#pragma unroll
+  for (int u = 0; u < NL; u++) {
+    const int it = u * VIEW_THREADS + tid;
+    if (it < 8 * K) {
+      const int k = it >> 3;
+      double dx = 0.0, dy = 0.0;
+      if (MODE == 1) { dx = level_dp(hyai, hybi, ps0, k, ps.x); dy = level_dp(hyai, hybi, ps0, k, ps.y); }
+      double2 y = x[u], a, r;
+      forcing_rule<MODE>(dt, dx, f[u].x, y.x, a.x, r.x);
+      forcing_rule<MODE>(dt, dy, f[u].y, y.y, a.y, r.y);
+      *(double2*)(L + k * 16 + 2 * h) = y;
+      if (BUDGET) {
+        *(double2*)(term + k * 16 + 2 * h) = make_double2(w.x * a.x, w.y * a.y);
+        *(double2*)(term + (K + k) * 16 + 2 * h) = make_double2(w.x * r.x, w.y * r.y);
+      }
+    }
+  }
+  if (BUDGET) {
+    __syncthreads();
+    if (tid < NORM_THREADS) {
+      const int p = tid & 15, g = tid >> 4;
+      double s0 = 0.0, s1 = 0.0;
+      for (int k = g * NORM_LPG; k < (g + 1) * NORM_LPG; k++) { s0 = s0 + term[k * 16 + p]; s1 = s1 + term[(K + k) * 16 + p]; }
+      part[tid] = s0; part[NORM_THREADS + tid] = s1;
+    }
+    __syncthreads();
+    if (tid < 2) {
+      const double* v = part + tid * NORM_THREADS;
+      double a = 0.0;
+      for (int i = 0; i < 16; i++) a = a + (((v[i] + v[16 + i]) + v[32 + i]) + v[48 + i]);
+      budget[((size_t)e * nq + q) * 2 + tid] = a;
+    }
+  }
+}
+
 }  // namespace tse

@@ -220,6 +220,13 @@ class PrimRun:
             np1 = self.step()
         return np1
 
+    def apply_forcing(self, fq, axes="eqkji", mode="tendency", dt=None, budget=False):
+        """the physics step between two remap cycles: HipMod.apply_forcing on the time level the next tracer step reads as n0 (level 1 for
+        an even step count, 2 for an odd one, as tse_prim_run_subcycle derives it).  dt defaults to rsplit * tstep, the time one remap
+        cycle covers."""
+        n0 = 1 if self.nstep % 2 == 0 else 2
+        return self.hip.apply_forcing(fq, axes, n0, dt=self.rsplit * self.tstep if dt is None else dt, mode=mode, budget=budget)
+
     def comm_stats(self):
         """{name: (ms, launches)} of this rank's halo-exchange timers (HipMod.comm_times: the seven comm_* groups and their totals) since
         hip.comm_timing(True).  Several ranks: a collective call over the control plane; on rank 0 the dict also holds "max" = {name:

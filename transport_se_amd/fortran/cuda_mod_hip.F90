@@ -48,6 +48,10 @@ module cuda_mod
   ! state exchange with a GPU-resident host (INTEGRATION.md section 2e): fields move between the host's own DEVICE arrays and the library
   ! on the device, through strided views; nothing crosses the host link
   public :: tse_view, view_put_hip, view_get_hip
+  ! tracer forcing, the physics step between two prim_run_subcycle_hip calls (INTEGRATION.md section 2f): Qdp(nt) = Qdp(nt) + dt*FQ, never
+  ! below zero, from a device array (apply_forcing_hip) or from elem(:)%derived%FQ in host memory (apply_forcing_elem_hip)
+  public :: apply_forcing_hip, apply_forcing_elem_hip
+  integer, parameter, public :: forcing_tendency = 0, forcing_adjust = 1   ! TSE_FORCING_TENDENCY, TSE_FORCING_ADJUST
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
   integer(c_int), save :: res_nstep = 0   ! the library's step count after the last prim_run_subcycle_hip
   integer(kind=8), save :: t_c0
@@ -174,6 +178,15 @@ module cuda_mod
      integer(c_int) function tse_view_get(ctx, field, nt, v, stream) bind(C, name='tse_view_get')
        import; type(c_ptr), value :: ctx, stream; character(kind=c_char), intent(in) :: field(*); integer(c_int), value :: nt
        type(tse_view), intent(in) :: v
+     end function
+     integer(c_int) function tse_apply_forcing(ctx, nt, dt, mode, fq, stream, budget) bind(C, name='tse_apply_forcing')
+       import; type(c_ptr), value :: ctx, stream, budget; integer(c_int), value :: nt, mode; real(c_double), value :: dt
+       type(tse_view), intent(in) :: fq
+     end function
+     integer(c_int) function tse_apply_forcing_host(ctx, nt, dt, mode, fq_elem1, elem_stride, qsize_d, budget) &
+          bind(C, name='tse_apply_forcing_host')
+       import; type(c_ptr), value :: ctx, fq_elem1, budget; integer(c_int), value :: nt, mode, qsize_d; real(c_double), value :: dt
+       integer(c_size_t), value :: elem_stride
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -767,5 +780,36 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine view_get_hip
+
+  ! Qdp(:,:,:,1:qsize,nt) <- Qdp + the source term of the host's device array at ptr (a "qdp" view: strides(1:5) in doubles for element, q,
+  ! level, j, i), clipped so that no tracer mass becomes negative (include/transport_se_hip.h: tse_apply_forcing).  mode forcing_tendency:
+  ! dt * FQ is added; forcing_adjust: FQ is the new mixing ratio and dt is ignored.  nt: the level the next tracer step reads as n0
+  ! (TimeLevel_Qdp).  stream as in view_put_hip.
+  subroutine apply_forcing_hip(nt, dt, mode, ptr, strides, stream)
+    integer,              intent(in) :: nt, mode
+    real(kind=real_kind), intent(in) :: dt
+    type(c_ptr),          intent(in) :: ptr, stream
+    integer(c_long_long), intent(in) :: strides(5)
+    type(tse_view) :: v
+    v%ptr = ptr; v%stride = strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_apply_forcing(ctx, int(nt,c_int), real(dt,c_double), int(mode,c_int), v, stream, c_null_ptr), 'apply_forcing_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine apply_forcing_hip
+
+  ! the same from elem(:)%derived%FQ(:,:,:,:,tl) in host memory (the path of copy_qdp_h2d brings it over); complete on return
+  subroutine apply_forcing_elem_hip(elem, nt, tl, dt, mode)
+    type(element_t), intent(in), target :: elem(:)
+    integer,              intent(in) :: nt, tl, mode
+    real(kind=real_kind), intent(in) :: dt
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_apply_forcing_host(ctx, int(nt,c_int), real(dt,c_double), int(mode,c_int), c_loc(elem(1)%derived%FQ(1,1,1,1,tl)), &
+                                      estride(elem), int(qsize_d,c_int), c_null_ptr), 'apply_forcing_elem_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine apply_forcing_elem_hip
 
 end module cuda_mod

@@ -115,6 +115,18 @@ def _stream_handle(stream):
     return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
 
 
+FORCING_MODES = {"tendency": 0, "adjust": 1}   # TSE_FORCING_TENDENCY, TSE_FORCING_ADJUST
+
+
+def _forcing_mode(mode):
+    """the mode names, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(mode, str):
+        if mode not in FORCING_MODES:
+            raise TseError("apply_forcing: unknown mode %r (the modes are %s)" % (mode, ", ".join(FORCING_MODES)))
+        return FORCING_MODES[mode]
+    return int(mode)
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -436,6 +448,25 @@ class HipMod:
         """dict(path=, lo=, hi=) that put / get would take for this array (module-level view_plan)"""
         v = build_view(field, array, axes, self.nelemd, self.qsize, self.nlev, for_get)
         return view_plan(field, self.nelemd, self.qsize, v, for_get, nlev=self.nlev)
+
+    # ---- tracer forcing: the physics step between two prim_run_subcycle calls (tse_apply_forcing / tse_apply_forcing_host) ----
+    def apply_forcing(self, fq, axes, nt, dt=0.0, mode="tendency", stream=None, budget=False):
+        """Qdp(nt) += the source term `fq`, a device array described as a "qdp" put view (build_view), never below zero (the rule of
+        include/transport_se_hip.h).  mode "tendency": v = dt * fq; "adjust": fq is the new mixing ratio, dt is ignored.  stream orders as
+        in put.  budget=True returns the host array [nelemd][qsize][2] (mass applied, mass the clip withheld; element shares in a fixed
+        order) and makes the call complete on return."""
+        v = build_view("qdp", fq, axes, self.nelemd, self.qsize, self.nlev, False)
+        out = np.empty((self.nelemd, self.qsize, 2)) if budget else None
+        self._chk(self.L.tse_apply_forcing(self.h, int(nt), float(dt), _forcing_mode(mode), C.byref(v), _stream_handle(stream), _vp(out)))
+        return out
+
+    def apply_forcing_host(self, elem_fq, nt, dt, mode, budget=False):
+        """the same from host memory: elem_fq[ie][q < qsize_d][k][j][i] (one time level of derived%FQ(np,np,nlev,qsize_d,timelevels)), as
+        copy_qdp_h2d takes Qdp; complete on return"""
+        f = elem_fq; assert f.dtype == np.float64 and f.flags.c_contiguous and f.ndim == 5
+        out = np.empty((self.nelemd, self.qsize, 2)) if budget else None
+        self._chk(self.L.tse_apply_forcing_host(self.h, int(nt), float(dt), _forcing_mode(mode), _vp(f), f.strides[0], f.shape[1], _vp(out)))
+        return out
 
     def synchronize(self):
         self._chk(self.L.tse_synchronize(self.h))
