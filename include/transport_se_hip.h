@@ -291,6 +291,42 @@ int tse_apply_forcing(tse_ctx *ctx, int nt, double dt, int mode, const tse_view 
  * tse_state_q has run: a context that forms Q holds no more memory than before); then the same kernel.  Complete on return. */
 int tse_apply_forcing_host(tse_ctx *ctx, int nt, double dt, int mode, const double *fq_elem1, size_t elem_stride, int qsize_d, double *budget);
 
+/* ---- vertical remap of a GPU-resident host's OWN level fields (E3SM vertical_remap -> remap1 = remap_Q_ppm, prim_advection_mod.F90:98-214) ----
+ * For every element, field slot f < nf and column: remap_Q_ppm(field, np, nf, dp_src, dp_tgt) with vert_remap_q_alg = alg (0 or 1: mirrored
+ * ghost cells; 2: piecewise-constant end cells; anything else is refused; independent of the context's own setting), in place in the
+ * host's device array.  The result is the fixed sequence of roundings of the library's remap kernel: bit for bit what tse_remap_q_ppm
+ * returns for the same column on the same grids, whatever path the views take.
+ *   mode TSE_REMAP_MASS  the field is mass per layer (Qdp, u*dp)
+ *   mode TSE_REMAP_MEAN  the field is a layer mean a (T, u): m = a * dp_src (one product) as a cell is read, the mass arithmetic, a' = m' /
+ *                        dp_tgt (a true division) as it is written -- the bits of the host's  ttmp = T*dp_star; remap1; T = ttmp/dp
+ * field: shape and rules of a "qdp" GET view with tracer extent nf (any nf >= 1, whatever the context's qsize; the q axis is whatever the
+ * host stacks: u and v are nf = 2): no zero stride, no two index tuples on one address.  Only the addresses of the view are written.
+ * dp_src, dp_tgt: shape and rules of a "dp" PUT view (a zero stride broadcasts).  Every view takes its own path of tse_view_plan.
+ * Library state: none is read or written -- not Qdp, dp, divdp, divdp_proj, dp3d, ps_v, the cached bounds, Q / lnps or the norm fields.
+ * One exception: a field whose footprint lies inside the library's "qdp1" or "qdp2" allocation (tse_device_ptr) is accepted, with the
+ * side effects of tse_copy_qdp_h2d (cached bounds dropped, Q / lnps stale); a view that meets any other allocation of the library is refused.
+ * Before anything is enqueued, as in tse_view_put (nonzero, tse_last_error(), nothing launched): null pointers, nf < 1, mode or alg out of
+ * range, device memory of the context's device, every footprint inside its allocation, the field overlapping neither grid, a stream that
+ * is being captured or belongs to another device.
+ * Bad grids are decided on the device, per element (the grids of a resident host never visit the host): 1 a dp_src that is not a finite
+ * positive number; 2 sum(dp_src) not finite, or so large that sum + 1 == sum; 3 a dp_tgt that is negative or not finite (MEAN: or zero);
+ * 4 a partial sum of dp_tgt below the last level that reaches sum(dp_src) + 1 -- the precondition of the bracket search, the test of
+ * tse_remap_q_ppm.  A refused element's field keeps every bit; the other elements are remapped.
+ * stream orders as in tse_view_put.  stream == NULL: complete on return; returns 2 if any element was refused, tse_last_error() names the
+ * lowest one.  Otherwise 0 after enqueueing, and tse_remap_view_status waits for the compute stream and reports what such calls refused
+ * since it was last read: the count of elements, and in where[4] the element, column, level (from 0) and code of the lowest element of the
+ * earliest call that refused one; then it clears.  (After a NULL-stream call tse_device_ptr "remap_status" holds [nelemd][4] ints: code,
+ * column, level and a flag for the message, of that call.)  Timer group "fieldremap". */
+#define TSE_REMAP_MASS 0
+#define TSE_REMAP_MEAN 1
+int tse_remap_view(tse_ctx *ctx, int nf, int mode, int alg, const tse_view *field, const tse_view *dp_src, const tse_view *dp_tgt, void *stream);
+int tse_remap_view_status(tse_ctx *ctx, int *nrefused, int where[4] /* element, column, level, code */);
+/* the path and the footprint [lo, hi) (doubles relative to ptr) of field, dp_src, dp_tgt, and every refusal that needs no device: nf, the
+ * extent rules, a zero stride in field, and the field overlapping a grid (the ptr members may be offsets into one allocation; with all three
+ * null only the strides are judged).  No context. */
+int tse_remap_view_plan(int nelemd, int nf, const tse_view *field, const tse_view *dp_src, const tse_view *dp_tgt,
+                        int path[3], long long lo[3], long long hi[3]);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -330,11 +366,12 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
 /* ---- introspection for tests and the benchmark harness ---- */
 /* device pointers of internal fields: "qdp1", "qdp2" [nelemd][qsize][nlev][16] (the two time levels are two allocations), "vn0", "dp", "divdp", "divdp_proj",
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
- * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference) */
+ * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference),
+ * "remap_status" [nelemd][4] ints (null before the first tse_remap_view) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

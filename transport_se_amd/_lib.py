@@ -11,7 +11,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libtransport_se_hip.so")
 SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_tables.cpp", "tse_views.cpp", "tse_kernels.h", "tse_device.h",
-                                             "tse_launch.h", "tse_layout.h", "tse_tables.h", "tse_views.h")]
+                                             "tse_launch.h", "tse_layout.h", "tse_tables.h", "tse_views.h", "tse_remap_check.h")]
 # the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own;
 # tse_tables.cpp and tse_views.cpp are host C++, which hipcc would otherwise compile as HIP)
 UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_tables.cpp", ["-x", "c++"]),
@@ -145,7 +145,8 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchr
            "tse_halo_layout", "tse_halo_minmax_layout", "tse_comm_unique_id", "tse_comm_init", "tse_comm_precheck", "tse_comm_version", "tse_comm_info", "tse_comm_abort",
            "tse_boundary_layout", "tse_patch_layout", "tse_placement", "tse_invalidate_cache", "tse_divergence_sphere", "tse_laplace_sphere_wk", "tse_remap_q_ppm", "tse_host_register", "tse_element_mass", "tse_element_qdiag",
            "tse_state_q", "tse_copy_q_d2h", "tse_copy_lnps_d2h", "tse_norm_setup", "tse_norm_reference", "tse_norm_partials", "tse_mix_partials",
-           "tse_view_put", "tse_view_get", "tse_view_plan", "tse_apply_forcing", "tse_apply_forcing_host"]
+           "tse_view_put", "tse_view_get", "tse_view_plan", "tse_apply_forcing", "tse_apply_forcing_host",
+           "tse_remap_view", "tse_remap_view_status", "tse_remap_view_plan"]
 COMM_ID_BYTES = 128
 
 
@@ -231,6 +232,9 @@ def lib(path=None, nlev=None):
     L.tse_view_plan.argtypes = [C.c_char_p, i, i, C.POINTER(View), i, C.POINTER(i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.tse_apply_forcing.argtypes = [vp, i, d, i, C.POINTER(View), vp, vp]
     L.tse_apply_forcing_host.argtypes = [vp, i, d, i, vp, sz, i, vp]
+    L.tse_remap_view.argtypes = [vp, i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(View), vp]
+    L.tse_remap_view_status.argtypes = [vp, C.POINTER(i), C.POINTER(i * 4)]
+    L.tse_remap_view_plan.argtypes = [i, i, C.POINTER(View), C.POINTER(View), C.POINTER(View), C.POINTER(i * 3), C.POINTER(C.c_longlong * 3), C.POINTER(C.c_longlong * 3)]
     if hasattr(L, "tse_test_dcmip_point"):   # the -DTSE_AB_HOOKS twin only (HipMod.test_dcmip_point)
         L.tse_test_dcmip_point.argtypes = [vp, i, d, vp, vp]
     _libs[path] = L

@@ -98,6 +98,12 @@ struct tse_ctx {
   int mm_halo = 0;    // == mm_valid: the neighbour ranks' share of those bounds is already in recvbuf_mm (or on its way: ev_mm)
   hipEvent_t ev_mm = nullptr;   // completion of that prefetched exchange on the communication stream
   hipEvent_t view_ev[2] = {nullptr, nullptr};   // tse_view_put / tse_view_get: the caller's stream -> compute stream -> the caller's stream (created by the first such call)
+  // tse_remap_view (allocated by its first call): the check kernel's verdict per element of the latest call, [nelemd][REMAP_STATUS] ints and
+  // [nelemd][2] doubles (value, limit); the accumulator of the calls that gave a stream, {count, packed first offender} (tse_remap_view_status)
+  int* rv_status = nullptr;
+  double* rv_detail = nullptr;
+  unsigned long long* rv_acc = nullptr;
+  unsigned rv_seq = 0;   // calls that gave a stream since the accumulator was last read
   // halo: one slot per neighbour rank (Schedule(1)%SendCycle/RecvCycle), entries per slot for the two exchange kinds
   int ncol_send = 0, ncol_recv = 0, nlyr_halo = 0;
   int nmm_send = 0, nmm_recv = 0;              // entries of the compact min/max exchange
@@ -481,6 +487,20 @@ int tse_init(tse_ctx** out, const tse_init_args* a) {
   return 0;
 }
 
+// every device allocation the context owns (each one a hipMalloc of its own): what tse_finalize frees, and what a view of tse_remap_view
+// may not touch
+static std::vector<void*> device_allocations(const tse_ctx* c) {
+  const PatchSet& P = c->pset;
+  void* ptrs[] = {c->dcmip_tab, c->dvv_d, c->Dinv, c->metdet, c->rmetdet, c->spheremp, c->rspheremp, c->hyai, c->hybi, c->dp0, c->dss_tab, c->send_src,
+                  c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
+                  c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->norm_owner, c->norm_colw, c->norm_dh, c->qref, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
+                  c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int,
+                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc};
+  std::vector<void*> out;
+  for (void* p : ptrs) if (p) out.push_back(p);
+  return out;
+}
+
 void tse_finalize(tse_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -491,14 +511,7 @@ void tse_finalize(tse_ctx* c) {
   if (c->bad_host) (void)hipHostFree(c->bad_host);
   for (hipEvent_t e : c->bad_ev) if (e) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; i++) { if (c->stage[i]) (void)hipHostFree(c->stage[i]); if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]); }
-  void* ptrs[] = {c->dcmip_tab, c->dvv_d, c->Dinv, c->metdet, c->rmetdet, c->spheremp, c->rspheremp, c->hyai, c->hybi, c->dp0, c->dss_tab, c->send_src,
-                  c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
-                  c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->norm_owner, c->norm_colw, c->norm_dh, c->qref, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
-                  c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (double* p : {c->T, c->B, c->C}) if (p) (void)hipFree(p);
-  const PatchSet& P = c->pset;
-  for (void* p : {(void*)P.pslots, (void*)P.plist_bnd, (void*)P.plist_int, (void*)P.pering, (void*)P.pring, (void*)P.plds, (void*)P.pnb}) if (p) (void)hipFree(p);
+  for (void* p : device_allocations(c)) (void)hipFree(p);
   resolve_timers(c);
   for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->sync_events) if (e) (void)hipEventDestroy(e);
@@ -1642,12 +1655,17 @@ static void launch_view(tse_ctx* c, const ViewPlan& p, const tse_view* v, double
 // Everything a view entry (tse_view_put, tse_view_get, tse_apply_forcing) checks before it enqueues: the plan of the view, nt, null and
 // alignment, the caller's stream (not being captured, on the context's device), the view's memory (device memory of the context's device)
 // and its footprint (inside the allocation that holds ptr).  Returns 0 with the plan in *out, or 1 with the message set, under the name `who`.
+static int view_runtime_checks(tse_ctx* c, const char* who, const char* field, const ViewPlan& p, const tse_view* v, void* stream, void** alloc);
 static int view_checks(tse_ctx* c, const char* who, const char* field, int nt, const tse_view* v, void* stream, bool get, ViewPlan* out) {
   if (!c) return fail("%s: null context", who);
   ViewPlan& p = *out;
   std::string err;
   if (view_plan(field, c->nelemd, c->qsize, v, get, &p, &err)) return fail("%s%s", strcmp(who, "tse_apply_forcing") ? "" : "tse_apply_forcing: ", err.c_str());
   if (p.field == VF_QDP && (nt < 1 || nt > 2)) return fail("%s: nt=%d", who, nt);
+  return view_runtime_checks(c, who, field, p, v, stream, nullptr);
+}
+// the part of view_checks that follows the plan (tse_remap_view makes its own plans); *alloc, if given: the base of the allocation that holds ptr
+static int view_runtime_checks(tse_ctx* c, const char* who, const char* field, const ViewPlan& p, const tse_view* v, void* stream, void** alloc) {
   if (!v->ptr) return fail("%s: null view pointer", who);
   if ((uintptr_t)v->ptr & 7) return fail("%s: the view pointer %p is not 8-byte aligned", who, v->ptr);
   if ((size_t)p.ext[0] * p.ext[1] >= ((size_t)1 << 31)) return fail("%s: %d elements x %d", who, p.ext[0], p.ext[1]);
@@ -1674,6 +1692,7 @@ static int view_checks(tse_ctx* c, const char* who, const char* field, int nt, c
   const __int128 a0 = (__int128)(uintptr_t)abase, a1 = a0 + (__int128)asize, p0 = (__int128)(uintptr_t)v->ptr;
   if (p0 + (__int128)p.lo * 8 < a0 || p0 + (__int128)p.hi * 8 > a1)
     return fail("%s: the view reaches doubles [%lld, %lld) around %p, outside its allocation [%p, +%zu bytes)", who, p.lo, p.hi, v->ptr, (void*)abase, asize);
+  if (alloc) *alloc = (void*)abase;
   return 0;
 }
 
@@ -1806,6 +1825,127 @@ int tse_apply_forcing_host(tse_ctx* c, int nt, double dt, int mode, const double
   return forcing_run(c, who, nt, dt, mode, p, &v, nullptr, budget);   // (null stream: complete on return, the caller may reuse FQ)
 }
 
+// ---- vertical remap of a resident host's own level fields (k_remap_view_check, k_remap_view: tse_kernels.h) ------------------------
+// The plans and the overlap test are host code (tse_views.cpp: remap_view_plan); here the checks that need the runtime, the stream order
+// of tse_view_put and two launches on the compute stream: the check kernel decides per element whether the bracket search can end on the
+// two grids (the test of check_remap_grids, on the device: the grids never visit the host), the remap kernel leaves a refused element alone.
+static constexpr size_t REMAP_VIEW_LDS = sizeof(RemapLds), REMAP_VIEW_LDS_MEAN = sizeof(RemapLds) + sizeof(double) * NLEV * 16;
+template <class F>
+static int with_remap_view(bool alg2, bool mean, bool wide, F&& f) {
+  if (mean) {
+    if (alg2) return wide ? f(k_remap_view<true, true, true>, REMAP_VIEW_LDS_MEAN) : f(k_remap_view<true, true, false>, REMAP_VIEW_LDS_MEAN);
+    return wide ? f(k_remap_view<false, true, true>, REMAP_VIEW_LDS_MEAN) : f(k_remap_view<false, true, false>, REMAP_VIEW_LDS_MEAN);
+  }
+  if (alg2) return wide ? f(k_remap_view<true, false, true>, REMAP_VIEW_LDS) : f(k_remap_view<true, false, false>, REMAP_VIEW_LDS);
+  return wide ? f(k_remap_view<false, false, true>, REMAP_VIEW_LDS) : f(k_remap_view<false, false, false>, REMAP_VIEW_LDS);
+}
+static_assert(REMAP_VIEW_LDS_MEAN <= 160 * 1024, "RemapLds and the target thicknesses of a layer-mean field fit a CU's LDS");
+static int remap_view_buffers(tse_ctx* c) {
+  if (c->rv_acc) return 0;
+  for (int i = 0; i < 8; i++) {   // (the attribute is per kernel and device; set once per context, before the first launch)
+    if (with_remap_view(i & 1, i & 2, i & 4, [](auto kern, size_t lds) -> int {
+          HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+          return 0;
+        })) return 1;
+  }
+  if (dalloc(&c->rv_status, (size_t)c->nelemd * REMAP_STATUS) || dalloc(&c->rv_detail, (size_t)c->nelemd * 2)) return 1;
+  HIPCHK(hipMemset(c->rv_status, 0, (size_t)c->nelemd * REMAP_STATUS * sizeof(int)));
+  unsigned long long* acc = nullptr;
+  if (dalloc(&acc, 2)) return 1;
+  const unsigned long long clear[2] = {0ull, ~0ull};
+  if (hipMemcpy(acc, clear, sizeof clear, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(acc); return fail("tse_remap_view: cannot clear the status"); }
+  c->rv_acc = acc;
+  return 0;
+}
+
+int tse_remap_view(tse_ctx* c, int nf, int mode, int alg, const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, void* stream) {
+  const char* who = "tse_remap_view";
+  if (!c) return fail("%s: null context", who);
+  if (mode != TSE_REMAP_MASS && mode != TSE_REMAP_MEAN) return fail("%s: mode=%d (0: mass per layer, 1: layer mean)", who, mode);
+  if (alg < 0 || alg > 2) return fail("%s: alg=%d (0|1: mirrored ghost cells, 2: piecewise-constant end cells)", who, alg);
+  if (c->nelemd >= (1 << 24)) return fail("%s: %d elements (the status word holds 24 bits of element index)", who, c->nelemd);
+  ViewPlan p[3];
+  { std::string err; if (remap_view_plan(c->nelemd, nf, field, dp_src, dp_tgt, p, &err)) return fail("%s", err.c_str()); }
+  const tse_view* v[3] = {field, dp_src, dp_tgt};
+  const char* name[3] = {"tse_remap_view: field", "tse_remap_view: dp_src", "tse_remap_view: dp_tgt"};
+  bool own_qdp = false;
+  const std::vector<void*> mine = device_allocations(c);
+  for (int i = 0; i < 3; i++) {
+    void* alloc = nullptr;
+    if (view_runtime_checks(c, name[i], i == 0 ? "qdp" : "dp", p[i], v[i], stream, &alloc)) return 1;
+    if (std::find(mine.begin(), mine.end(), alloc) == mine.end()) continue;
+    // the library's own memory: only its Qdp, and only as the field (a host with real dynamics remaps the engine's tracers on its own grids)
+    if (i == 0 && (alloc == c->q(1) || alloc == c->q(2))) own_qdp = true;
+    else return fail("%s: %p lies inside an allocation of the library that is not qdp1 or qdp2 (or is not the field); the call works on the host's own arrays", name[i], v[i]->ptr);
+  }
+  { std::string err; if (remap_view_overlap(field, dp_src, dp_tgt, p, &err)) return fail("%s", err.c_str()); }
+  if (remap_view_buffers(c)) return 1;
+  hipStream_t us = (hipStream_t)stream;
+  if (us && !c->view_ev[0])
+    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+
+  RemapViewArgs a;
+  a.field = (double*)field->ptr; a.src = (const double*)dp_src->ptr; a.tgt = (const double*)dp_tgt->ptr;
+  for (int k = 0; k < 5; k++) { a.fs[k] = field->stride[k]; a.ss[k] = dp_src->stride[k]; a.ts[k] = dp_tgt->stride[k]; }
+  a.spath = p[1].path; a.tpath = p[2].path;
+  // level-fastest rows whose chunks of CL levels are 16-byte aligned in every column: k_view_levels' WIDE rule
+  const long long* s = field->stride;
+  const bool wide = p[0].path == 1 && ((uintptr_t)field->ptr & 15) == 0 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
+  const bool mean = mode == TSE_REMAP_MEAN;
+
+  if (own_qdp) set_bounds_cache(c, 0);   // the side effects of tse_copy_qdp_h2d
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
+  {
+    Scope sc(c, "fieldremap");
+    hipLaunchKernelGGL(k_remap_view_check<>, dim3(c->nelemd), dim3(REMAP_CHECK_THREADS), 0, c->stream, a, (int)mean, c->rv_status, c->rv_detail,
+                       us ? c->rv_acc : (unsigned long long*)nullptr, c->rv_seq & 0xffffffu);
+    with_remap_view(alg == 2, mean, wide, [&](auto kern, size_t lds) -> int {
+      hipLaunchKernelGGL(kern, dim3(c->nelemd), dim3(REMAP_THREADS), lds, c->stream, nf, a, (const int*)c->rv_status);
+      return 0;
+    });
+    LAUNCH_CHECK();
+  }
+  if (us) {
+    c->rv_seq++;
+    HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0));
+    return 0;
+  }
+  // complete on return: the verdicts come back, the lowest refused element is named
+  std::vector<int> st((size_t)c->nelemd * REMAP_STATUS);
+  HIPCHK(hipMemcpyAsync(st.data(), c->rv_status, st.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  int nref = 0, first = -1;
+  for (int e = 0; e < c->nelemd; e++)
+    if (st[(size_t)e * REMAP_STATUS]) { nref++; if (first < 0) first = e; }
+  if (!nref) return 0;
+  double det[2];
+  HIPCHK(hipMemcpy(det, c->rv_detail + (size_t)first * 2, sizeof det, hipMemcpyDeviceToHost));
+  RemapGridFault f;
+  f.code = st[(size_t)first * REMAP_STATUS]; f.level = st[(size_t)first * REMAP_STATUS + 2]; f.has_limit = st[(size_t)first * REMAP_STATUS + 3];
+  f.value = det[0]; f.limit = det[1];
+  fail("%s: %d of %d elements refused and left as they were; the first: %s", who, nref, c->nelemd,
+       remap_grid_message(first, st[(size_t)first * REMAP_STATUS + 1], f, mean).c_str());
+  return 2;
+}
+
+int tse_remap_view_status(tse_ctx* c, int* nrefused, int where[4]) {
+  if (!c) return fail("tse_remap_view_status: null context");
+  if (nrefused) *nrefused = 0;
+  if (where) where[0] = where[1] = where[2] = where[3] = 0;
+  if (!c->rv_acc) return 0;   // no tse_remap_view yet
+  HIPCHK(hipStreamSynchronize(c->stream));
+  unsigned long long acc[2] = {0ull, ~0ull};
+  HIPCHK(hipMemcpy(acc, c->rv_acc, sizeof acc, hipMemcpyDeviceToHost));
+  if (acc[0]) {
+    const unsigned long long clear[2] = {0ull, ~0ull};
+    HIPCHK(hipMemcpy(c->rv_acc, clear, sizeof clear, hipMemcpyHostToDevice));
+    if (nrefused) *nrefused = (int)std::min<unsigned long long>(acc[0], 0x7fffffffull);
+    if (where) { where[0] = (int)((acc[1] >> 16) & 0xffffffull); where[1] = (int)((acc[1] >> 12) & 15ull); where[2] = (int)((acc[1] >> 4) & 255ull); where[3] = (int)(acc[1] & 15ull); }
+  }
+  c->rv_seq = 0;
+  return 0;
+}
+
 // ---- introspection ------------------------------------------------------------------------------
 void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   struct Ent { const char* n; void* p; size_t b; };
@@ -1816,7 +1956,7 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
                 {"omega_p", c->omega_p, lev}, {"dp3d", c->dp3d, lev}, {"ps_v", c->ps_v, (size_t)c->nelemd * 16 * 8}, {"q", c->qmix, trc}, {"lnps", c->lnps, (size_t)c->nelemd * 16 * 8}, {"qref", c->qref, lev}, {"qmin", c->qmin, mm},
                 {"qmax", c->qmax, mm}, {"sendbuf", c->sendbuf, (size_t)c->ncol_send * c->nlyr_halo * 8},
                 {"recvbuf", c->recvbuf, (size_t)c->ncol_recv * c->nlyr_halo * 8}, {"sendbuf_mm", c->sendbuf_mm, (size_t)c->nmm_send * m2},
-                {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}};
+                {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}, {"remap_status", c->rv_status, (size_t)c->nelemd * REMAP_STATUS * sizeof(int)}};
   for (auto& e : ents) if (!strcmp(e.n, name)) { if (nbytes) *nbytes = e.p ? e.b : 0; return e.p; }
   if (nbytes) *nbytes = 0;
   return nullptr;

@@ -18,6 +18,7 @@
 #pragma once
 #include <type_traits>
 #include "tse_device.h"
+#include "tse_remap_check.h"
 
 namespace tse {
 
@@ -1969,6 +1970,35 @@ __device__ __forceinline__ void remap_columns_fast(const RemapLds& S, double* __
 
 #pragma clang fp contract(fast)   // (the default of the rest of the file)
 
+// Phase 1b of the remap kernels (k_remap, k_remap_view): the grid coefficients (compute_ppm_grids, :221-260) in the folded form the
+// column loops use, one (j,p) per work item, from the old thicknesses dpo that phase 1a left in S.dsel (index j+1, ghost rows filled).
+// All threads of the block, between two barriers of the caller.  One text for both kernels: what the compiler contracts here is part
+// of the result.
+__device__ __forceinline__ void remap_grid_coefs(RemapLds& S, int tid, int nthreads) {
+  double (*const dpo)[16] = S.dsel;
+  for (int w = tid; w < (NLEV + 4) * 16; w += nthreads) S.rdpo[w >> 4][w & 15] = 1.0 / dpo[w >> 4][w & 15];
+  for (int w = tid; w < (NLEV + 2) * 16; w += nthreads) {
+    const int jj = w >> 4, p = w & 15;  // jj = j, j = 0..NLEV+1
+#define DX(j) dpo[(j) + 1][p]
+    const double c1 = DX(jj) / (DX(jj - 1) + DX(jj) + DX(jj + 1));
+    S.cd[jj][0][p] = c1 * ((2. * DX(jj - 1) + DX(jj)) / (DX(jj + 1) + DX(jj)));
+    S.cd[jj][1][p] = c1 * ((DX(jj) + 2. * DX(jj + 1)) / (DX(jj - 1) + DX(jj)));
+    if (jj <= NLEV) {
+      const double c4 = DX(jj) / (DX(jj) + DX(jj + 1));
+      const double c5 = 1. / (DX(jj - 1) + DX(jj) + DX(jj + 1) + DX(jj + 2));
+      // (:255-257) c6*(c7 - c8), evaluated as the reference does (left to right)
+      const double c678 = ((2. * DX(jj + 1) * DX(jj)) / (DX(jj) + DX(jj + 1))) *
+                          ((DX(jj - 1) + DX(jj)) / (2. * DX(jj) + DX(jj + 1)) - (DX(jj + 2) + DX(jj + 1)) / (2. * DX(jj + 1) + DX(jj)));
+      const double c9 = DX(jj) * (DX(jj - 1) + DX(jj)) / (2. * DX(jj) + DX(jj + 1));
+      const double c10 = DX(jj + 1) * (DX(jj + 1) + DX(jj + 2)) / (DX(jj) + 2. * DX(jj + 1));
+      S.ca[jj][0][p] = c4 + c5 * c678;
+      S.ca[jj][1][p] = c5 * c9;
+      S.ca[jj][2][p] = c5 * c10;
+    }
+#undef DX
+  }
+}
+
 template <int NT, bool ALG2 = false, bool FUSED = false>
 __global__ __launch_bounds__(REMAP_THREADS / NT, NT == 1 ? REMAP_PER_CU : 1 /* <= 256 registers: two blocks per CU (80 levels: one) */) void k_remap(
     int qsize, double dt, double ps0, const double* __restrict__ hyai, const double* __restrict__ hybi, const double* __restrict__ dp,
@@ -2082,28 +2112,8 @@ __global__ __launch_bounds__(REMAP_THREADS / NT, NT == 1 ? REMAP_PER_CU : 1 /* <
     S.z2[k - 1][p] = (pin_k1 - (pio[kk - 1][p] + pio[kk][p]) * 0.5) / dpo[kk + 1][p];
   }
   __syncthreads();   // pio, dA, dB are dead: the coefficients go where they were
-  // ---- phase 1b: grid coefficients (compute_ppm_grids, :221-260) in the folded form the column loop uses, one (j,p) per work item
-  for (int w = tid; w < (NLEV + 4) * 16; w += nthreads) S.rdpo[w >> 4][w & 15] = 1.0 / dpo[w >> 4][w & 15];
-  for (int w = tid; w < (NLEV + 2) * 16; w += nthreads) {
-    const int jj = w >> 4, p = w & 15;  // jj = j, j = 0..NLEV+1
-#define DX(j) dpo[(j) + 1][p]
-    const double c1 = DX(jj) / (DX(jj - 1) + DX(jj) + DX(jj + 1));
-    S.cd[jj][0][p] = c1 * ((2. * DX(jj - 1) + DX(jj)) / (DX(jj + 1) + DX(jj)));
-    S.cd[jj][1][p] = c1 * ((DX(jj) + 2. * DX(jj + 1)) / (DX(jj - 1) + DX(jj)));
-    if (jj <= NLEV) {
-      const double c4 = DX(jj) / (DX(jj) + DX(jj + 1));
-      const double c5 = 1. / (DX(jj - 1) + DX(jj) + DX(jj + 1) + DX(jj + 2));
-      // (:255-257) c6*(c7 - c8), evaluated as the reference does (left to right)
-      const double c678 = ((2. * DX(jj + 1) * DX(jj)) / (DX(jj) + DX(jj + 1))) *
-                          ((DX(jj - 1) + DX(jj)) / (2. * DX(jj) + DX(jj + 1)) - (DX(jj + 2) + DX(jj + 1)) / (2. * DX(jj + 1) + DX(jj)));
-      const double c9 = DX(jj) * (DX(jj - 1) + DX(jj)) / (2. * DX(jj) + DX(jj + 1));
-      const double c10 = DX(jj + 1) * (DX(jj + 1) + DX(jj + 2)) / (DX(jj) + 2. * DX(jj + 1));
-      S.ca[jj][0][p] = c4 + c5 * c678;
-      S.ca[jj][1][p] = c5 * c9;
-      S.ca[jj][2][p] = c5 * c10;
-    }
-#undef DX
-  }
+  // ---- phase 1b: grid coefficients (compute_ppm_grids, :221-260) in the folded form the column loop uses
+  remap_grid_coefs(S, tid, nthreads);
   __syncthreads();
   // ---- phase 2: data part
   if (S.slow) {
@@ -2588,6 +2598,200 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_forcing(int nq, long long vs_e
       budget[((size_t)e * nq + q) * 2 + tid] = a;
     }
   }
+}
+
+// ---- remap of a host's own level fields through strided views (tse_remap_view) ---------------------------------------------------
+// remap_Q_ppm(field, np, nf, dp_src, dp_tgt) for every element, in place in the host's own device array, on the host's own two grids.
+// All three arrays are strided views (strides in doubles for element, q, level, j, i; the two grids have no q axis).  Nothing of the
+// library's state is read or written.
+struct RemapViewArgs {
+  double* field;
+  const double *src, *tgt;
+  long long fs[5], ss[5], ts[5];
+  int spath, tpath;   // path of tse_view_plan of the two grids (1: a block reads along the levels of a row)
+};
+constexpr int REMAP_STATUS = 4;   // ints per element of the status array: code (RemapGridCode), column, level, whether detail holds a limit
+
+// The precondition of the bracket search, decided on the device (the grids of a resident host never reach the host): block = element,
+// lane p < 16 runs remap_column_check (tse_remap_check.h: two loops of NLEV trips, no search) on column p, lane 0 takes the lowest
+// column that offends -- check_remap_grids' order -- and writes status[e] = {code, column, level, has_limit} and detail[e] = {value, limit}.
+// acc (null: a call that reports on return): acc[0] += 1 per refused element, acc[1] = min over them of
+// seq << 40 | e << 16 | column << 12 | level << 4 | code, i.e. the lowest element of the earliest call (seq) not read yet.
+constexpr int REMAP_CHECK_THREADS = 64;
+template <int = 0>   // (a template: the header is included by two translation units)
+__global__ __launch_bounds__(REMAP_CHECK_THREADS) void k_remap_view_check(RemapViewArgs a, int mean, int* __restrict__ status, double* __restrict__ detail,
+                                                                          unsigned long long* __restrict__ acc, unsigned seq) {
+  __shared__ int code[16], lev[16], hasl[16];
+  __shared__ double val[16], lim[16];
+  const long long e = blockIdx.x;
+  const int p = threadIdx.x;
+  if (p < 16) {
+    RemapGridFault f;
+    remap_column_check(a.src + e * a.ss[0] + (p >> 2) * a.ss[3] + (p & 3) * a.ss[4], a.ss[2],
+                       a.tgt + e * a.ts[0] + (p >> 2) * a.ts[3] + (p & 3) * a.ts[4], a.ts[2], NLEV, mean != 0, &f);
+    code[p] = f.code; lev[p] = f.level; hasl[p] = f.has_limit; val[p] = f.value; lim[p] = f.limit;
+  }
+  __syncthreads();
+  if (p == 0) {
+    int c = 0;
+    while (c < 15 && code[c] == 0) c++;
+    int* st = status + e * REMAP_STATUS;
+    st[0] = code[c]; st[1] = code[c] ? c : 0; st[2] = code[c] ? lev[c] : 0; st[3] = code[c] ? hasl[c] : 0;
+    detail[e * 2] = val[c]; detail[e * 2 + 1] = lim[c];
+    if (code[c] && acc) {
+      atomicAdd(acc, 1ull);
+      atomicMin(acc + 1, (unsigned long long)seq << 40 | (unsigned long long)e << 16 | (unsigned long long)c << 12 | (unsigned long long)lev[c] << 4 |
+                             (unsigned long long)code[c]);
+    }
+  }
+}
+
+// The column loop of remap_columns_generic (any kid(k) >= k - 1; the same operations in the same order: the same bits) on a column that
+// is addressed through the view: col = the column's first level, sk = its level stride.  Thread = (field slot f, point p).
+//   point-fastest view  the 16 lanes of a slot read one 128-byte line per level (sk = the level stride);
+//   level-fastest view  a lane walks along its own row; WIDE (view base 16-byte aligned; even element, q and point strides): the CL = 4
+//                       levels of a chunk are two 16-byte loads and, on the way back, two 16-byte stores; otherwise 8 bytes per level;
+//   any other strides   one address per entry (the same code as point-fastest: only the strides differ).
+// Loads run REMAP_PF levels ahead (WIDE: four to eight), as in the generic loop; a cell is stored after it has been consumed (kid(k) >=
+// k - 1: by level k the window has taken cell k + 1), so the field is remapped in place.
+// MEAN: the field holds layer means a.  m = a * dp_src as the cell is consumed (one product; S.dsel holds dp_src), the mass arithmetic
+// unchanged, a' = m' / dp_tgt (a true division; dpt holds dp_tgt) as it is stored.
+#pragma clang fp contract(off)
+template <bool ALG2, bool MEAN, bool WIDE>
+__device__ __forceinline__ void remap_columns_view(const RemapLds& S, const double (*__restrict__ dpt)[16], double* __restrict__ col, long long sk, int p) {
+  int R = 0;                                   // highest cell consumed so far (ghost cells continue past NLEV)
+  double pf[REMAP_PF];
+  if (WIDE) {
+#pragma unroll
+    for (int t = 0; t < REMAP_PF; t += 2) { const double2 v = *reinterpret_cast<const double2*>(col + t); pf[t] = v.x; pf[t + 1] = v.y; }
+  } else {
+#pragma unroll
+    for (int t = 0; t < REMAP_PF; t++) pf[t] = col[t * sk];
+  }
+  double pm1 = 0, pa1 = 0, pm2 = 0, pa2 = 0;   // the last two real cells (mass, mean) for the bottom mirror
+#define TSE_READ_NEXT(m_, a_)                                                                          \
+  do {                                                                                                 \
+    R++;                                                                                               \
+    if (R <= NLEV) {                                                                                   \
+      m_ = MEAN ? pf[0] * S.dsel[R + 1][p] : pf[0];                                                    \
+      _Pragma("unroll") for (int t = 0; t + 1 < REMAP_PF; t++) pf[t] = pf[t + 1];                      \
+      if (WIDE) {                                                                                      \
+        if ((R & (CL - 1)) == 0 && R + REMAP_PF <= NLEV) { /* cells R+5 .. R+8: the FIFO's upper half */ \
+          const double2 v0 = *reinterpret_cast<const double2*>(col + R + CL);                          \
+          const double2 v1 = *reinterpret_cast<const double2*>(col + R + CL + 2);                      \
+          pf[CL] = v0.x; pf[CL + 1] = v0.y; pf[CL + 2] = v1.x; pf[CL + 3] = v1.y;                      \
+        }                                                                                              \
+      } else if (R + REMAP_PF <= NLEV) pf[REMAP_PF - 1] = col[(long long)(R + REMAP_PF - 1) * sk];     \
+      a_ = m_ * S.rdpo[R + 1][p];                                                                      \
+      pm2 = pm1; pa2 = pa1; pm1 = m_; pa1 = a_;                                                        \
+    } else if (R == NLEV + 1) { m_ = pm1; a_ = pa1; } /* a(nlev+1) = a(nlev)   */                      \
+    else { m_ = pm2; a_ = pa2; }                      /* a(nlev+2) = a(nlev-1) */                      \
+  } while (0)
+  double m1, a1, m2, a2, m3, a3;
+  TSE_READ_NEXT(m1, a1); TSE_READ_NEXT(m2, a2); TSE_READ_NEXT(m3, a3);
+  int kk = 1;
+  double am2 = a2, am1 = a1, a0 = a1, ap1 = a2, ap2 = a3;  // a(-1)=a(2), a(0)=a(1)
+  double m0 = m1, mp1 = m2, mp2 = m3;
+  double dma_m1 = remap_dma_at(S, 0, p, am2, am1, a0), dma_0 = remap_dma_at(S, 1, p, am1, a0, ap1), dma_p1 = remap_dma_at(S, 2, p, a0, ap1, ap2);
+  double ai_m1 = remap_ai_at(S, 0, p, am1, a0, dma_0, dma_m1), ai_0 = remap_ai_at(S, 1, p, a0, ap1, dma_p1, dma_0);
+  double masso_kk = 0.0, massn1 = 0.0;
+  double c0, c1, c2;
+  remap_coefs(ai_m1, ai_0, a0, c0, c1, c2);
+  ppm_alg2<ALG2>(kk, a0, c0, c1, c2);
+  static_assert(REMAP_PF == 2 * CL && NLEV % CL == 0, "WIDE: the FIFO is two chunks of CL levels, a column whole chunks");
+  for (int k0 = 1; k0 <= NLEV; k0 += CL) {
+    double out[CL];
+#pragma unroll
+    for (int i = 0; i < CL; i++) {
+      const int k = k0 + i;
+      const int kt = S.kid[k - 1][p];   // <= NLEV: the window advances by at most NLEV - 1 cells per column
+      while (kk < kt) {
+        masso_kk = masso_kk + m0;
+        am2 = am1; am1 = a0; a0 = ap1; ap1 = ap2; m0 = mp1; mp1 = mp2;
+        TSE_READ_NEXT(mp2, ap2);
+        kk++;
+        dma_m1 = dma_0; dma_0 = dma_p1; dma_p1 = remap_dma_at(S, kk + 1, p, a0, ap1, ap2);
+        ai_m1 = ai_0; ai_0 = remap_ai_at(S, kk, p, a0, ap1, dma_p1, dma_0);
+        remap_coefs(ai_m1, ai_0, a0, c0, c1, c2);
+        ppm_alg2<ALG2>(kk, a0, c0, c1, c2);
+      }
+      double z1, zz2, z3;
+      ppm_zterms(S.z2[k - 1][p], z1, zz2, z3);
+      const double massn2 = fma(ppm_integ(c0, c1, c2, z1, zz2, z3), S.dsel[kk + 1][p] /* = dpo(kk) */, masso_kk);
+      const double qnew = massn2 - massn1;
+      massn1 = massn2;
+      out[i] = MEAN ? qnew / dpt[k - 1][p] : qnew;
+      if (!WIDE) col[(long long)(k - 1) * sk] = out[i];
+    }
+    if (WIDE) {
+      *reinterpret_cast<double2*>(col + k0 - 1) = make_double2(out[0], out[1]);
+      *reinterpret_cast<double2*>(col + k0 + 1) = make_double2(out[2], out[3]);
+    }
+  }
+#undef TSE_READ_NEXT
+}
+#pragma clang fp contract(fast)
+
+// One block per element, RemapLds as in k_remap: phase 1a (thicknesses through the views, the serial interface sums on 16 lanes), the
+// bracket search, phase 1b (remap_grid_coefs), then remap_columns_view on every (field slot, point).  No bounds, no dp3d / ps_v / bad, no
+// DSS on read.  An element the check kernel refused (status) is left by the WHOLE block before the first barrier and before any search:
+// its field keeps every bit.  The search is bounded besides: pio has NLEV + 2 rows.
+// Dynamic LDS: RemapLds, and for MEAN behind it dpt[NLEV][16], the target thicknesses the new masses are divided by.
+template <bool ALG2, bool MEAN, bool WIDE>
+__global__ __launch_bounds__(REMAP_THREADS) void k_remap_view(int nf, RemapViewArgs a, const int* __restrict__ status) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  RemapLds& S = *reinterpret_cast<RemapLds*>(smem_raw);
+  double (*const dpt)[16] = reinterpret_cast<double (*)[16]>(smem_raw + sizeof(RemapLds));   // MEAN only
+  const long long e = blockIdx.x;
+  if (status[e * REMAP_STATUS] != 0) return;   // (uniform over the block)
+  const int tid = threadIdx.x, nthreads = blockDim.x;
+  double (*const pio)[16] = S.pio();
+  double (*const dpo)[16] = S.dsel;
+  double (*const tgt)[16] = S.rdpo;   // phase 1a parks dp_tgt (index k) where phase 1b puts 1/dpo
+  // ---- phase 1a: the two grids through their views; a level-fastest view is read along its rows
+  for (int w = tid; w < NLEV * 16; w += nthreads) {
+    const int ks = a.spath == 1 ? w % NLEV : w >> 4, ps = a.spath == 1 ? w / NLEV : w & 15;
+    dpo[ks + 2][ps] = a.src[e * a.ss[0] + ks * a.ss[2] + (ps >> 2) * a.ss[3] + (ps & 3) * a.ss[4]];
+    const int kt = a.tpath == 1 ? w % NLEV : w >> 4, pt = a.tpath == 1 ? w / NLEV : w & 15;
+    const double d = a.tgt[e * a.ts[0] + kt * a.ts[2] + (pt >> 2) * a.ts[3] + (pt & 3) * a.ts[4]];
+    tgt[kt][pt] = d;
+    if (MEAN) dpt[kt][pt] = d;
+  }
+  __syncthreads();
+  if (tid < 16) {   // the serial sums of k_remap's phase 1a (their roundings are part of the result)
+    const int p = tid;
+    double run = 0.0;
+    pio[0][p] = 0.0;
+    for (int k = 0; k < NLEV; k++) { run = run + dpo[k + 2][p]; pio[k + 1][p] = run; }
+    const double pio_prev = run;
+    pio[NLEV + 1][p] = pio_prev + 1.;
+    for (int k = 1; k <= 2; k++) { dpo[2 - k][p] = dpo[k + 1][p]; dpo[NLEV + k + 1][p] = dpo[NLEV + 2 - k][p]; }
+    double pin = 0.0;
+    for (int k = 1; k <= NLEV; k++) {
+      pin = pin + tgt[k - 1][p];
+      S.z2[k - 1][p] = (k == NLEV) ? pio_prev : pin;  // pin(nlev+1) = pio(nlev+1)
+    }
+  }
+  __syncthreads();
+  // bracket search (:160-172), one (k,p) per work item; ends at pio(nlev+2) = pio(nlev+1) + 1 at the latest on a grid that passed the
+  // check, and at the last row of pio on any other
+  for (int w = tid; w < NLEV * 16; w += nthreads) {
+    const int k = (w >> 4) + 1, p = w & 15;
+    const double pin_k1 = S.z2[k - 1][p];
+    int kk = k;
+    while (kk < NLEV + 2 && pio[kk - 1][p] <= pin_k1) kk++;
+    kk--;
+    if (kk == NLEV + 1) kk = NLEV;
+    S.kid[k - 1][p] = (unsigned char)kk;
+    S.z2[k - 1][p] = (pin_k1 - (pio[kk - 1][p] + pio[kk][p]) * 0.5) / dpo[kk + 1][p];
+  }
+  __syncthreads();   // pio and the parked dp_tgt are dead: the coefficients go where they were
+  remap_grid_coefs(S, tid, nthreads);
+  __syncthreads();
+  // ---- phase 2
+  const int p = tid & 15;
+  double* const base = a.field + e * a.fs[0] + (p >> 2) * a.fs[3] + (p & 3) * a.fs[4];
+  for (int f = tid >> 4; f < nf; f += nthreads >> 4) remap_columns_view<ALG2, MEAN, WIDE>(S, dpt, base + f * a.fs[1], a.fs[2], p);
 }
 
 }  // namespace tse

@@ -439,35 +439,34 @@ int build_tables(const tse_init_args& a, bool strips, HostTables* out, std::stri
   return 0;
 }
 
+// the wording of a column fault (tse_remap_check.h), for check_remap_grids and for the device-side check of tse_remap_view
+std::string remap_grid_message(int e, int p, const RemapGridFault& f, bool mean) {
+  const char* what = "";
+  switch (f.code) {
+    case REMAP_GRID_SRC: what = "dp1 is not a finite positive number: dp1"; break;
+    case REMAP_GRID_SRC_SUM:
+      what = f.has_limit ? "sum(dp1) is so large that sum(dp1) + 1 == sum(dp1), the search of the last level cannot end: sum(dp1)"
+                                : "sum(dp1) is not finite: sum(dp1)";
+      break;
+    case REMAP_GRID_TGT: what = mean ? "dp2 is zero, negative or not finite (a layer mean is divided by it): dp2" : "dp2 is negative or not finite: dp2"; break;
+    case REMAP_GRID_TGT_SUM: what = "the target grid leaves the source column: partial sum of dp2"; break;
+  }
+  // Every message ends on the limit, "nan" where the fault has none: the text check_remap_grids has always produced (its `lim == lim`
+  // was compiled away under -fno-honor-nans), kept to the letter because callers match on it.
+  std::string msg;
+  fail(&msg, "%s = %.17g at element %d, column %d, level %d (counted from 0); sum(dp1) + 1 = %.17g", what, f.value, e, p, f.level,
+       f.has_limit ? f.limit : std::nan(""));
+  return msg;
+}
+
 int check_remap_grids(const double* dp1, const double* dp2, int nelem, int nlev, int* where, std::string* err) {
   if (!dp1 || !dp2 || nelem < 0 || nlev < 1) return fail(err, "remap grids: null argument or bad size (nelem = %d, nlev = %d)", nelem, nlev);
-  auto bad = [&](int e, int p, int k, const char* what, double v, double lim) {
-    if (where) { where[0] = e; where[1] = p; where[2] = k; }
-    if (lim == lim) return fail(err, "%s = %.17g at element %d, column %d, level %d (counted from 0); sum(dp1) + 1 = %.17g", what, v, e, p, k, lim);
-    return fail(err, "%s = %.17g at element %d, column %d, level %d (counted from 0)", what, v, e, p, k);
-  };
-  const double nan = std::nan("");
   for (int e = 0; e < nelem; e++)
     for (int p = 0; p < 16; p++) {
-      const double* c1 = dp1 + (size_t)e * nlev * 16 + p;
-      const double* c2 = dp2 + (size_t)e * nlev * 16 + p;
-      double pio = 0.0;   // the kernel's serial sums (phase 1a)
-      for (int k = 0; k < nlev; k++) {
-        const double d = c1[(size_t)k * 16];
-        if (!(d > 0.0) || !std::isfinite(d)) return bad(e, p, k, "dp1 is not a finite positive number: dp1", d, nan);
-        pio = pio + d;
-      }
-      if (!std::isfinite(pio)) return bad(e, p, nlev - 1, "sum(dp1) is not finite: sum(dp1)", pio, nan);
-      const double end = pio + 1.0;   // pio(nlev+2)
-      // the sentinel must lie above the column: the search of the LAST level compares pin(nlev+1) = pio(nlev+1) with it, and from
-      // sum(dp1) = 2^53 on the + 1 is absorbed (pio(nlev+2) == pio(nlev+1)) and that search would not end either
-      if (!(end > pio)) return bad(e, p, nlev - 1, "sum(dp1) is so large that sum(dp1) + 1 == sum(dp1), the search of the last level cannot end: sum(dp1)", pio, end);
-      double pin = 0.0;
-      for (int k = 0; k < nlev; k++) {
-        const double d = c2[(size_t)k * 16];
-        if (!(d >= 0.0) || !std::isfinite(d)) return bad(e, p, k, "dp2 is negative or not finite: dp2", d, nan);
-        pin = pin + d;
-        if (k + 1 < nlev && !(pin < end)) return bad(e, p, k, "the target grid leaves the source column: partial sum of dp2", pin, end);
+      RemapGridFault f;   // the column test itself is shared with the device (tse_remap_check.h)
+      if (remap_column_check(dp1 + (size_t)e * nlev * 16 + p, 16, dp2 + (size_t)e * nlev * 16 + p, 16, nlev, false, &f)) {
+        if (where) { where[0] = e; where[1] = p; where[2] = f.level; }
+        return fail(err, "%s", remap_grid_message(e, p, f, false).c_str());
       }
     }
   return 0;

@@ -8,6 +8,7 @@
 
 #include "../../include/transport_se_hip.h"
 #include "tse_layout.h"
+#include "tse_remap_check.h"
 
 namespace tse {
 
@@ -60,6 +61,9 @@ int build_tables(const tse_init_args& a, bool strips, HostTables* out, std::stri
 // sum(dp1), a dp2 that is negative or not finite, a partial sum of dp2 below the last level that is >= sum(dp1) + 1 (both in fp64).
 // Returns 0, or 1 with the first offender in scan order (element, then column, then level; all counted from 0) in where[3] (if
 // given) and in *err.
+// The test of one column is remap_column_check (tse_remap_check.h), which the device runs too (tse_remap_view).
 int check_remap_grids(const double* dp1, const double* dp2, int nelem, int nlev, int* where, std::string* err);
+// the message of a column fault in check_remap_grids' wording (mean: the zero target layer a layer-mean field refuses)
+std::string remap_grid_message(int e, int p, const RemapGridFault& f, bool mean);
 
 }  // namespace tse

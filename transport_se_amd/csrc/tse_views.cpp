@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 
@@ -100,6 +101,36 @@ int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool 
   return 0;
 }
 
+// tse_remap_view's three views: `field` a "qdp" get view of nf tracer slots (written in place: no zero stride, no two index tuples on one
+// address), dp_src and dp_tgt "dp" put views (a zero stride broadcasts).  remap_view_overlap: the field's footprint, taken from its ptr,
+// may meet neither grid's -- the kernel reads the grids of an element while it writes the element's field.
+int remap_view_plan(int nelemd, int nf, const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, ViewPlan out[3], std::string* err) {
+  const char* who = "tse_remap_view";
+  if (!field || !dp_src || !dp_tgt || !out) return refuse(err, "%s: null view", who);
+  if (nf < 1) return refuse(err, "%s: nf = %d (at least one field)", who, nf);
+  const tse_view* v[3] = {field, dp_src, dp_tgt};
+  const char* name[3] = {"field", "dp_src", "dp_tgt"};
+  for (int i = 0; i < 3; i++) {
+    std::string e;
+    if (view_plan(i == 0 ? "qdp" : "dp", nelemd, nf, v[i], i == 0, &out[i], &e)) return refuse(err, "%s: %s: %s", who, name[i], e.c_str());
+  }
+  return 0;
+}
+
+int remap_view_overlap(const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, const ViewPlan out[3], std::string* err) {
+  const char* who = "tse_remap_view";
+  const tse_view* v[3] = {field, dp_src, dp_tgt};
+  const char* name[3] = {"field", "dp_src", "dp_tgt"};
+  const __int128 f0 = (__int128)(uintptr_t)field->ptr + (__int128)out[0].lo * 8, f1 = (__int128)(uintptr_t)field->ptr + (__int128)out[0].hi * 8;
+  for (int i = 1; i < 3; i++) {
+    const __int128 g0 = (__int128)(uintptr_t)v[i]->ptr + (__int128)out[i].lo * 8, g1 = (__int128)(uintptr_t)v[i]->ptr + (__int128)out[i].hi * 8;
+    if (f0 < g1 && g0 < f1)
+      return refuse(err, "%s: the field [%p%+lld, %p%+lld doubles) overlaps %s [%p%+lld, %p%+lld doubles): it is remapped in place while the grids are read", who,
+                    field->ptr, out[0].lo, field->ptr, out[0].hi, name[i], v[i]->ptr, out[i].lo, v[i]->ptr, out[i].hi);
+  }
+  return 0;
+}
+
 }  // namespace tse
 
 extern "C" int tse_view_plan(const char* field, int nelemd, int qsize, const tse_view* v, int for_get, int* path, long long* lo, long long* hi) {
@@ -109,5 +140,20 @@ extern "C" int tse_view_plan(const char* field, int nelemd, int qsize, const tse
   if (path) *path = p.path;
   if (lo) *lo = p.lo;
   if (hi) *hi = p.hi;
+  return 0;
+}
+
+extern "C" int tse_remap_view_plan(int nelemd, int nf, const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, int path[3], long long lo[3],
+                                   long long hi[3]) {
+  tse::ViewPlan p[3];
+  std::string err;
+  if (tse::remap_view_plan(nelemd, nf, field, dp_src, dp_tgt, p, &err)) return tse::set_last_error(err.c_str());
+  // strides alone (all three ptr null): nothing is known of where the views lie
+  if ((field->ptr || dp_src->ptr || dp_tgt->ptr) && tse::remap_view_overlap(field, dp_src, dp_tgt, p, &err)) return tse::set_last_error(err.c_str());
+  for (int i = 0; i < 3; i++) {
+    if (path) path[i] = p[i].path;
+    if (lo) lo[i] = p[i].lo;
+    if (hi) hi[i] = p[i].hi;
+  }
   return 0;
 }

@@ -24,6 +24,12 @@ struct ViewPlan {
 // Returns 0, or 1 with the reason in *err (a refused axis is named).
 int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool for_get, ViewPlan* out, std::string* err);
 
+// The three views of tse_remap_view / tse_remap_view_plan -> out[0..2] = the plans of field, dp_src, dp_tgt.  Everything that needs no device:
+// nf, the extent rules of a "qdp" get view with nf tracer slots and of two "dp" put views (remap_view_plan), and that the field's footprint
+// meets neither grid's (remap_view_overlap, on the plans; tse_remap_view makes it after each footprint is known to lie in its allocation).
+int remap_view_plan(int nelemd, int nf, const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, ViewPlan out[3], std::string* err);
+int remap_view_overlap(const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, const ViewPlan plan[3], std::string* err);
+
 // the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
 int set_last_error(const char* msg);
 

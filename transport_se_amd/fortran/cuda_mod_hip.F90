@@ -52,6 +52,11 @@ module cuda_mod
   ! below zero, from a device array (apply_forcing_hip) or from elem(:)%derived%FQ in host memory (apply_forcing_elem_hip)
   public :: apply_forcing_hip, apply_forcing_elem_hip
   integer, parameter, public :: forcing_tendency = 0, forcing_adjust = 1   ! TSE_FORCING_TENDENCY, TSE_FORCING_ADJUST
+  ! vertical remap of the host's own level fields on its own grids (INTEGRATION.md section 2g): remap_Q_ppm in place in a device array
+  public :: remap_view_hip, remap_view_status_hip
+  integer, parameter, public :: remap_mass = 0, remap_mean = 1   ! TSE_REMAP_MASS, TSE_REMAP_MEAN
+  logical, save :: remap_refused = .false.            ! remap_view_hip / remap_view_status_hip: the master thread's answer, read by every thread
+  integer(c_int), save :: remap_nrefused = 0, remap_where(4) = 0
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
   integer(c_int), save :: res_nstep = 0   ! the library's step count after the last prim_run_subcycle_hip
   integer(kind=8), save :: t_c0
@@ -187,6 +192,13 @@ module cuda_mod
           bind(C, name='tse_apply_forcing_host')
        import; type(c_ptr), value :: ctx, fq_elem1, budget; integer(c_int), value :: nt, mode, qsize_d; real(c_double), value :: dt
        integer(c_size_t), value :: elem_stride
+     end function
+     integer(c_int) function tse_remap_view(ctx, nf, mode, alg, field, dp_src, dp_tgt, stream) bind(C, name='tse_remap_view')
+       import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nf, mode, alg
+       type(tse_view), intent(in) :: field, dp_src, dp_tgt
+     end function
+     integer(c_int) function tse_remap_view_status(ctx, nrefused, first) bind(C, name='tse_remap_view_status')
+       import; type(c_ptr), value :: ctx; integer(c_int), intent(out) :: nrefused, first(4)
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -811,5 +823,42 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine apply_forcing_elem_hip
+
+  ! field(:,:,:,1:nf) of the host's DEVICE array at ptr <- remap_Q_ppm of it from the layer thicknesses at src_ptr to those at tgt_ptr, in
+  ! place (include/transport_se_hip.h: tse_remap_view).  strides(1:5) in doubles for element, q, level, j, i; the grids have no q axis
+  ! (stride 0).  mode remap_mass: the field is mass per layer (Qdp, u*dp); remap_mean: a layer mean (T, u).  alg: vert_remap_q_alg of
+  ! this call.  stream as in view_put_hip.  nrefused (with c_null_ptr as the stream): elements whose grids the device refused and left
+  ! as they were (the message names the first); with a stream it is 0 and remap_view_status_hip reports.  Every other failure aborts.
+  subroutine remap_view_hip(nf, mode, alg, ptr, strides, src_ptr, src_strides, tgt_ptr, tgt_strides, stream, refused)
+    integer,              intent(in)  :: nf, mode, alg
+    type(c_ptr),          intent(in)  :: ptr, src_ptr, tgt_ptr, stream
+    integer(c_long_long), intent(in)  :: strides(5), src_strides(5), tgt_strides(5)
+    logical,              intent(out) :: refused
+    type(tse_view) :: vf, vs, vt
+    integer(c_int) :: rc
+    vf%ptr = ptr; vf%stride = strides
+    vs%ptr = src_ptr; vs%stride = src_strides
+    vt%ptr = tgt_ptr; vt%stride = tgt_strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    rc = tse_remap_view(ctx, int(nf,c_int), int(mode,c_int), int(alg,c_int), vf, vs, vt, stream)
+    if (rc /= 0 .and. rc /= 2) call check(rc, 'remap_view_hip')
+    remap_refused = (rc == 2)
+    !$OMP END MASTER
+    !$OMP BARRIER
+    refused = remap_refused
+  end subroutine remap_view_hip
+
+  ! what remap_view_hip calls with a stream refused since the last read: the number of elements, and in first(1:4) the element, column,
+  ! level (all counted from 0) and code (1..4) of the first one; waits for the library's compute stream, then clears
+  subroutine remap_view_status_hip(nrefused, first)
+    integer, intent(out) :: nrefused, first(4)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_remap_view_status(ctx, remap_nrefused, remap_where), 'remap_view_status_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+    nrefused = remap_nrefused; first = remap_where
+  end subroutine remap_view_status_hip
 
 end module cuda_mod

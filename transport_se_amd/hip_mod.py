@@ -127,6 +127,34 @@ def _forcing_mode(mode):
     return int(mode)
 
 
+REMAP_MODES = {"mass": 0, "mean": 1}   # TSE_REMAP_MASS, TSE_REMAP_MEAN
+
+
+def _remap_mode(mode):
+    """the mode names, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(mode, str):
+        if mode not in REMAP_MODES:
+            raise TseError("remap_view: unknown mode %r (the modes are %s)" % (mode, ", ".join(REMAP_MODES)))
+        return REMAP_MODES[mode]
+    return int(mode)
+
+
+def _raw_view(strides, ptr=None):
+    return strides if isinstance(strides, _lib.View) else _lib.View(ptr, (C.c_longlong * 5)(*[int(x) for x in strides]))
+
+
+def remap_view_plan(nelemd, nf, field, dp_src, dp_tgt, nlev=None):
+    """tse_remap_view_plan: [dict(path=, lo=, hi=)] of the three views of HipMod.remap_view -- field, dp_src, dp_tgt, each a _lib.View or
+    its five strides (doubles, in the order of VIEW_AXES), or a pair (strides, offset in bytes into one common allocation) so that the
+    overlap of the field with a grid is tested as well.  Needs no device.  Raises TseError for views remap_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    v = [_raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x) for x in (field, dp_src, dp_tgt)]
+    path, lo, hi = (C.c_int * 3)(), (C.c_longlong * 3)(), (C.c_longlong * 3)()
+    if L.tse_remap_view_plan(int(nelemd), int(nf), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(3)]
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -467,6 +495,40 @@ class HipMod:
         out = np.empty((self.nelemd, self.qsize, 2)) if budget else None
         self._chk(self.L.tse_apply_forcing_host(self.h, int(nt), float(dt), _forcing_mode(mode), _vp(f), f.strides[0], f.shape[1], _vp(out)))
         return out
+
+    # ---- vertical remap of the host's own level fields (tse_remap_view / tse_remap_view_status) ----
+    def remap_view(self, field, axes, dp_src, src_axes, dp_tgt, tgt_axes, mode="mass", alg=0, stream=None, nf=None):
+        """remap_Q_ppm of the device array `field` (a "qdp" get view whose tracer extent is the array's own: any nf >= 1) from the layer
+        thicknesses dp_src to dp_tgt (device arrays, "dp" put views), in place; mode "mass": the field is mass per layer, "mean": a layer
+        mean (multiplied by dp_src on read, divided by dp_tgt on write); alg: vert_remap_q_alg of this call (0|1|2).  Nothing of the
+        library's state is touched (include/transport_se_hip.h names the one exception).  stream orders as in put.  Returns the
+        library's code: 0, or with stream=None 2 when some element's grids were refused on the device (those elements keep every bit;
+        last_error() names the first); every other failure raises.  An argument may also be a ready _lib.View (then nf is needed)."""
+        if isinstance(field, _lib.View):
+            vf = field
+        else:
+            cai = getattr(field, "__cuda_array_interface__", None)
+            if cai is not None and "q" in str(axes) and len(cai["shape"]) == len(str(axes)):
+                nf = int(cai["shape"][str(axes).index("q")])
+            vf = build_view("qdp", field, axes, self.nelemd, nf, self.nlev, True)
+        vs = dp_src if isinstance(dp_src, _lib.View) else build_view("dp", dp_src, src_axes, self.nelemd, 1, self.nlev, False)
+        vt = dp_tgt if isinstance(dp_tgt, _lib.View) else build_view("dp", dp_tgt, tgt_axes, self.nelemd, 1, self.nlev, False)
+        if nf is None:
+            raise TseError("remap_view: nf is needed with a ready view")
+        rc = self.L.tse_remap_view(self.h, int(nf), _remap_mode(mode), int(alg), C.byref(vf), C.byref(vs), C.byref(vt), _stream_handle(stream))
+        if rc not in (0, 2):
+            self._chk(rc)
+        return rc
+
+    def remap_view_status(self):
+        """(count, (element, column, level, code)) of the elements that remap_view calls with a stream refused since the last read (the
+        first offender: the lowest element of the earliest such call; None when count is 0); waits for the compute stream, then clears"""
+        n, where = C.c_int(), (C.c_int * 4)()
+        self._chk(self.L.tse_remap_view_status(self.h, C.byref(n), C.byref(where)))
+        return n.value, (tuple(where) if n.value else None)
+
+    def last_error(self):
+        return self.L.tse_last_error().decode()
 
     def synchronize(self):
         self._chk(self.L.tse_synchronize(self.h))
