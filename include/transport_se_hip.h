@@ -327,6 +327,40 @@ int tse_remap_view_status(tse_ctx *ctx, int *nrefused, int where[4] /* element, 
 int tse_remap_view_plan(int nelemd, int nf, const tse_view *field, const tse_view *dp_src, const tse_view *dp_tgt,
                         int path[3], long long lo[3], long long hi[3]);
 
+/* ---- direct stiffness summation (DSS) of a GPU-resident host's OWN fields: the reference's spheremp*f -> edgeVpack -> bndry_exchangeV ->
+ * edgeVunpack -> rspheremp* idiom (prim_advection_mod.F90:911-960, edge_mod.F90:366-511,648-742), in place in the host's device array ----
+ * field: nf fields (the q axis of the view: whatever the host stacks; any nf >= 1, whatever the context's qsize; u and v are nf = 2) of nk
+ * levels each, 1 <= nk <= nlev + 1 (a surface field, a layer field, an interface field; every layer is summed).  For every layer and every
+ * GLL point p of element e
+ *     out = rspheremp[e][p] * (((w + c0) + c1) + c2)
+ *   mode TSE_DSS_AVERAGE  w = spheremp * f, one stored product (a nodal field: u, T, dp3d, ps_v)
+ *   mode TSE_DSS_WEAK     w = f (f carries the mass weight already: the result of a weak operator)
+ * c0..c2 are the contributions of the points that share the node, in the reference's order of unpacking (edges S, E, N, W, then the
+ * corner); an absent one adds +0.0; one from another rank is the w that rank packed.  Nothing is contracted, so the result has the bits of
+ * rspheremp * DSS(w) of the tracer engine's own DSS on every path of the view and on any number of ranks.
+ * View rules: those of a "qdp" get view (tse_view_plan) with nf and nk in place of qsize and nlev -- no zero stride on an axis of extent
+ * above 1 (an axis of extent 1 may carry stride 0), the axes nest so that no two index tuples share an address, device memory of the
+ * context's device, the footprint inside the allocation that holds ptr, a stream that is not being captured and belongs to this device.
+ * Refused besides: mode outside 0|1, nf < 1, nk outside 1..nlev+1, and a view inside any allocation of the library (qdp1 / qdp2 and this
+ * call's own staging buffers included: the call works on the host's arrays).  On failure: nonzero, tse_last_error(), nothing enqueued.
+ * Only the addresses of the view are written.  No library state is read or written: not Qdp, the level fields, the cached element bounds
+ * or the freshness of Q / lnps.
+ * Paths (tse_dss_view_plan): 0 point-fastest; 1 level-fastest (stride level = 1, i = S >= nk, j = 4S) for nk == nlev, through LDS; 2 any
+ * other strides, and a level-fastest view with another nk.  The three give the same bits.
+ * COLLECTIVE: on a context with neighbour ranks every rank makes the call, with the same nf, nk and mode, in the same order relative to
+ * the other exchanging calls.  It uses the context's own exchange (the RCCL communicator of tse_comm_init, or the callback, kind 0) with
+ * nf * nk layers per column; staging and halo buffers are the call's own, allocated by the first call, grown when a call brings more
+ * layers, freed by tse_finalize.
+ * stream orders as in tse_view_put (not null: wait for it, run on the compute stream, make it wait; null: complete on return).  Nothing
+ * waits on the CPU on one rank or with RCCL; the callback exchange drains the compute stream first, as everywhere.
+ * Timer group "fielddss" (two launches per call: stage and sum); pack and exchange count under comm_pack_q / comm_exchange_q / comm_wait. */
+#define TSE_DSS_AVERAGE 0
+#define TSE_DSS_WEAK    1
+int tse_dss_view(tse_ctx *ctx, int nf, int nk, int mode, const tse_view *field, void *stream);
+/* the path and the footprint [lo, hi) (doubles relative to ptr) such a view gets, and every refusal that needs no device (nf, nk, a zero
+ * stride on an extent above 1, a view that may overlap itself, a null view).  No context, no device. */
+int tse_dss_view_plan(int nelemd, int nf, int nk, const tse_view *field, int *path, long long *lo, long long *hi);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -371,7 +405,7 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

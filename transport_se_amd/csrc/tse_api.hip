@@ -104,6 +104,10 @@ struct tse_ctx {
   double* rv_detail = nullptr;
   unsigned long long* rv_acc = nullptr;
   unsigned rv_seq = 0;   // calls that gave a stream since the accumulator was last read
+  // tse_dss_view (allocated by its first call, grown when a call brings more layers): the staging field [nelemd][dv_layers][16] and, on a
+  // rank with neighbours, its own send and receive buffers [columns][dv_layers] -- the context's own are sized by qsize
+  double *dv_stage = nullptr, *dv_send = nullptr, *dv_recv = nullptr;
+  size_t dv_layers = 0;
   // halo: one slot per neighbour rank (Schedule(1)%SendCycle/RecvCycle), entries per slot for the two exchange kinds
   int ncol_send = 0, ncol_recv = 0, nlyr_halo = 0;
   int nmm_send = 0, nmm_recv = 0;              // entries of the compact min/max exchange
@@ -495,7 +499,7 @@ static std::vector<void*> device_allocations(const tse_ctx* c) {
                   c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
                   c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->norm_owner, c->norm_colw, c->norm_dh, c->qref, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
                   c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int,
-                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc};
+                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc, c->dv_stage, c->dv_send, c->dv_recv};
   std::vector<void*> out;
   for (void* p : ptrs) if (p) out.push_back(p);
   return out;
@@ -810,11 +814,12 @@ int tse_compute_divdp(tse_ctx* c) {
 // kind 0: sendbuf/recvbuf, one entry per edge-buffer column; kind 1: the compact min/max buffers.
 // With a communicator: one grouped RCCL receive + send per neighbour slot enqueued on `st`, no host synchronisation
 // (bndry_mod.F90:74-112 posts all sends and receives, then waits).  Otherwise the host's callback, after `st` has drained.
-static int halo_exchange(tse_ctx* c, int nlyr, int kind, hipStream_t st) {
+// sb / rb: other buffers of the same column layout instead of the context's (tse_dss_view brings its own: nlyr is not bounded by qsize).
+static int halo_exchange(tse_ctx* c, int nlyr, int kind, hipStream_t st, double* sb = nullptr, double* rb = nullptr) {
   if (!c->halo()) return 0;
   CommScope s(c, kind ? "comm_exchange_mm" : "comm_exchange_q", st);
-  double* sb = kind ? c->sendbuf_mm : c->sendbuf;
-  double* rb = kind ? c->recvbuf_mm : c->recvbuf;
+  if (!sb) sb = kind ? c->sendbuf_mm : c->sendbuf;
+  if (!rb) rb = kind ? c->recvbuf_mm : c->recvbuf;
   if (c->comm) {
     const std::vector<int>& ls = kind ? c->mm_send_len : c->send_len;
     const std::vector<int>& lr = kind ? c->mm_recv_len : c->recv_len;
@@ -1943,6 +1948,96 @@ int tse_remap_view_status(tse_ctx* c, int* nrefused, int where[4]) {
     if (where) { where[0] = (int)((acc[1] >> 16) & 0xffffffull); where[1] = (int)((acc[1] >> 12) & 15ull); where[2] = (int)((acc[1] >> 4) & 255ull); where[3] = (int)(acc[1] & 15ull); }
   }
   c->rv_seq = 0;
+  return 0;
+}
+
+// ---- DSS of a resident host's own fields (k_dss_view_stage, k_dss_view_sum: tse_kernels.h) -----------------------------------------
+// The plan is host code (tse_views.cpp: dss_view_plan); here the checks that need the runtime, the stream order of tse_view_put, and on the
+// compute stream: stage -> (pack -> halo_exchange kind 0 with nf * nk layers, on a rank with neighbours) -> sum.  The staging field and the
+// halo buffers are the call's own; a steady-state call allocates nothing.
+static int dss_view_buffers(tse_ctx* c, size_t nl) {
+  if (nl <= c->dv_layers) return 0;
+  HIPCHK(hipStreamSynchronize(c->stream));   // (an earlier call may still read the buffers that are given back)
+  double** bufs[3] = {&c->dv_stage, &c->dv_send, &c->dv_recv};
+  for (double** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+  c->dv_layers = 0;
+  if (dalloc(&c->dv_stage, (size_t)c->nelemd * nl * 16)) return 1;
+  if (c->halo() && (dalloc(&c->dv_send, (size_t)std::max(1, c->ncol_send) * nl) || dalloc(&c->dv_recv, (size_t)std::max(1, c->ncol_recv) * nl))) return 1;
+  c->dv_layers = nl;
+  return 0;
+}
+template <int MODE>
+static void launch_dss_view_stage(tse_ctx* c, int path, bool wide, const DssViewArgs& a, const double* view) {
+  const size_t slabs = (size_t)c->nelemd * a.nf * a.nk;
+  auto blocks = [](size_t items) { return dim3((unsigned)((items + VIEW_THREADS - 1) / VIEW_THREADS)); };
+#define TSE_DSS_STAGE(PATH, W, grid) hipLaunchKernelGGL((k_dss_view_stage<PATH, W, MODE>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, (const double*)c->spheremp, view, c->dv_stage)
+  if (path == 0) { if (wide) TSE_DSS_STAGE(0, true, blocks(slabs * 8)); else TSE_DSS_STAGE(0, false, blocks(slabs * 16)); }
+  else if (path == 1) { const dim3 grid((unsigned)((size_t)c->nelemd * a.nf)); if (wide) TSE_DSS_STAGE(1, true, grid); else TSE_DSS_STAGE(1, false, grid); }
+  else TSE_DSS_STAGE(2, false, blocks(slabs * 16));
+#undef TSE_DSS_STAGE
+}
+static void launch_dss_view_sum(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double* view) {
+  const long long nl = (long long)a.nf * a.nk;
+#define TSE_DSS_SUM(PATH, W, nblocks) hipLaunchKernelGGL((k_dss_view_sum<PATH, W>), dim3((unsigned)(nblocks)), dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, (const int2*)c->dss_tab, \
+    (const double*)c->rspheremp, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view)
+  if (path == 0) { if (wide) TSE_DSS_SUM(0, true, dss_view_sum_blocks(c->nelemd, nl * 8)); else TSE_DSS_SUM(0, false, dss_view_sum_blocks(c->nelemd, nl * 16)); }
+  else if (path == 1) { const long long nb = 8ll * ((c->nelemd + 7) >> 3) * a.nf; if (wide) TSE_DSS_SUM(1, true, nb); else TSE_DSS_SUM(1, false, nb); }
+  else TSE_DSS_SUM(2, false, dss_view_sum_blocks(c->nelemd, nl * 16));
+#undef TSE_DSS_SUM
+}
+
+int tse_dss_view(tse_ctx* c, int nf, int nk, int mode, const tse_view* field, void* stream) {
+  const char* who = "tse_dss_view";
+  if (!c) return fail("%s: null context", who);
+  if (mode != TSE_DSS_AVERAGE && mode != TSE_DSS_WEAK) return fail("%s: mode=%d (0: average, f <- rspheremp * DSS(spheremp * f); 1: weak, f <- rspheremp * DSS(f))", who, mode);
+  ViewPlan p;
+  { std::string err; if (dss_view_plan(c->nelemd, nf, nk, field, &p, &err)) return fail("%s", err.c_str()); }
+  const size_t nl = (size_t)nf * nk;
+  if ((size_t)c->nelemd * nl >= ((size_t)1 << 27)) return fail("%s: %d elements x %zu layers (the launches count 32-bit blocks)", who, c->nelemd, nl);
+  void* alloc = nullptr;
+  if (view_runtime_checks(c, who, "field", p, field, stream, &alloc)) return 1;
+  const std::vector<void*> mine = device_allocations(c);
+  if (std::find(mine.begin(), mine.end(), alloc) != mine.end())
+    return fail("%s: %p lies inside an allocation of the library; the call works on the host's own arrays", who, field->ptr);
+  unsigned pack_blocks = 0;
+  if (c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
+  if (dss_view_buffers(c, nl)) return 1;
+  hipStream_t us = (hipStream_t)stream;
+  if (us && !c->view_ev[0])
+    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+
+  DssViewArgs a;
+  for (int k = 0; k < 5; k++) a.vs[k] = field->stride[k];
+  a.nf = nf; a.nk = nk;
+  // 16 bytes per lane on the view side: k_view_lines' rule on path 0, k_view_levels' on path 1
+  const long long* s = field->stride;
+  const bool base16 = ((uintptr_t)field->ptr & 15) == 0;
+  const bool wide = p.path == 0 ? base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0 : p.path == 1 && base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
+
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
+  {
+    Scope sc(c, "fielddss");
+    if (mode == TSE_DSS_AVERAGE) launch_dss_view_stage<0>(c, p.path, wide, a, (const double*)field->ptr);
+    else launch_dss_view_stage<1>(c, p.path, wide, a, (const double*)field->ptr);
+    LAUNCH_CHECK();
+  }
+  if (c->halo()) {
+    CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
+    if (c->ncol_send) {
+      CommScope sc(c, "comm_pack_q", c->stream);
+      hipLaunchKernelGGL(k_pack<>, dim3(pack_blocks), dim3(256), 0, c->stream, c->ncol_send, (int)nl, c->send_src, (const double*)c->dv_stage, (const double*)nullptr,
+                         c->dv_send, (int)nl, 0, (int)nl);
+      LAUNCH_CHECK();
+    }
+    if (halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv)) return 1;
+  }
+  {
+    Scope sc(c, "fielddss");
+    launch_dss_view_sum(c, p.path, wide, a, (double*)field->ptr);
+    LAUNCH_CHECK();
+  }
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
+  else HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -2794,4 +2794,193 @@ __global__ __launch_bounds__(REMAP_THREADS) void k_remap_view(int nf, RemapViewA
   for (int f = tid >> 4; f < nf; f += nthreads >> 4) remap_columns_view<ALG2, MEAN, WIDE>(S, dpt, base + f * a.fs[1], a.fs[2], p);
 }
 
+// ---- DSS of a host's own fields through a strided view (tse_dss_view) -------------------------------------------------------------
+// f <- rspheremp * DSS(w), w = spheremp * f (MODE 0, a stored product) or w = f (MODE 1), for nf fields of nk levels in the host's own
+// array, in place.  12 of an element's 16 points are shared, so a pass that read its neighbours from the host's array would race with
+// their writers: the field crosses twice through a dense staging field stage[e][layer][16], layer = f * nk + k.
+//   k_dss_view_stage   view -> w -> stage, whole 128-byte lines on the stage side
+//   (k_pack from the stage, halo_exchange: on a rank with neighbours)
+//   k_dss_view_sum     own w and the up to three contributions of dss_tab[e][p][0..2] from the stage (local) or the receive buffer
+//                      (remote, [column][layer]), added in table order, times rspheremp, -> view
+// The three paths of a view (tse_views.h) address the view side only:
+//   PATH 0  point-fastest: thread = (element, layer, part of the 128-byte line), 16 bytes per lane (WIDE: view base 16-byte aligned, even
+//           element / q / level strides) or 8;
+//   PATH 2  any strides: thread = (element, layer, point), one address per entry;
+//   PATH 1  level-fastest, nk == NLEV: block = (element, field), the rows of consecutive levels pass through the LDS image tile[p][VIEW_PITCH]
+//           with the lane mapping of k_view_levels (WIDE as there).
+// Every sum is ((w + c0) + c1) + c2 with +0.0 for an absent contribution and nothing contracted: the three paths, and any cut of the mesh
+// into ranks, give the same bits.
+struct DssViewArgs { long long vs[5]; int nf, nk; };
+
+// the view side of a level-fastest tile, as k_view_levels moves it: 16 rows of K consecutive levels at pitch S <-> tile[p][VIEW_PITCH]
+template <bool WIDE, int K>
+__device__ __forceinline__ void dss_rows_to_tile(const double* __restrict__ V, long long S, double* __restrict__ tile, int tid) {
+  constexpr int KP = K / 2;
+  static_assert(K % 2 == 0, "whole level pairs");
+  if (WIDE) {
+    constexpr int NV = (16 * KP + VIEW_THREADS - 1) / VIEW_THREADS;
+    double2 r[NV];
+#pragma unroll
+    for (int u = 0; u < NV; u++) { const int it = min(u * VIEW_THREADS + tid, 16 * KP - 1); r[u] = *(const double2*)(V + (it / KP) * S + 2 * (it % KP)); }   // (a lane past the end reloads the last item)
+#pragma unroll
+    for (int u = 0; u < NV; u++) view_keep(r[u]);
+#pragma unroll
+    for (int u = 0; u < NV; u++) {
+      const int it = u * VIEW_THREADS + tid;
+      if (it < 16 * KP) *(double2*)(tile + (it / KP) * VIEW_PITCH + 2 * (it % KP)) = r[u];
+    }
+  } else {
+    constexpr int NV = (16 * K + VIEW_THREADS - 1) / VIEW_THREADS;
+    double r[NV];
+#pragma unroll
+    for (int u = 0; u < NV; u++) { const int it = min(u * VIEW_THREADS + tid, 16 * K - 1); r[u] = V[(it / K) * S + it % K]; }
+#pragma unroll
+    for (int u = 0; u < NV; u++) view_keep(r[u]);
+#pragma unroll
+    for (int u = 0; u < NV; u++) {
+      const int it = u * VIEW_THREADS + tid;
+      if (it < 16 * K) tile[(it / K) * VIEW_PITCH + it % K] = r[u];
+    }
+  }
+}
+template <bool WIDE, int K>
+__device__ __forceinline__ void dss_tile_to_rows(const double* __restrict__ tile, double* __restrict__ V, long long S, int tid) {
+  constexpr int KP = K / 2;
+  if (WIDE) {
+    for (int it = tid; it < 16 * KP; it += VIEW_THREADS) *(double2*)(V + (it / KP) * S + 2 * (it % KP)) = *(const double2*)(tile + (it / KP) * VIEW_PITCH + 2 * (it % KP));
+  } else {
+    for (int it = tid; it < 16 * K; it += VIEW_THREADS) V[(it / K) * S + it % K] = tile[(it / K) * VIEW_PITCH + it % K];
+  }
+}
+
+template <int PATH, bool WIDE, int MODE>
+__global__ __launch_bounds__(VIEW_THREADS) void k_dss_view_stage(int nelemd, DssViewArgs a, const double* __restrict__ spheremp, const double* __restrict__ view,
+                                                                 double* __restrict__ stage) {
+#pragma clang fp contract(off)
+  const int nl = a.nf * a.nk;
+  if (PATH == 1) {
+    __shared__ __attribute__((aligned(16))) double tile[16 * VIEW_PITCH];
+    constexpr int K = NLEV, NL = (8 * K + VIEW_THREADS - 1) / VIEW_THREADS;
+    const int f = (int)(blockIdx.x % (unsigned)a.nf), tid = threadIdx.x, h = tid & 7;
+    const long long e = (long long)(blockIdx.x / (unsigned)a.nf);
+    const double2 m = *(const double2*)(spheremp + (size_t)e * 16 + 2 * h);
+    dss_rows_to_tile<WIDE, K>(view + e * a.vs[0] + f * a.vs[1], a.vs[4], tile, tid);
+    __syncthreads();
+    double* L = stage + ((size_t)e * nl + (size_t)f * K) * 16;
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+      const int it = u * VIEW_THREADS + tid;
+      if (it < 8 * K) {
+        const double* s = tile + 2 * h * VIEW_PITCH + (it >> 3);
+        double2 x = make_double2(s[0], s[VIEW_PITCH]);
+        if (MODE == 0) { x.x = m.x * x.x; x.y = m.y * x.y; }
+        *(double2*)(L + (it >> 3) * 16 + 2 * h) = x;
+      }
+    }
+  } else {
+    constexpr int W = (PATH == 0 && WIDE) ? 2 : 1, PARTS = 16 / W;
+    const size_t t = (size_t)blockIdx.x * VIEW_THREADS + threadIdx.x;
+    if (t >= (size_t)nelemd * nl * PARTS) return;
+    const int part = (int)(t % PARTS);
+    const size_t r = t / PARTS;
+    const int layer = (int)(r % (unsigned)nl);
+    const long long e = (long long)(r / (unsigned)nl);
+    const int f = layer / a.nk, k = layer - f * a.nk;
+    const double* V = view + e * a.vs[0] + f * a.vs[1] + k * a.vs[2];
+    double* S = stage + ((size_t)e * nl + layer) * 16 + part * W;
+    if (W == 2) {
+      double2 x = *(const double2*)(V + 2 * part);
+      if (MODE == 0) { const double2 m = *(const double2*)(spheremp + (size_t)e * 16 + 2 * part); x.x = m.x * x.x; x.y = m.y * x.y; }
+      *(double2*)S = x;
+    } else {
+      double x = V[(part >> 2) * a.vs[3] + (part & 3) * a.vs[4]];
+      if (MODE == 0) x = spheremp[(size_t)e * 16 + part] * x;
+      *S = x;
+    }
+  }
+}
+
+// ((w + c0) + c1) + c2 of point p of element e in one layer.  Every slot is one unconditional load, as in k_dss_lvl: an empty slot re-reads
+// the point's own w and adds +0.0 whatever it read, a local one reads the neighbour's line of the stage, a remote one the receive buffer.
+__device__ __forceinline__ double dss_view_point(const int2* __restrict__ tab, const double* __restrict__ stage, const double* __restrict__ recvbuf, int nl,
+                                                 int e, int p, int layer, double& rs, const double* __restrict__ rspheremp) {
+#pragma clang fp contract(off)
+  const double* own = stage + ((size_t)e * nl + layer) * 16 + p;
+  const int2* tt = tab + ((size_t)e * 16 + p) * 3;
+  const double* ap[3];
+  bool has[3];
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const int2 t = tt[s];
+    ap[s] = own; has[s] = false;
+    if (t.x >= 0) { ap[s] = stage + ((size_t)t.x * nl + layer) * 16 + t.y; has[s] = true; }
+    else if (t.x <= -2) { ap[s] = recvbuf + (size_t)(-(t.x + 2)) * nl + layer; has[s] = true; }
+  }
+  double w = *own, c[3];
+  rs = rspheremp[(size_t)e * 16 + p];
+#pragma unroll
+  for (int s = 0; s < 3; s++) c[s] = *ap[s];
+#pragma unroll
+  for (int s = 0; s < 3; s++) c[s] = has[s] ? c[s] : 0.0;
+  w = w + c[0]; w = w + c[1]; w = w + c[2];
+  return w;
+}
+
+// Blocks are dealt to the XCDs in contiguous ranges of `order` (blockIdx & 7 = the XCD, as in dss_lane), so that the lines of a
+// neighbour come from the L2 that holds the block's own.  PATH 0 / 2: lanes flattened over (element slot, layer, part) within a range;
+// PATH 1: block = (element slot, field).
+template <int PATH, bool WIDE>
+__global__ __launch_bounds__(VIEW_THREADS) void k_dss_view_sum(int nelemd, DssViewArgs a, const int2* __restrict__ tab, const double* __restrict__ rspheremp,
+                                                               const double* __restrict__ stage, const double* __restrict__ recvbuf, const int* __restrict__ order,
+                                                               double* __restrict__ view) {
+#pragma clang fp contract(off)
+  const int nl = a.nf * a.nk;
+  const int S8 = (nelemd + 7) >> 3, xcd = blockIdx.x & 7;
+  const unsigned it = blockIdx.x >> 3;
+  if (PATH == 1) {
+    __shared__ __attribute__((aligned(16))) double tile[16 * VIEW_PITCH];
+    constexpr int K = NLEV, NL = (8 * K + VIEW_THREADS - 1) / VIEW_THREADS;
+    const int idx = (int)(it / (unsigned)a.nf), f = (int)(it % (unsigned)a.nf), slot = xcd * S8 + idx;
+    if (idx >= S8 || slot >= nelemd) return;   // (uniform over the block: before the barrier)
+    const int e = order[slot], tid = threadIdx.x, h = tid & 7;
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+      const int i2 = u * VIEW_THREADS + tid;
+      if (i2 < 8 * K) {
+        const int k = i2 >> 3;
+        double r0, r1;
+        const double x0 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * h, f * K + k, r0, rspheremp);
+        const double x1 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * h + 1, f * K + k, r1, rspheremp);
+        double* s = tile + 2 * h * VIEW_PITCH + k;
+        s[0] = r0 * x0; s[VIEW_PITCH] = r1 * x1;
+      }
+    }
+    __syncthreads();
+    dss_tile_to_rows<WIDE, K>(tile, view + (long long)e * a.vs[0] + f * a.vs[1], a.vs[4], tid);
+  } else {
+    constexpr int W = (PATH == 0 && WIDE) ? 2 : 1, PARTS = 16 / W;
+    const long long units = (long long)nl * PARTS;
+    const long long g = (long long)it * VIEW_THREADS + threadIdx.x;
+    const long long idx = g / units;
+    const int r = (int)(g - idx * units);
+    const long long slot = (long long)xcd * S8 + idx;
+    if (idx >= S8 || slot >= nelemd) return;
+    const int e = order[slot], layer = r / PARTS, part = r - layer * PARTS;
+    const int f = layer / a.nk, k = layer - f * a.nk;
+    double* V = view + (long long)e * a.vs[0] + f * a.vs[1] + k * a.vs[2];
+    if (W == 2) {
+      double r0, r1;
+      const double x0 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * part, layer, r0, rspheremp);
+      const double x1 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * part + 1, layer, r1, rspheremp);
+      *(double2*)(V + 2 * part) = make_double2(r0 * x0, r1 * x1);
+    } else {
+      double r0;
+      const double x0 = dss_view_point(tab, stage, recvbuf, nl, e, part, layer, r0, rspheremp);
+      V[(part >> 2) * a.vs[3] + (part & 3) * a.vs[4]] = r0 * x0;
+    }
+  }
+}
+// blocks of k_dss_view_sum<0 | 2>: 8 XCD ranges of ceil(nelemd / 8) element slots, `units` lanes per element
+inline long long dss_view_sum_blocks(int nelemd, long long units) { return 8 * ((((long long)((nelemd + 7) >> 3)) * units + VIEW_THREADS - 1) / VIEW_THREADS); }
+
 }  // namespace tse

@@ -40,6 +40,39 @@ int refuse(std::string* err, const char* fmt, ...) {
 
 }  // namespace
 
+// The part of a plan that follows the extents: the footprint, for a destination view that no two index tuples share an address, and the
+// path the strides take.
+static int footprint_and_path(const char* who, ViewPlan& p, const long long* s, bool for_get, bool has_level, std::string* err) {
+  // footprint; every product in 128 bits, refused beyond 2^60 doubles
+  const __int128 LIMIT = (__int128)1 << 60;
+  __int128 lo = 0, hi = 0;
+  for (int a = 0; a < 5; a++) {
+    const __int128 span = (__int128)s[a] * (p.ext[a] - 1);
+    if (span > LIMIT || span < -LIMIT) return refuse(err, "%s: the %s stride %lld is out of range", who, AXIS[a], s[a]);
+    if (span < 0) lo += span; else hi += span;
+  }
+  p.lo = (long long)lo; p.hi = (long long)hi + 1;
+
+  if (for_get) {
+    // no two index tuples on one address: the axes that move (extent > 1) sorted by |stride|, each at least the previous one's stride
+    // times its extent.  Sufficient, not necessary: an interleaved but disjoint view is refused too.
+    int idx[5], n = 0;
+    for (int a = 0; a < 5; a++) if (p.ext[a] > 1) idx[n++] = a;
+    auto mag = [&](int a) { return s[a] < 0 ? -(__int128)s[a] : (__int128)s[a]; };
+    std::stable_sort(idx, idx + n, [&](int x, int y) { return mag(x) < mag(y); });
+    for (int i = 1; i < n; i++)
+      if (mag(idx[i]) < mag(idx[i - 1]) * p.ext[idx[i - 1]])
+        return refuse(err, "%s: the view may overlap itself: the %s stride (%lld) is smaller than the %s stride (%lld) times its extent %d", who,
+                      AXIS[idx[i]], s[idx[i]], AXIS[idx[i - 1]], s[idx[i - 1]], p.ext[idx[i - 1]]);
+  }
+
+  const long long S = s[4];
+  if (s[4] == 1 && s[3] == NP) p.path = 0;
+  else if (has_level && s[2] == 1 && S >= p.ext[2] && s[3] == NP * S) p.path = 1;
+  else p.path = 2;
+  return 0;
+}
+
 int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool for_get, ViewPlan* out, std::string* err) {
   const char* who = for_get ? "tse_view_get" : "tse_view_put";
   if (!field || !v || !out) return refuse(err, "%s: null %s", who, !field ? "field name" : !v ? "view" : "plan");
@@ -70,33 +103,7 @@ int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool 
     if (has[a] && for_get && s[a] == 0) return refuse(err, "%s: stride 0 on the %s axis: a destination view may not broadcast", who, AXIS[a]);
   }
 
-  // footprint; every product in 128 bits, refused beyond 2^60 doubles
-  const __int128 LIMIT = (__int128)1 << 60;
-  __int128 lo = 0, hi = 0;
-  for (int a = 0; a < 5; a++) {
-    const __int128 span = (__int128)s[a] * (p.ext[a] - 1);
-    if (span > LIMIT || span < -LIMIT) return refuse(err, "%s: the %s stride %lld is out of range", who, AXIS[a], s[a]);
-    if (span < 0) lo += span; else hi += span;
-  }
-  p.lo = (long long)lo; p.hi = (long long)hi + 1;
-
-  if (for_get) {
-    // no two index tuples on one address: the axes that move (extent > 1) sorted by |stride|, each at least the previous one's stride
-    // times its extent.  Sufficient, not necessary: an interleaved but disjoint view is refused too.
-    int idx[5], n = 0;
-    for (int a = 0; a < 5; a++) if (p.ext[a] > 1) idx[n++] = a;
-    auto mag = [&](int a) { return s[a] < 0 ? -(__int128)s[a] : (__int128)s[a]; };
-    std::stable_sort(idx, idx + n, [&](int x, int y) { return mag(x) < mag(y); });
-    for (int i = 1; i < n; i++)
-      if (mag(idx[i]) < mag(idx[i - 1]) * p.ext[idx[i - 1]])
-        return refuse(err, "%s: the view may overlap itself: the %s stride (%lld) is smaller than the %s stride (%lld) times its extent %d", who,
-                      AXIS[idx[i]], s[idx[i]], AXIS[idx[i - 1]], s[idx[i - 1]], p.ext[idx[i - 1]]);
-  }
-
-  const long long S = s[4];
-  if (s[4] == 1 && s[3] == NP) p.path = 0;
-  else if (has[2] && s[2] == 1 && S >= p.ext[2] && s[3] == NP * S) p.path = 1;
-  else p.path = 2;
+  if (footprint_and_path(who, p, s, for_get, has[2], err)) return 1;
   *out = p;
   return 0;
 }
@@ -131,6 +138,30 @@ int remap_view_overlap(const tse_view* field, const tse_view* dp_src, const tse_
   return 0;
 }
 
+// tse_dss_view's view: the rules of a "qdp" get view (written in place) with nf field slots on the q axis and nk levels; an axis of extent
+// 1 may carry any stride, 0 included.  The dense side is the staging field [e][f * nk + k][16].  Path 1 exists for nk == NLEV alone: a
+// level-fastest view of another depth takes the generic path, and the plan says so.
+int dss_view_plan(int nelemd, int nf, int nk, const tse_view* v, ViewPlan* out, std::string* err) {
+  const char* who = "tse_dss_view";
+  if (!v || !out) return refuse(err, "%s: null %s", who, !v ? "view" : "plan");
+  if (nelemd <= 0) return refuse(err, "%s: nelemd = %d", who, nelemd);
+  if (nf < 1) return refuse(err, "%s: nf = %d (at least one field)", who, nf);
+  if (nk < 1 || nk > NLEVP) return refuse(err, "%s: nk = %d (1 to nlev + 1 = %d levels)", who, nk, NLEVP);
+  if ((long long)nf * nk >= (1ll << 24)) return refuse(err, "%s: nf * nk = %lld layers", who, (long long)nf * nk);
+  ViewPlan p;
+  p.field = VF_QDP;
+  p.ext[0] = nelemd; p.ext[1] = nf; p.ext[2] = nk; p.ext[3] = NP; p.ext[4] = NP;
+  const long long slab = NP * NP;
+  p.lib[4] = 1; p.lib[3] = NP; p.lib[2] = slab; p.lib[1] = slab * nk; p.lib[0] = slab * nk * nf;
+  const long long* s = v->stride;
+  for (int a = 0; a < 5; a++)
+    if (p.ext[a] > 1 && s[a] == 0) return refuse(err, "%s: stride 0 on the %s axis (extent %d): the field is written in place and may not broadcast", who, AXIS[a], p.ext[a]);
+  if (footprint_and_path(who, p, s, true, true, err)) return 1;
+  if (p.path == 1 && nk != NLEV) p.path = 2;
+  *out = p;
+  return 0;
+}
+
 }  // namespace tse
 
 extern "C" int tse_view_plan(const char* field, int nelemd, int qsize, const tse_view* v, int for_get, int* path, long long* lo, long long* hi) {
@@ -155,5 +186,15 @@ extern "C" int tse_remap_view_plan(int nelemd, int nf, const tse_view* field, co
     if (lo) lo[i] = p[i].lo;
     if (hi) hi[i] = p[i].hi;
   }
+  return 0;
+}
+
+extern "C" int tse_dss_view_plan(int nelemd, int nf, int nk, const tse_view* field, int* path, long long* lo, long long* hi) {
+  tse::ViewPlan p;
+  std::string err;
+  if (tse::dss_view_plan(nelemd, nf, nk, field, &p, &err)) return tse::set_last_error(err.c_str());
+  if (path) *path = p.path;
+  if (lo) *lo = p.lo;
+  if (hi) *hi = p.hi;
   return 0;
 }

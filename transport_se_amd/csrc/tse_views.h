@@ -30,6 +30,10 @@ int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool 
 int remap_view_plan(int nelemd, int nf, const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, ViewPlan out[3], std::string* err);
 int remap_view_overlap(const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, const ViewPlan plan[3], std::string* err);
 
+// The view of tse_dss_view / tse_dss_view_plan: nf field slots of nk levels (1 <= nk <= NLEVP), the rules of a "qdp" get view except that an
+// axis of extent 1 may carry stride 0.  lib[] are the strides of the staging field [e][f * nk + k][16]; path 1 only for nk == NLEV.
+int dss_view_plan(int nelemd, int nf, int nk, const tse_view* field, ViewPlan* out, std::string* err);
+
 // the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
 int set_last_error(const char* msg);
 

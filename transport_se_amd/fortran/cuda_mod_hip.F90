@@ -55,6 +55,9 @@ module cuda_mod
   ! vertical remap of the host's own level fields on its own grids (INTEGRATION.md section 2g): remap_Q_ppm in place in a device array
   public :: remap_view_hip, remap_view_status_hip
   integer, parameter, public :: remap_mass = 0, remap_mean = 1   ! TSE_REMAP_MASS, TSE_REMAP_MEAN
+  ! DSS of the host's own device-resident fields (tse_dss_view)
+  public :: dss_view_hip
+  integer, parameter, public :: dss_average = 0, dss_weak = 1   ! TSE_DSS_AVERAGE, TSE_DSS_WEAK
   logical, save :: remap_refused = .false.            ! remap_view_hip / remap_view_status_hip: the master thread's answer, read by every thread
   integer(c_int), save :: remap_nrefused = 0, remap_where(4) = 0
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
@@ -199,6 +202,10 @@ module cuda_mod
      end function
      integer(c_int) function tse_remap_view_status(ctx, nrefused, first) bind(C, name='tse_remap_view_status')
        import; type(c_ptr), value :: ctx; integer(c_int), intent(out) :: nrefused, first(4)
+     end function
+     integer(c_int) function tse_dss_view(ctx, nf, nk, mode, field, stream) bind(C, name='tse_dss_view')
+       import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nf, nk, mode
+       type(tse_view), intent(in) :: field
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -860,5 +867,23 @@ contains
     !$OMP BARRIER
     nrefused = remap_nrefused; first = remap_where
   end subroutine remap_view_status_hip
+
+  ! field(:,:,1:nk,1:nf) of the host's DEVICE array at ptr <- rspheremp * DSS(w) of it, in place (include/transport_se_hip.h:
+  ! tse_dss_view): the spheremp* -> edgeVpack -> bndry_exchangeV -> edgeVunpack -> rspheremp* idiom in one call.  strides(1:5) in doubles
+  ! for element, q, level, j, i (an axis of extent 1 may carry stride 0).  mode dss_average: w = spheremp * f (a nodal field: u, T, dp3d,
+  ! ps_v); dss_weak: w = f (the result of a weak operator).  nk: 1 to nlev + 1 levels.  COLLECTIVE: every rank calls with the same nf, nk
+  ! and mode.  stream as in view_put_hip.  A refusal aborts.
+  subroutine dss_view_hip(nf, nk, mode, ptr, strides, stream)
+    integer,              intent(in) :: nf, nk, mode
+    type(c_ptr),          intent(in) :: ptr, stream
+    integer(c_long_long), intent(in) :: strides(5)
+    type(tse_view) :: v
+    v%ptr = ptr; v%stride = strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_dss_view(ctx, int(nf,c_int), int(nk,c_int), int(mode,c_int), v, stream), 'dss_view_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine dss_view_hip
 
 end module cuda_mod

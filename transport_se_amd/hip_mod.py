@@ -155,6 +155,73 @@ def remap_view_plan(nelemd, nf, field, dp_src, dp_tgt, nlev=None):
     return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(3)]
 
 
+DSS_MODES = {"average": 0, "weak": 1}   # TSE_DSS_AVERAGE, TSE_DSS_WEAK
+
+
+def _dss_mode(mode):
+    """the mode names, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(mode, str):
+        if mode not in DSS_MODES:
+            raise TseError("dss_view: unknown mode %r (the modes are %s)" % (mode, ", ".join(DSS_MODES)))
+        return DSS_MODES[mode]
+    return int(mode)
+
+
+def build_dss_view(array, axes, nelemd):
+    """(_lib.View, nf, nk) of `array` -- anything with __cuda_array_interface__ -- for dss_view: its dimensions are named, in order, by the
+    letters of `axes` over e q k j i; e, j and i are needed, a missing q or k letter means extent 1 and stride 0; nf and nk are the
+    array's own extents.  Raises TseError as build_view does.  The device is not touched."""
+    who = "dss_view"
+    cai = getattr(array, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TseError("%s: the array has no __cuda_array_interface__ (a device array is needed)" % who)
+    axes = str(axes)
+    for a in axes:
+        if a not in VIEW_AXES:
+            raise TseError("%s: unknown axis letter %r in %r (the letters are %s)" % (who, a, axes, " ".join(VIEW_AXES)))
+        if axes.count(a) > 1:
+            raise TseError("%s: axis %r appears twice in %r" % (who, a, axes))
+    for a in "eji":
+        if a not in axes:
+            raise TseError("%s: the axes %r lack %r" % (who, axes, a))
+    if cai["typestr"] != "<f8":
+        raise TseError("%s: element type %s, the library moves <f8 only" % (who, cai["typestr"]))
+    shape = tuple(int(x) for x in cai["shape"])
+    if len(shape) != len(axes):
+        raise TseError("%s: %d axes named for an array of %d dimensions" % (who, len(axes), len(shape)))
+    ptr, readonly = cai["data"]
+    if readonly:
+        raise TseError("%s: the array is read-only and would be written in place" % who)
+    strides = cai.get("strides")
+    if strides is None:   # C-contiguous
+        strides, acc = [], 8
+        for n in reversed(shape):
+            strides.insert(0, acc); acc *= n
+    want = dict(e=nelemd, j=NP, i=NP)
+    ext = dict(q=1, k=1)
+    v = _lib.View()
+    v.ptr = int(ptr)
+    for a, n, sb in zip(axes, shape, strides):
+        if a in want and n != want[a]:
+            raise TseError("%s: axis %r has extent %d, the array has %d" % (who, a, want[a], n))
+        if int(sb) % 8:
+            raise TseError("%s: the byte stride %d of axis %r is not a multiple of 8" % (who, sb, a))
+        ext[a] = n
+        v.stride[VIEW_AXES.index(a)] = int(sb) // 8
+    return v, ext["q"], ext["k"]
+
+
+def dss_view_plan(nelemd, nf, nk, field, nlev=None):
+    """tse_dss_view_plan: dict(path=, lo=, hi=) of the view HipMod.dss_view would be given -- `field` a _lib.View or its five strides
+    (doubles, in the order of VIEW_AXES).  Needs no device.  Raises TseError for a view dss_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    path, lo, hi = C.c_int(), C.c_longlong(), C.c_longlong()
+    v = None if field is None else C.byref(_raw_view(field))
+    if L.tse_dss_view_plan(int(nelemd), int(nf), int(nk), v, C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return dict(path=path.value, lo=lo.value, hi=hi.value)
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -526,6 +593,22 @@ class HipMod:
         n, where = C.c_int(), (C.c_int * 4)()
         self._chk(self.L.tse_remap_view_status(self.h, C.byref(n), C.byref(where)))
         return n.value, (tuple(where) if n.value else None)
+
+    # ---- DSS of the host's own fields (tse_dss_view) ----
+    def dss_view(self, field, axes, mode="average", stream=None, nf=None, nk=None):
+        """field <- rspheremp * DSS(w) of the device array `field`, in place: nf fields of nk levels, both the array's own extents along
+        the letters q and k of `axes` (a missing letter: extent 1).  mode "average": w = spheremp * field (a nodal field: u, T, dp3d,
+        ps_v); "weak": w = field (it carries the mass weight already).  The order of addition is the tracer engine's own, so the bits
+        do not depend on the view's path or on the number of ranks.  COLLECTIVE on a context with neighbour ranks: every rank calls
+        with the same nf, nk and mode.  Nothing of the library's state is touched.  stream orders as in put.  `field` may also be a
+        ready _lib.View (then nf and nk are needed)."""
+        if isinstance(field, _lib.View):
+            if nf is None or nk is None:
+                raise TseError("dss_view: nf and nk are needed with a ready view")
+            v = field
+        else:
+            v, nf, nk = build_dss_view(field, axes, self.nelemd)
+        self._chk(self.L.tse_dss_view(self.h, int(nf), int(nk), _dss_mode(mode), C.byref(v), _stream_handle(stream)))
 
     def last_error(self):
         return self.L.tse_last_error().decode()
