@@ -361,6 +361,37 @@ int tse_dss_view(tse_ctx *ctx, int nf, int nk, int mode, const tse_view *field, 
  * stride on an extent above 1, a view that may overlap itself, a null view).  No context, no device. */
 int tse_dss_view_plan(int nelemd, int nf, int nk, const tse_view *field, int *path, long long *lo, long long *hi);
 
+/* ---- weak Laplacian and biharmonic of a GPU-resident host's OWN scalar fields: the scalar half of its hyperviscosity, the reference's
+ * laplace_sphere_wk (derivative_mod.F90:2418-2460, constant coefficient) and biharmonic_wk_scalar / the T and dp3d part of
+ * biharmonic_wk_dp3d (viscosity_mod.F90:315-344, 229-279) on every layer of nf fields of nk levels, 1 <= nk <= nlev + 1 ----
+ *   order TSE_LAPLACE     out = laplace_sphere_wk(in): weak (it carries spheremp), not summed over elements; no exchange, not collective
+ *   order TSE_BIHARMONIC  w = laplace_sphere_wk(in);  m[p] = rspheremp[e][p] * (((w + c0) + c1) + c2), tse_dss_view's TSE_DSS_WEAK sum (table
+ *                         order, +0.0 for an absent contribution, the sender's packed w for a remote one);  out = laplace_sphere_wk(m)
+ * The Laplacian is tse_laplace_sphere_wk's own device routine, nothing contracted beyond what it spells out, so every slab of order 1 has
+ * that entry's bits and order 2 has the bits of tse_laplace_sphere_wk -> tse_dss_view(TSE_DSS_WEAK) -> tse_laplace_sphere_wk, on one rank or
+ * many and on every path of either view.  The result is the weak tendency BEFORE the final DSS: the host multiplies by -nu * dt and follows
+ * with tse_dss_view(..., TSE_DSS_WEAK, ...), as advance_hypervis does.  No nu, no dp0 scaling, no hypervis_scaling tensor; the vector
+ * Laplacian of u and v is not part of this entry.
+ * Views: `in` and `out` each obey the rules of tse_dss_view's view and each takes its own path (0 point-fastest, 1 level-fastest for
+ * nk == nlev, 2 anything else).  out may be the same view as in -- the same ptr and the same five strides: in place, like the reference's
+ * qtens -- otherwise the two footprints [lo, hi) must be disjoint; any other overlap is refused.  Only the addresses of out are written;
+ * with a separate out, in keeps every bit.  Refused besides: order outside 1|2, nf < 1, nk outside 1..nlev+1, either view inside an
+ * allocation of the library (the staging buffers included).  On failure: nonzero, tse_last_error(), nothing enqueued.
+ * No library state is read or written; the staging and halo buffers are tse_dss_view's, grown when a call brings more layers, so a
+ * steady-state call allocates nothing.
+ * COLLECTIVE for order 2 on a context with neighbour ranks, as tse_dss_view (exchange kind 0 with nf * nk layers); order 1 never exchanges.
+ * stream orders as in tse_dss_view (not null: wait for it, run on the compute stream, make it wait; null: complete on return; a stream
+ * under capture or of another device is refused).
+ * Timer group "fieldlap" (two launches per call for either order: the stage kernel, in -> first Laplacian -> staging field, and the out
+ * kernel, staging field -> [sum, rspheremp, second Laplacian] -> out); pack and exchange count under comm_pack_q / comm_exchange_q / comm_wait. */
+#define TSE_LAPLACE    1   /* out = laplace_sphere_wk(in): weak, not summed; no exchange, not collective */
+#define TSE_BIHARMONIC 2   /* out = laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(in))): collective like tse_dss_view */
+int tse_biharmonic_view(tse_ctx *ctx, int nf, int nk, int order, const tse_view *in, const tse_view *out, void *stream);
+/* the paths and footprints [lo, hi) (doubles relative to each ptr) of in ([0]) and out ([1]), and every refusal that needs no device; the
+ * overlap rule is applied when either ptr is not null.  Host only: no context, no device. */
+int tse_biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view *in, const tse_view *out,
+                             int path[2], long long lo[2], long long hi[2]);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -401,11 +432,12 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
 /* device pointers of internal fields: "qdp1", "qdp2" [nelemd][qsize][nlev][16] (the two time levels are two allocations), "vn0", "dp", "divdp", "divdp_proj",
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
  * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference),
- * "remap_status" [nelemd][4] ints (null before the first tse_remap_view) */
+ * "remap_status" [nelemd][4] ints (null before the first tse_remap_view), "view_stage" [nelemd][layers][16] the staging field tse_dss_view and
+ * tse_biharmonic_view share (null before the first call of either; it moves only when a call brings more layers than any before) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -2041,6 +2041,96 @@ int tse_dss_view(tse_ctx* c, int nf, int nk, int mode, const tse_view* field, vo
   return 0;
 }
 
+// ---- weak Laplacian / biharmonic of a resident host's own scalar fields (k_lap_view_stage, k_lap_view_out: tse_kernels.h) ------------
+// The plan is host code (tse_views.cpp: biharmonic_view_plan / biharmonic_view_overlap); here the checks that need the runtime, the
+// stream order of tse_view_put, and on the compute stream: stage -> (order 2 on a rank with neighbours: pack -> halo_exchange kind 0 with
+// nf * nk layers) -> out.  The buffers are tse_dss_view's (dss_view_buffers); a steady-state call allocates nothing.
+// 16 bytes per lane on the view side: k_view_lines' rule on path 0, k_view_levels' on path 1
+static bool dss_view_wide(int path, const tse_view* v) {
+  const long long* s = v->stride;
+  const bool base16 = ((uintptr_t)v->ptr & 15) == 0;
+  return path == 0 ? base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0 : path == 1 && base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
+}
+static DssViewArgs dss_view_args(int nf, int nk, const tse_view* v) {
+  DssViewArgs a;
+  for (int k = 0; k < 5; k++) a.vs[k] = v->stride[k];
+  a.nf = nf; a.nk = nk;
+  return a;
+}
+static void launch_lap_view_stage(tse_ctx* c, int path, bool wide, const DssViewArgs& a, const double* view) {
+  const long long quads = (long long)c->nelemd * lap_view_groups((long long)a.nf * a.nk);
+  const dim3 flat((unsigned)((quads * 4 + VIEW_THREADS - 1) / VIEW_THREADS)), tiles((unsigned)((size_t)c->nelemd * a.nf));
+#define TSE_LAP_STAGE(PATH, W, grid) hipLaunchKernelGGL((k_lap_view_stage<PATH, W>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), view, c->dv_stage)
+  if (path == 0) { if (wide) TSE_LAP_STAGE(0, true, flat); else TSE_LAP_STAGE(0, false, flat); }
+  else if (path == 1) { if (wide) TSE_LAP_STAGE(1, true, tiles); else TSE_LAP_STAGE(1, false, tiles); }
+  else TSE_LAP_STAGE(2, false, flat);
+#undef TSE_LAP_STAGE
+}
+template <int ORDER>
+static void launch_lap_view_out(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double* view) {
+  const dim3 flat((unsigned)lap_view_out_blocks(c->nelemd, (long long)a.nf * a.nk)), tiles((unsigned)(8ll * ((c->nelemd + 7) >> 3) * a.nf));
+#define TSE_LAP_OUT(PATH, W, grid) hipLaunchKernelGGL((k_lap_view_out<PATH, W, ORDER>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), \
+    (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view)
+  if (path == 0) { if (wide) TSE_LAP_OUT(0, true, flat); else TSE_LAP_OUT(0, false, flat); }
+  else if (path == 1) { if (wide) TSE_LAP_OUT(1, true, tiles); else TSE_LAP_OUT(1, false, tiles); }
+  else TSE_LAP_OUT(2, false, flat);
+#undef TSE_LAP_OUT
+}
+
+int tse_biharmonic_view(tse_ctx* c, int nf, int nk, int order, const tse_view* in, const tse_view* out, void* stream) {
+  const char* who = "tse_biharmonic_view";
+  if (!c) return fail("%s: null context", who);
+  if (order != TSE_LAPLACE && order != TSE_BIHARMONIC)
+    return fail("%s: order=%d (1: out = laplace_sphere_wk(in); 2: out = laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(in))))", who, order);
+  ViewPlan p[2];
+  { std::string err; if (biharmonic_view_plan(c->nelemd, nf, nk, in, out, p, &err)) return fail("%s", err.c_str()); }
+  const size_t nl = (size_t)nf * nk;
+  if ((size_t)c->nelemd * nl >= ((size_t)1 << 27)) return fail("%s: %d elements x %zu layers (the launches count 32-bit blocks)", who, c->nelemd, nl);
+  const tse_view* v[2] = {in, out};
+  const std::vector<void*> mine = device_allocations(c);
+  for (int i = 0; i < 2; i++) {
+    void* alloc = nullptr;
+    if (view_runtime_checks(c, who, i ? "out" : "in", p[i], v[i], stream, &alloc)) return 1;
+    if (std::find(mine.begin(), mine.end(), alloc) != mine.end())
+      return fail("%s: %s: %p lies inside an allocation of the library; the call works on the host's own arrays", who, i ? "out" : "in", v[i]->ptr);
+  }
+  { std::string err; if (biharmonic_view_overlap(in, out, p, &err)) return fail("%s", err.c_str()); }
+  const bool exchange = order == TSE_BIHARMONIC && c->halo();
+  unsigned pack_blocks = 0;
+  if (exchange && c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
+  if (dss_view_buffers(c, nl)) return 1;
+  hipStream_t us = (hipStream_t)stream;
+  if (us && !c->view_ev[0])
+    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  const DssViewArgs ai = dss_view_args(nf, nk, in), ao = dss_view_args(nf, nk, out);
+
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
+  {
+    Scope sc(c, "fieldlap");
+    launch_lap_view_stage(c, p[0].path, dss_view_wide(p[0].path, in), ai, (const double*)in->ptr);
+    LAUNCH_CHECK();
+  }
+  if (exchange) {
+    CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
+    if (c->ncol_send) {
+      CommScope sc(c, "comm_pack_q", c->stream);
+      hipLaunchKernelGGL(k_pack<>, dim3(pack_blocks), dim3(256), 0, c->stream, c->ncol_send, (int)nl, c->send_src, (const double*)c->dv_stage, (const double*)nullptr,
+                         c->dv_send, (int)nl, 0, (int)nl);
+      LAUNCH_CHECK();
+    }
+    if (halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv)) return 1;
+  }
+  {
+    Scope sc(c, "fieldlap");
+    if (order == TSE_LAPLACE) launch_lap_view_out<1>(c, p[1].path, dss_view_wide(p[1].path, out), ao, (double*)out->ptr);
+    else launch_lap_view_out<2>(c, p[1].path, dss_view_wide(p[1].path, out), ao, (double*)out->ptr);
+    LAUNCH_CHECK();
+  }
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
+  else HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // ---- introspection ------------------------------------------------------------------------------
 void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   struct Ent { const char* n; void* p; size_t b; };
@@ -2051,7 +2141,8 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
                 {"omega_p", c->omega_p, lev}, {"dp3d", c->dp3d, lev}, {"ps_v", c->ps_v, (size_t)c->nelemd * 16 * 8}, {"q", c->qmix, trc}, {"lnps", c->lnps, (size_t)c->nelemd * 16 * 8}, {"qref", c->qref, lev}, {"qmin", c->qmin, mm},
                 {"qmax", c->qmax, mm}, {"sendbuf", c->sendbuf, (size_t)c->ncol_send * c->nlyr_halo * 8},
                 {"recvbuf", c->recvbuf, (size_t)c->ncol_recv * c->nlyr_halo * 8}, {"sendbuf_mm", c->sendbuf_mm, (size_t)c->nmm_send * m2},
-                {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}, {"remap_status", c->rv_status, (size_t)c->nelemd * REMAP_STATUS * sizeof(int)}};
+                {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}, {"remap_status", c->rv_status, (size_t)c->nelemd * REMAP_STATUS * sizeof(int)},
+                {"view_stage", c->dv_stage, (size_t)c->nelemd * c->dv_layers * 16 * 8}};   // (the staging field of tse_dss_view / tse_biharmonic_view: null before their first call)
   for (auto& e : ents) if (!strcmp(e.n, name)) { if (nbytes) *nbytes = e.p ? e.b : 0; return e.p; }
   if (nbytes) *nbytes = 0;
   return nullptr;

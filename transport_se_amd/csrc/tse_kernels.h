@@ -2983,4 +2983,166 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_dss_view_sum(int nelemd, DssVi
 // blocks of k_dss_view_sum<0 | 2>: 8 XCD ranges of ceil(nelemd / 8) element slots, `units` lanes per element
 inline long long dss_view_sum_blocks(int nelemd, long long units) { return 8 * ((((long long)((nelemd + 7) >> 3)) * units + VIEW_THREADS - 1) / VIEW_THREADS); }
 
+// ---- weak Laplacian and biharmonic of a host's own scalar fields through strided views (tse_biharmonic_view) ------------------------
+// ORDER 1: out = laplace_sphere_wk(in) (weak, not summed).  ORDER 2: out = laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(in))),
+// biharmonic_wk_scalar / biharmonic_wk_dp3d's scalar part (viscosity_mod.F90:229-279,315-344) before the final DSS, for nf fields of nk
+// levels.  The Laplacian is k_elem_op<1>'s -- load_row_geo, make_lap_geo, laplace_lean_row, a quad of lanes per slab, lane = row j -- and
+// the sum is k_dss_view_sum's (dss_view_point, then one product with rspheremp), so order 2 has the bits of
+// tse_laplace_sphere_wk -> tse_dss_view(WEAK) -> tse_laplace_sphere_wk.  Two launches for either order, four passes over the field:
+//   k_lap_view_stage<PATH, WIDE>       in -> lap -> stage[e][layer][16], a quad writes one 128-byte line
+//   (k_pack from the stage, halo_exchange: ORDER 2 on a rank with neighbours)
+//   k_lap_view_out<PATH, WIDE, ORDER>  ORDER 2: every lane gathers the four points of its row (own line, the neighbours' lines, the receive
+//                                      buffer), times rspheremp; the quad applies the second Laplacian -> out.  ORDER 1: own line -> out.
+// PATH and WIDE are those of the kernel's own view (the stage kernel's of `in`, the out kernel's of `out`), as in k_dss_view_stage:
+//   PATH 0  a lane's row is one 32-byte access (WIDE) or four 8-byte ones, a quad's slab one line;
+//   PATH 2  one address per entry;
+//   PATH 1  block = (element, field): the view side passes through the LDS image tile[p][VIEW_PITCH] (dss_rows_to_tile /
+//           dss_tile_to_rows), quad q of the block takes the levels q, q + 64, ...
+// On paths 0 and 2 a thread keeps its LapGeo (20 doubles, formed from 36 loaded ones) over LAP_VIEW_LAYERS consecutive layers of its
+// element.  Whole quads stay active (quad_matvec moves data across the quad): element and layer indices are clamped and only the
+// store is predicated; every predicate is the same for the four lanes of a quad.
+#ifndef TSE_LAP_VIEW_LAYERS
+#define TSE_LAP_VIEW_LAYERS 4   // (profiles/biharmonic_view_rate.txt holds the comparison of 1, 2, 4 and 8)
+#endif
+constexpr int LAP_VIEW_LAYERS = TSE_LAP_VIEW_LAYERS;
+
+template <int PATH, bool WIDE>
+__device__ __forceinline__ void lap_view_load_row(const double* __restrict__ V, const DssViewArgs& a, int j, double s[4]) {
+  if (PATH == 0 && WIDE) load4(V + 4 * j, s);
+  else if (PATH == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) s[i] = V[4 * j + i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) s[i] = V[j * a.vs[3] + i * a.vs[4]];
+  }
+}
+template <int PATH, bool WIDE>
+__device__ __forceinline__ void lap_view_store_row(double* __restrict__ V, const DssViewArgs& a, int j, const double r[4]) {
+  if (PATH == 0 && WIDE) store4(V + 4 * j, r);
+  else if (PATH == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) V[4 * j + i] = r[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) V[j * a.vs[3] + i * a.vs[4]] = r[i];
+  }
+}
+inline long long lap_view_groups(long long nl) { return (nl + LAP_VIEW_LAYERS - 1) / LAP_VIEW_LAYERS; }
+
+template <int PATH, bool WIDE>
+__global__ __launch_bounds__(VIEW_THREADS) void k_lap_view_stage(int nelemd, DssViewArgs a, Dvv_t D, GeoPtrs G, const double* __restrict__ view,
+                                                                 double* __restrict__ stage) {
+#pragma clang fp contract(off)
+  const int nl = a.nf * a.nk, tid = threadIdx.x, j = tid & 3;
+  RowGeo g;
+  LapGeo L;
+  if (PATH == 1) {
+    __shared__ __attribute__((aligned(16))) double tile[16 * VIEW_PITCH];
+    constexpr int K = NLEV;
+    const int f = (int)(blockIdx.x % (unsigned)a.nf), e = (int)(blockIdx.x / (unsigned)a.nf);   // (the grid is nelemd * nf blocks)
+    load_row_geo(g, G.dvv, G.Dinv, G.metdet, G.rmetdet, G.spheremp, e, j);
+    make_lap_geo(L, g);
+    dss_rows_to_tile<WIDE, K>(view + (long long)e * a.vs[0] + f * a.vs[1], a.vs[4], tile, tid);
+    __syncthreads();
+    double* S = stage + ((size_t)e * nl + (size_t)f * K) * 16 + 4 * j;
+    for (int k = tid >> 2; k < K; k += VIEW_THREADS / 4) {
+      double s[4], r[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) s[i] = tile[(4 * j + i) * VIEW_PITCH + k];
+      laplace_lean_row(D, L, s, r);
+      store4(S + (size_t)k * 16, r);
+    }
+  } else {
+    const int groups = (nl + LAP_VIEW_LAYERS - 1) / LAP_VIEW_LAYERS;
+    const size_t qd = ((size_t)blockIdx.x * VIEW_THREADS + tid) >> 2;
+    const size_t eraw = qd / (unsigned)groups;
+    const int grp = (int)(qd - eraw * (unsigned)groups);
+    const bool live = eraw < (size_t)nelemd;
+    const int e = live ? (int)eraw : nelemd - 1;
+    load_row_geo(g, G.dvv, G.Dinv, G.metdet, G.rmetdet, G.spheremp, e, j);
+    make_lap_geo(L, g);
+    const int l0 = grp * LAP_VIEW_LAYERS;
+#pragma unroll
+    for (int u = 0; u < LAP_VIEW_LAYERS; u++) {
+      const int layer = min(l0 + u, nl - 1);
+      const int f = layer / a.nk, k = layer - f * a.nk;
+      double s[4], r[4];
+      lap_view_load_row<PATH, WIDE>(view + (long long)e * a.vs[0] + f * a.vs[1] + k * a.vs[2], a, j, s);
+      laplace_lean_row(D, L, s, r);
+      if (live && l0 + u < nl) store4(stage + ((size_t)e * nl + layer) * 16 + 4 * j, r);
+    }
+  }
+}
+
+template <int PATH, bool WIDE, int ORDER>
+__global__ __launch_bounds__(VIEW_THREADS) void k_lap_view_out(int nelemd, DssViewArgs a, Dvv_t D, GeoPtrs G, const int2* __restrict__ tab,
+                                                               const double* __restrict__ stage, const double* __restrict__ recvbuf,
+                                                               const int* __restrict__ order, double* __restrict__ view) {
+#pragma clang fp contract(off)
+  const int nl = a.nf * a.nk, tid = threadIdx.x, j = tid & 3;
+  const int S8 = (nelemd + 7) >> 3, xcd = blockIdx.x & 7;   // contiguous ranges of `order` per XCD, as in k_dss_view_sum
+  const unsigned it = blockIdx.x >> 3;
+  RowGeo g;
+  LapGeo L;
+  if (PATH == 1) {
+    __shared__ __attribute__((aligned(16))) double tile[16 * VIEW_PITCH];
+    constexpr int K = NLEV;
+    const int idx = (int)(it / (unsigned)a.nf), f = (int)(it % (unsigned)a.nf), slot = xcd * S8 + idx;
+    if (idx >= S8 || slot >= nelemd) return;   // (uniform over the block: before the barrier)
+    const int e = order[slot];
+    if (ORDER == 2) {
+      load_row_geo(g, G.dvv, G.Dinv, G.metdet, G.rmetdet, G.spheremp, e, j);
+      make_lap_geo(L, g);
+    }
+    for (int k = tid >> 2; k < K; k += VIEW_THREADS / 4) {
+      double m[4], r[4];
+      if (ORDER == 2) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          double rs;
+          const double x = dss_view_point(tab, stage, recvbuf, nl, e, 4 * j + i, f * K + k, rs, G.rspheremp);
+          m[i] = rs * x;
+        }
+        laplace_lean_row(D, L, m, r);
+      } else load4(stage + ((size_t)e * nl + (size_t)f * K + k) * 16 + 4 * j, r);
+#pragma unroll
+      for (int i = 0; i < 4; i++) tile[(4 * j + i) * VIEW_PITCH + k] = r[i];
+    }
+    __syncthreads();
+    dss_tile_to_rows<WIDE, K>(tile, view + (long long)e * a.vs[0] + f * a.vs[1], a.vs[4], tid);
+  } else {
+    const int groups = (nl + LAP_VIEW_LAYERS - 1) / LAP_VIEW_LAYERS;
+    const long long qd = ((long long)it * VIEW_THREADS + tid) >> 2;
+    const long long idx = qd / groups;
+    const int grp = (int)(qd - idx * groups);
+    const long long slot = (long long)xcd * S8 + idx;
+    const bool live = idx < S8 && slot < nelemd;
+    const int e = order[live ? slot : nelemd - 1];
+    if (ORDER == 2) {
+      load_row_geo(g, G.dvv, G.Dinv, G.metdet, G.rmetdet, G.spheremp, e, j);
+      make_lap_geo(L, g);
+    }
+    const int l0 = grp * LAP_VIEW_LAYERS;
+#pragma unroll
+    for (int u = 0; u < LAP_VIEW_LAYERS; u++) {
+      const int layer = min(l0 + u, nl - 1);
+      const int f = layer / a.nk, k = layer - f * a.nk;
+      double m[4], r[4];
+      if (ORDER == 2) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          double rs;
+          const double x = dss_view_point(tab, stage, recvbuf, nl, e, 4 * j + i, layer, rs, G.rspheremp);
+          m[i] = rs * x;
+        }
+        laplace_lean_row(D, L, m, r);
+      } else load4(stage + ((size_t)e * nl + layer) * 16 + 4 * j, r);
+      if (live && l0 + u < nl) lap_view_store_row<PATH, WIDE>(view + (long long)e * a.vs[0] + f * a.vs[1] + k * a.vs[2], a, j, r);
+    }
+  }
+}
+// blocks of k_lap_view_out<0 | 2>: 8 XCD ranges of ceil(nelemd / 8) element slots, one quad per LAP_VIEW_LAYERS layers of an element
+inline long long lap_view_out_blocks(int nelemd, long long nl) { return dss_view_sum_blocks(nelemd, 4 * lap_view_groups(nl)); }
+
 }  // namespace tse

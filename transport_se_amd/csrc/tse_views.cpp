@@ -141,8 +141,7 @@ int remap_view_overlap(const tse_view* field, const tse_view* dp_src, const tse_
 // tse_dss_view's view: the rules of a "qdp" get view (written in place) with nf field slots on the q axis and nk levels; an axis of extent
 // 1 may carry any stride, 0 included.  The dense side is the staging field [e][f * nk + k][16].  Path 1 exists for nk == NLEV alone: a
 // level-fastest view of another depth takes the generic path, and the plan says so.
-int dss_view_plan(int nelemd, int nf, int nk, const tse_view* v, ViewPlan* out, std::string* err) {
-  const char* who = "tse_dss_view";
+int dss_view_plan(int nelemd, int nf, int nk, const tse_view* v, ViewPlan* out, std::string* err, const char* who) {
   if (!v || !out) return refuse(err, "%s: null %s", who, !v ? "view" : "plan");
   if (nelemd <= 0) return refuse(err, "%s: nelemd = %d", who, nelemd);
   if (nf < 1) return refuse(err, "%s: nf = %d (at least one field)", who, nf);
@@ -159,6 +158,36 @@ int dss_view_plan(int nelemd, int nf, int nk, const tse_view* v, ViewPlan* out, 
   if (footprint_and_path(who, p, s, true, true, err)) return 1;
   if (p.path == 1 && nk != NLEV) p.path = 2;
   *out = p;
+  return 0;
+}
+
+// tse_biharmonic_view's two views: each a view of tse_dss_view (dss_view_plan).  biharmonic_view_overlap: `out` is `in` itself (the same
+// pointer and the same five strides: in place) or its footprint, taken from its ptr, does not meet in's -- the first kernel reads `in`
+// whole before the second writes `out`, but a partial overlap would leave a field that is neither the input nor the result.
+int biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err) {
+  const char* who = "tse_biharmonic_view";
+  if (!in || !out_view || !out) return refuse(err, "%s: null view", who);
+  const tse_view* v[2] = {in, out_view};
+  for (int i = 0; i < 2; i++) {
+    std::string e;
+    if (dss_view_plan(nelemd, nf, nk, v[i], &out[i], &e, who)) return refuse(err, "%s (%s)", e.c_str(), i == 0 ? "in" : "out");
+  }
+  return 0;
+}
+
+bool biharmonic_view_in_place(const tse_view* in, const tse_view* out) {
+  if (in->ptr != out->ptr) return false;
+  for (int a = 0; a < 5; a++) if (in->stride[a] != out->stride[a]) return false;
+  return true;
+}
+
+int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err) {
+  if (biharmonic_view_in_place(in, out)) return 0;
+  const __int128 f0 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].lo * 8, f1 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].hi * 8;
+  const __int128 g0 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].lo * 8, g1 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].hi * 8;
+  if (f0 < g1 && g0 < f1)
+    return refuse(err, "tse_biharmonic_view: out [%p%+lld, %p%+lld doubles) overlaps in [%p%+lld, %p%+lld doubles) without being the same view (the same "
+                  "pointer and strides: in place)", out->ptr, plan[1].lo, out->ptr, plan[1].hi, in->ptr, plan[0].lo, in->ptr, plan[0].hi);
   return 0;
 }
 
@@ -196,5 +225,19 @@ extern "C" int tse_dss_view_plan(int nelemd, int nf, int nk, const tse_view* fie
   if (path) *path = p.path;
   if (lo) *lo = p.lo;
   if (hi) *hi = p.hi;
+  return 0;
+}
+
+extern "C" int tse_biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out, int path[2], long long lo[2], long long hi[2]) {
+  tse::ViewPlan p[2];
+  std::string err;
+  if (tse::biharmonic_view_plan(nelemd, nf, nk, in, out, p, &err)) return tse::set_last_error(err.c_str());
+  // strides alone (both ptr null): nothing is known of where the views lie
+  if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err)) return tse::set_last_error(err.c_str());
+  for (int i = 0; i < 2; i++) {
+    if (path) path[i] = p[i].path;
+    if (lo) lo[i] = p[i].lo;
+    if (hi) hi[i] = p[i].hi;
+  }
   return 0;
 }

@@ -32,7 +32,15 @@ int remap_view_overlap(const tse_view* field, const tse_view* dp_src, const tse_
 
 // The view of tse_dss_view / tse_dss_view_plan: nf field slots of nk levels (1 <= nk <= NLEVP), the rules of a "qdp" get view except that an
 // axis of extent 1 may carry stride 0.  lib[] are the strides of the staging field [e][f * nk + k][16]; path 1 only for nk == NLEV.
-int dss_view_plan(int nelemd, int nf, int nk, const tse_view* field, ViewPlan* out, std::string* err);
+// who: the entry the refusals name.
+int dss_view_plan(int nelemd, int nf, int nk, const tse_view* field, ViewPlan* out, std::string* err, const char* who = "tse_dss_view");
+
+// The two views of tse_biharmonic_view / tse_biharmonic_view_plan -> out[0..1] = the plans of in, out: each a view of tse_dss_view.
+// biharmonic_view_in_place: out is the same pointer and the same five strides as in.  biharmonic_view_overlap: otherwise the two
+// footprints, each taken from its ptr, are disjoint (touching is disjoint).
+int biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err);
+bool biharmonic_view_in_place(const tse_view* in, const tse_view* out);
+int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err);
 
 // the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
 int set_last_error(const char* msg);

@@ -58,6 +58,9 @@ module cuda_mod
   ! DSS of the host's own device-resident fields (tse_dss_view)
   public :: dss_view_hip
   integer, parameter, public :: dss_average = 0, dss_weak = 1   ! TSE_DSS_AVERAGE, TSE_DSS_WEAK
+  ! weak Laplacian / biharmonic of the host's own device-resident scalar fields (tse_biharmonic_view)
+  public :: biharmonic_view_hip
+  integer, parameter, public :: lap_order1 = 1, lap_order2 = 2   ! TSE_LAPLACE, TSE_BIHARMONIC
   logical, save :: remap_refused = .false.            ! remap_view_hip / remap_view_status_hip: the master thread's answer, read by every thread
   integer(c_int), save :: remap_nrefused = 0, remap_where(4) = 0
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
@@ -206,6 +209,10 @@ module cuda_mod
      integer(c_int) function tse_dss_view(ctx, nf, nk, mode, field, stream) bind(C, name='tse_dss_view')
        import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nf, nk, mode
        type(tse_view), intent(in) :: field
+     end function
+     integer(c_int) function tse_biharmonic_view(ctx, nf, nk, order, vin, vout, stream) bind(C, name='tse_biharmonic_view')
+       import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nf, nk, order
+       type(tse_view), intent(in) :: vin, vout
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -885,5 +892,25 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine dss_view_hip
+
+  ! out(:,:,1:nk,1:nf) at out_ptr <- laplace_sphere_wk of field(:,:,1:nk,1:nf) of the host's DEVICE array at ptr (order lap_order1: weak,
+  ! not summed, no exchange) or laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(field))) (lap_order2: biharmonic_wk_scalar before its
+  ! final DSS; include/transport_se_hip.h: tse_biharmonic_view).  strides(1:5) and out_strides(1:5) in doubles for element, q, level, j, i.
+  ! out_ptr and out_strides equal to ptr and strides: in place; otherwise the two arrays may not overlap.  nk: 1 to nlev + 1 levels.
+  ! COLLECTIVE for lap_order2: every rank calls with the same nf and nk.  The host scales by -nu*dt and follows with
+  ! dss_view_hip(..., dss_weak, ...).  stream as in view_put_hip.  A refusal aborts.
+  subroutine biharmonic_view_hip(nf, nk, order, ptr, strides, out_ptr, out_strides, stream)
+    integer,              intent(in) :: nf, nk, order
+    type(c_ptr),          intent(in) :: ptr, out_ptr, stream
+    integer(c_long_long), intent(in) :: strides(5), out_strides(5)
+    type(tse_view) :: vi, vo
+    vi%ptr = ptr; vi%stride = strides
+    vo%ptr = out_ptr; vo%stride = out_strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_biharmonic_view(ctx, int(nf,c_int), int(nk,c_int), int(order,c_int), vi, vo, stream), 'biharmonic_view_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine biharmonic_view_hip
 
 end module cuda_mod

@@ -167,11 +167,11 @@ def _dss_mode(mode):
     return int(mode)
 
 
-def build_dss_view(array, axes, nelemd):
+def build_dss_view(array, axes, nelemd, who="dss_view", written=True):
     """(_lib.View, nf, nk) of `array` -- anything with __cuda_array_interface__ -- for dss_view: its dimensions are named, in order, by the
     letters of `axes` over e q k j i; e, j and i are needed, a missing q or k letter means extent 1 and stride 0; nf and nk are the
-    array's own extents.  Raises TseError as build_view does.  The device is not touched."""
-    who = "dss_view"
+    array's own extents.  Raises TseError as build_view does.  The device is not touched.  who: the call the messages name;
+    written=False: an array that is only read may be read-only."""
     cai = getattr(array, "__cuda_array_interface__", None)
     if cai is None:
         raise TseError("%s: the array has no __cuda_array_interface__ (a device array is needed)" % who)
@@ -190,7 +190,7 @@ def build_dss_view(array, axes, nelemd):
     if len(shape) != len(axes):
         raise TseError("%s: %d axes named for an array of %d dimensions" % (who, len(axes), len(shape)))
     ptr, readonly = cai["data"]
-    if readonly:
+    if readonly and written:
         raise TseError("%s: the array is read-only and would be written in place" % who)
     strides = cai.get("strides")
     if strides is None:   # C-contiguous
@@ -220,6 +220,33 @@ def dss_view_plan(nelemd, nf, nk, field, nlev=None):
     if L.tse_dss_view_plan(int(nelemd), int(nf), int(nk), v, C.byref(path), C.byref(lo), C.byref(hi)):
         raise TseError(L.tse_last_error().decode())
     return dict(path=path.value, lo=lo.value, hi=hi.value)
+
+
+LAP_ORDERS = {"laplace": 1, "biharmonic": 2}   # TSE_LAPLACE, TSE_BIHARMONIC
+
+
+def _lap_order(order):
+    """the order names, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(order, str):
+        if order not in LAP_ORDERS:
+            raise TseError("biharmonic_view: unknown order %r (the orders are %s)" % (order, ", ".join(LAP_ORDERS)))
+        return LAP_ORDERS[order]
+    return int(order)
+
+
+def biharmonic_view_plan(nelemd, nf, nk, field, out=None, nlev=None):
+    """tse_biharmonic_view_plan: [dict(path=, lo=, hi=)] of the two views of HipMod.biharmonic_view, in and out -- each a _lib.View, its
+    five strides (doubles, in the order of VIEW_AXES), or a pair (strides, address) so that the overlap rule is tested as well; out=None:
+    in place (the same view).  Needs no device.  Raises TseError for views biharmonic_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    raw = lambda x: _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
+    vi = None if field is None else raw(field)
+    vo = vi if out is None else raw(out)
+    path, lo, hi = (C.c_int * 2)(), (C.c_longlong * 2)(), (C.c_longlong * 2)()
+    if L.tse_biharmonic_view_plan(int(nelemd), int(nf), int(nk), None if vi is None else C.byref(vi), None if vo is None else C.byref(vo),
+                                  C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
 
 
 class HipMod:
@@ -609,6 +636,33 @@ class HipMod:
         else:
             v, nf, nk = build_dss_view(field, axes, self.nelemd)
         self._chk(self.L.tse_dss_view(self.h, int(nf), int(nk), _dss_mode(mode), C.byref(v), _stream_handle(stream)))
+
+    # ---- weak Laplacian / biharmonic of the host's own scalar fields (tse_biharmonic_view) ----
+    def biharmonic_view(self, field, axes, out=None, out_axes=None, order=2, stream=None, nf=None, nk=None):
+        """out <- laplace_sphere_wk(field) (order 1 or "laplace": weak, not summed, no exchange) or
+        laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(field))) (order 2 or "biharmonic": the reference's biharmonic_wk_scalar before
+        the final DSS) on every layer of the device array `field`: nf fields of nk levels, the array's own extents along the letters q and
+        k of `axes` (a missing letter: extent 1).  out=None: in place; otherwise another device array of the same nf and nk whose axes
+        `out_axes` names (default: `axes`), disjoint from `field`.  The bits are those of laplace_sphere_wk -> dss_view(mode="weak") ->
+        laplace_sphere_wk on every path of either view and on any number of ranks.  Order 2 is COLLECTIVE on a context with neighbour
+        ranks, as dss_view.  Nothing of the library's state is touched.  stream orders as in put.  `field` and `out` may also be ready
+        _lib.Views (then nf and nk are needed)."""
+        who = "biharmonic_view"
+        if isinstance(field, _lib.View):
+            if nf is None or nk is None:
+                raise TseError("%s: nf and nk are needed with a ready view" % who)
+            vi = field
+        else:
+            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=out is None)
+        if out is None:
+            vo = vi
+        elif isinstance(out, _lib.View):
+            vo = out
+        else:
+            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
+            if (onf, onk) != (nf, nk):
+                raise TseError("%s: out has %d fields of %d levels, field has %d of %d" % (who, onf, onk, nf, nk))
+        self._chk(self.L.tse_biharmonic_view(self.h, int(nf), int(nk), _lap_order(order), C.byref(vi), C.byref(vo), _stream_handle(stream)))
 
     def last_error(self):
         return self.L.tse_last_error().decode()
