@@ -67,7 +67,10 @@ typedef struct {
                           8: one clip to them, the clipped mass redistributed in proportion to the room left; qmin is not clamped
                           at 0); 0: no limiter (control_mod's default).  Every other value is refused.  With 0 no tracer bounds are
                           kept: tse_get_qminmax fails. */
-  int rsplit;          /* control_mod rsplit (vertical remap frequency), informational */
+  int rsplit;          /* control_mod rsplit (vertical remap frequency): the tracer steps per remap cycle of tse_prim_run_subcycle, the only
+                          entry that reads it (the step-by-step entries leave the remap to the caller).  tse_init accepts any value; on a
+                          context with rsplit < 1 (the reference's default is 0) tse_prim_run_subcycle returns nonzero with a message
+                          and launches nothing */
   const double *Dvv;   /* deriv%Dvv(np,np), Fortran order */
   const double *hyai;  /* hvcoord%hyai(nlevp) */
   const double *hybi;  /* hvcoord%hybi(nlevp) */
@@ -159,7 +162,9 @@ int tse_qdp_time_avg(tse_ctx *ctx, int rkstage, int n0_qdp, int np1_qdp);
 int tse_vertical_remap(tse_ctx *ctx, double dt, int np1_qdp);
 /* The library caches the element min/max of Qdp(np1)/dp that the last kernel of a tracer step emits and reuses them as
  * the next step's first-stage bounds (prim_advection_mod.F90:765-779 recomputes them).  Every entry point that changes
- * Qdp or dp drops the cache; a caller that writes state through tse_device_ptr must call this itself. */
+ * Qdp or dp drops the cache -- tse_dcmip_step_inputs and tse_prim_run_subcycle too, whenever they replace a dp that another entry wrote
+ * (tse_set_derived, tse_view_put, tse_remap_q_ppm) by the prescribed one; a caller that writes state through tse_device_ptr must call
+ * this itself. */
 int tse_invalidate_cache(tse_ctx *ctx);
 
 /* Single calls of the public routines the path is built from, on host arrays (one call covers every local element):
@@ -194,6 +199,7 @@ int tse_dcmip_set_initial(tse_ctx *ctx);
 int tse_dcmip_step_inputs(tse_ctx *ctx, int nstep, double tstep);
 /* prim_run_subcycle x nsub: rsplit x (step inputs + tracer step) + vertical_remap; *nstep is tl%nstep in/out.  *nstep may lie inside
  * an rsplit cycle (steps taken through tse_advec_tracers_remap_rk2): the first of the nsub cycles then completes that cycle.
+ * Refused (nonzero, tse_last_error(), nothing launched, *nstep unchanged) on a context initialised with rsplit < 1.
  * Returns 2 on "negative layer thickness" (prim_advection_mod.F90:1323) with *nstep = the step count at the end of the FIRST
  * failing cycle; the flag is polled two cycles behind the launches (the host never waits for the device), so up to two
  * further cycles may have been started on the bad state.  Several ranks: escalate as for tse_vertical_remap. */

@@ -1572,7 +1572,11 @@ static int dcmip_step_launch(tse_ctx* c, int nstep, double tstep, hipStream_t st
   size_t tot = (size_t)c->nelemd * 16;   // one thread per column
   double t_wind = (nstep > 0 ? nstep - 1 : 0) * tstep, t_now = nstep * tstep;
   // derived%dp is rewritten with the same time-independent p_i(k+1) - p_i(k) on every step (dcmip_wrapper_mod.F90:183,199), so
-  // the cached next-step bounds (formed with that dp) stay valid; every other writer of dp drops them (tse_set_derived)
+  // the cached next-step bounds (formed with that dp) stay valid; every other writer of dp drops them (tse_set_derived).  That holds
+  // only while dp IS the prescribed one (dcmip_static).  Otherwise this launch replaces the dp another writer left (tse_set_derived,
+  // tse_view_put, tse_remap_q_ppm), and bounds a step or a remap emitted in between were formed with that other dp: they go, with their
+  // prefetched halo.  (Q / lnps depend on Qdp and ps_v alone and stay fresh.)
+  if (!c->dcmip_static) { c->mm_valid = 0; c->mm_halo = 0; }
   hipLaunchKernelGGL(k_dcmip_step<>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, c->nelemd, c->dcmip_test, t_wind, t_now,
                      c->lat, c->lon, c->dcmip_tab, c->pint, c->vn0, c->dcmip_static ? nullptr : c->dp, c->eta, c->dcmip_static ? nullptr : c->omega_p);
   LAUNCH_CHECK();
@@ -1581,6 +1585,11 @@ static int dcmip_step_launch(tse_ctx* c, int nstep, double tstep, hipStream_t st
 }
 int tse_dcmip_step_inputs(tse_ctx* c, int nstep, double tstep) { return join_inputs(c) || dcmip_step_launch(c, nstep, tstep, c->stream); }
 int tse_prim_run_subcycle(tse_ctx* c, double tstep, int nsub, int* nstep_io) {
+  if (!c || !nstep_io) return fail("tse_prim_run_subcycle: null argument");
+  // rsplit is the cycle length below (a modulus and a trip count): the reference's default rsplit = 0 (no vertically Lagrangian cycle,
+  // control_mod.F90) has no meaning for this loop and is refused before anything is launched or any state is touched
+  if (c->rsplit < 1)
+    return fail("tse_prim_run_subcycle: rsplit = %d (tse_init_args), the loop needs rsplit >= 1 tracer steps per remap cycle", c->rsplit);
   c->dss_deferred_n0 = 0;
   const int nstep0 = *nstep_io;
   int nstep = nstep0;
