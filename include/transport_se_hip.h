@@ -398,6 +398,42 @@ int tse_biharmonic_view(tse_ctx *ctx, int nf, int nk, int order, const tse_view 
 int tse_biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view *in, const tse_view *out,
                              int path[2], long long lo[2], long long hi[2]);
 
+/* ---- weak vector Laplacian and biharmonic of a GPU-resident host's OWN wind: the vector half of its hyperviscosity, the reference's
+ * vlaplace_sphere_wk in its constant-coefficient branch vlaplace_sphere_wk_contra (derivative_mod.F90:2545-2591, hypervis_scaling == 0) and
+ * the wind's line of biharmonic_wk_dp3d (viscosity_mod.F90:177-286), on nk levels of the two components of one view, 1 <= nk <= nlev + 1 ----
+ *   lap(v) = gradient_sphere_wk_testcov(nu_ratio * divergence_sphere(v)) - curl_sphere_wk_testcov(vorticity_sphere(v))
+ *            + 2 * spheremp * v * rrearth^2                       (rigid rotation is not damped)
+ *   order TSE_VLAPLACE     out = lap(in): weak (it carries spheremp), not summed over elements; no exchange, not collective
+ *   order TSE_VBIHARMONIC  w = lap(in);  m_c[p] = rspheremp[e][p] * (((w_c + c0) + c1) + c2) per component, tse_dss_view's TSE_DSS_WEAK sum over
+ *                          2 * nk layers;  out = lap(m).  nu_ratio multiplies div in BOTH Laplacians (the reference's nu_ratio1 = nu_ratio2
+ *                          for hypervis_scaling == 0, its "applied twice"); the product is always formed, with 1.0 it changes no bit.  Two
+ *                          different ratios: order 1, tse_dss_view(TSE_DSS_WEAK, nf = 2), order 1.
+ * tse_vector_setup brings the three element fields the operator needs and tse_init_args does not carry: elem(ie)%D(2,2,np,np),
+ * elem(ie)%metinv(2,2,np,np), elem(ie)%mp(np,np), each as the address of elem(1)%X and the byte stride to elem(2)%X.  They are copied to the
+ * device and folded there, once, with the library's Dinv, metdet, rmetdet and spheremp into 14 tables per point (csrc/tse_device.h:
+ * vlaplace_row), so the metric products are re-associated and the result need not have the reference's bits.  What holds: the routine is
+ * compiled without implicit contraction, so a point's result is one fixed sequence of roundings -- it does not depend on the path of either
+ * view, on the other levels of the call, on the slab's neighbours in the wavefront or on the number of ranks -- and order 2 has the bits of
+ * order 1 -> tse_dss_view(TSE_DSS_WEAK, nf = 2) -> order 1.  tse_vector_setup may be called again; it completes on return.
+ * Views: `in` and `out` are views of tse_dss_view with nf = 2; the q axis is the wind component, as for "vn0" (E3SM's
+ * state%v(np,np,2,nlev,tl): component stride 16, level stride 32, one call per time level).  Each takes its own path; out is the same view
+ * as in (in place) or has a disjoint footprint; only the addresses of out are written.  Everything tse_biharmonic_view refuses is refused
+ * here, and besides: a call before tse_vector_setup, an nu_ratio that is not finite.  On failure: nonzero, tse_last_error(), nothing enqueued.
+ * The result is the weak tendency BEFORE the final DSS: the host multiplies by -nu * dt and follows with tse_dss_view(TSE_DSS_WEAK).
+ * Not part of this entry: the tensor / cartesian branch (hypervis_scaling > 0), variable_hyperviscosity, subcell_Laplace_fluxes.
+ * No library state is read or written except the tables of tse_vector_setup; the staging and halo buffers are tse_dss_view's ("view_stage",
+ * grown when a call brings more layers, here 2 * nk), so a steady-state call allocates nothing.  COLLECTIVE for order 2 on a context with
+ * neighbour ranks (exchange kind 0 with 2 * nk layers); order 1 never exchanges.  stream orders as in tse_dss_view.
+ * Timer group "fieldvlap" (two launches per call for either order: the stage kernel, in -> first Laplacian -> staging field, and the out
+ * kernel, staging field -> [sum, rspheremp, second Laplacian] -> out); pack and exchange count under comm_pack_q / comm_exchange_q / comm_wait. */
+int tse_vector_setup(tse_ctx *ctx, const double *D, size_t D_stride, const double *metinv, size_t metinv_stride,
+                     const double *mp, size_t mp_stride);
+#define TSE_VLAPLACE    1   /* out = vlaplace_sphere_wk(in): weak, not summed; no exchange, not collective */
+#define TSE_VBIHARMONIC 2   /* out = vlaplace_sphere_wk(rspheremp * DSS(vlaplace_sphere_wk(in))): collective like tse_dss_view */
+int tse_vlaplace_view(tse_ctx *ctx, int nk, int order, double nu_ratio, const tse_view *in, const tse_view *out, void *stream);
+/* the paths and footprints of in ([0]) and out ([1]) and every refusal that needs no device, as tse_biharmonic_view_plan with nf = 2 */
+int tse_vlaplace_view_plan(int nelemd, int nk, const tse_view *in, const tse_view *out, int path[2], long long lo[2], long long hi[2]);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -438,12 +474,12 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
 /* device pointers of internal fields: "qdp1", "qdp2" [nelemd][qsize][nlev][16] (the two time levels are two allocations), "vn0", "dp", "divdp", "divdp_proj",
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
  * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference),
- * "remap_status" [nelemd][4] ints (null before the first tse_remap_view), "view_stage" [nelemd][layers][16] the staging field tse_dss_view and
- * tse_biharmonic_view share (null before the first call of either; it moves only when a call brings more layers than any before) */
+ * "remap_status" [nelemd][4] ints (null before the first tse_remap_view), "view_stage" [nelemd][layers][16] the staging field tse_dss_view,
+ * tse_biharmonic_view and tse_vlaplace_view share (null before the first call of any; it moves only when a call brings more layers than any before) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -108,6 +108,9 @@ struct tse_ctx {
   // rank with neighbours, its own send and receive buffers [columns][dv_layers] -- the context's own are sized by qsize
   double *dv_stage = nullptr, *dv_send = nullptr, *dv_recv = nullptr;
   size_t dv_layers = 0;
+  // tse_vector_setup: the per-point tables of the vector Laplacian, [nelemd][VEC_TABS][16] (k_vec_fold; allocated by its first call)
+  double* vec_tab = nullptr;
+  bool vec_ready = false;
   // halo: one slot per neighbour rank (Schedule(1)%SendCycle/RecvCycle), entries per slot for the two exchange kinds
   int ncol_send = 0, ncol_recv = 0, nlyr_halo = 0;
   int nmm_send = 0, nmm_recv = 0;              // entries of the compact min/max exchange
@@ -499,7 +502,7 @@ static std::vector<void*> device_allocations(const tse_ctx* c) {
                   c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
                   c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->norm_owner, c->norm_colw, c->norm_dh, c->qref, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
                   c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int,
-                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc, c->dv_stage, c->dv_send, c->dv_recv};
+                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc, c->dv_stage, c->dv_send, c->dv_recv, c->vec_tab};
   std::vector<void*> out;
   for (void* p : ptrs) if (p) out.push_back(p);
   return out;
@@ -2133,6 +2136,110 @@ int tse_biharmonic_view(tse_ctx* c, int nf, int nk, int order, const tse_view* i
     Scope sc(c, "fieldlap");
     if (order == TSE_LAPLACE) launch_lap_view_out<1>(c, p[1].path, dss_view_wide(p[1].path, out), ao, (double*)out->ptr);
     else launch_lap_view_out<2>(c, p[1].path, dss_view_wide(p[1].path, out), ao, (double*)out->ptr);
+    LAUNCH_CHECK();
+  }
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
+  else HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- weak vector Laplacian / biharmonic of a resident host's own wind (k_vec_fold, k_vlap_view_stage, k_vlap_view_out: tse_kernels.h) ----
+// tse_vector_setup: elem%D, elem%metinv, elem%mp -> [e][p][9] on the device -> the folded tables (allocated once; a later call overwrites them)
+int tse_vector_setup(tse_ctx* c, const double* D, size_t D_stride, const double* metinv, size_t metinv_stride, const double* mp, size_t mp_stride) {
+  if (!c) return fail("tse_vector_setup: null context");
+  if (!D || !metinv || !mp) return fail("tse_vector_setup: null argument");
+  const int n = c->nelemd;
+  std::vector<double> d, m, w, h((size_t)n * 16 * 9);
+  gather_strided(d, D, D_stride, n, 64);
+  gather_strided(m, metinv, metinv_stride, n, 64);
+  gather_strided(w, mp, mp_stride, n, 16);
+  for (size_t t = 0; t < (size_t)n * 16; t++) {
+    for (int k = 0; k < 4; k++) { h[t * 9 + k] = d[t * 4 + k]; h[t * 9 + 4 + k] = m[t * 4 + k]; }
+    h[t * 9 + 8] = w[t];
+  }
+  if (!c->vec_tab && dalloc(&c->vec_tab, (size_t)n * VEC_TABS * 16)) return 1;
+  c->vec_ready = false;
+  HIPCHK(hipStreamSynchronize(c->stream));   // (a kernel still running reads the old tables)
+  double* src = nullptr;
+  if (upload(&src, h)) return 1;
+  hipLaunchKernelGGL(k_vec_fold<>, dim3((unsigned)(((size_t)n * 16 + 255) / 256)), dim3(256), 0, c->stream, n, c->geo(), (const double*)src, c->vec_tab);
+  const hipError_t launched = hipGetLastError(), done = hipStreamSynchronize(c->stream);
+  (void)hipFree(src);
+  HIPCHK(launched); HIPCHK(done);
+  c->vec_ready = true;
+  return 0;
+}
+static void launch_vlap_view_stage(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double nu_ratio, const double* view) {
+  const long long quads = (long long)c->nelemd * vlap_view_groups(a.nk);
+  const dim3 flat((unsigned)((quads * 4 + VIEW_THREADS - 1) / VIEW_THREADS)), tiles((unsigned)c->nelemd);
+#define TSE_VLAP_STAGE(PATH, W, grid) hipLaunchKernelGGL((k_vlap_view_stage<PATH, W>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), \
+    (const double*)c->vec_tab, nu_ratio, view, c->dv_stage)
+  if (path == 0) { if (wide) TSE_VLAP_STAGE(0, true, flat); else TSE_VLAP_STAGE(0, false, flat); }
+  else if (path == 1) { if (wide) TSE_VLAP_STAGE(1, true, tiles); else TSE_VLAP_STAGE(1, false, tiles); }
+  else TSE_VLAP_STAGE(2, false, flat);
+#undef TSE_VLAP_STAGE
+}
+template <int ORDER>
+static void launch_vlap_view_out(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double nu_ratio, double* view) {
+  const dim3 flat((unsigned)vlap_view_out_blocks(c->nelemd, a.nk)), tiles((unsigned)(8ll * ((c->nelemd + 7) >> 3)));
+#define TSE_VLAP_OUT(PATH, W, grid) hipLaunchKernelGGL((k_vlap_view_out<PATH, W, ORDER>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), \
+    (const double*)c->vec_tab, nu_ratio, (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view)
+  if (path == 0) { if (wide) TSE_VLAP_OUT(0, true, flat); else TSE_VLAP_OUT(0, false, flat); }
+  else if (path == 1) { if (wide) TSE_VLAP_OUT(1, true, tiles); else TSE_VLAP_OUT(1, false, tiles); }
+  else TSE_VLAP_OUT(2, false, flat);
+#undef TSE_VLAP_OUT
+}
+
+// As tse_biharmonic_view with nf = 2 (the plan is vlaplace_view_plan, tse_views.cpp); the kernels take both components of a level at once.
+int tse_vlaplace_view(tse_ctx* c, int nk, int order, double nu_ratio, const tse_view* in, const tse_view* out, void* stream) {
+  const char* who = "tse_vlaplace_view";
+  if (!c) return fail("%s: null context", who);
+  if (order != TSE_VLAPLACE && order != TSE_VBIHARMONIC)
+    return fail("%s: order=%d (1: out = vlaplace_sphere_wk(in); 2: out = vlaplace_sphere_wk(rspheremp * DSS(vlaplace_sphere_wk(in))))", who, order);
+  if (!std::isfinite(nu_ratio)) return fail("%s: nu_ratio = %g is not finite", who, nu_ratio);
+  if (!c->vec_ready) return fail("%s: call tse_vector_setup first (elem%%D, elem%%metinv and elem%%mp are not part of tse_init_args)", who);
+  ViewPlan p[2];
+  { std::string err; if (vlaplace_view_plan(c->nelemd, nk, in, out, p, &err)) return fail("%s", err.c_str()); }
+  const size_t nl = (size_t)2 * nk;
+  if ((size_t)c->nelemd * nl >= ((size_t)1 << 27)) return fail("%s: %d elements x %zu layers (the launches count 32-bit blocks)", who, c->nelemd, nl);
+  const tse_view* v[2] = {in, out};
+  const std::vector<void*> mine = device_allocations(c);
+  for (int i = 0; i < 2; i++) {
+    void* alloc = nullptr;
+    if (view_runtime_checks(c, who, i ? "out" : "in", p[i], v[i], stream, &alloc)) return 1;
+    if (std::find(mine.begin(), mine.end(), alloc) != mine.end())
+      return fail("%s: %s: %p lies inside an allocation of the library; the call works on the host's own arrays", who, i ? "out" : "in", v[i]->ptr);
+  }
+  { std::string err; if (biharmonic_view_overlap(in, out, p, &err, who)) return fail("%s", err.c_str()); }
+  const bool exchange = order == TSE_VBIHARMONIC && c->halo();
+  unsigned pack_blocks = 0;
+  if (exchange && c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
+  if (dss_view_buffers(c, nl)) return 1;
+  hipStream_t us = (hipStream_t)stream;
+  if (us && !c->view_ev[0])
+    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  const DssViewArgs ai = dss_view_args(2, nk, in), ao = dss_view_args(2, nk, out);
+
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
+  {
+    Scope sc(c, "fieldvlap");
+    launch_vlap_view_stage(c, p[0].path, dss_view_wide(p[0].path, in), ai, nu_ratio, (const double*)in->ptr);
+    LAUNCH_CHECK();
+  }
+  if (exchange) {
+    CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
+    if (c->ncol_send) {
+      CommScope sc(c, "comm_pack_q", c->stream);
+      hipLaunchKernelGGL(k_pack<>, dim3(pack_blocks), dim3(256), 0, c->stream, c->ncol_send, (int)nl, c->send_src, (const double*)c->dv_stage, (const double*)nullptr,
+                         c->dv_send, (int)nl, 0, (int)nl);
+      LAUNCH_CHECK();
+    }
+    if (halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv)) return 1;
+  }
+  {
+    Scope sc(c, "fieldvlap");
+    if (order == TSE_VLAPLACE) launch_vlap_view_out<1>(c, p[1].path, dss_view_wide(p[1].path, out), ao, nu_ratio, (double*)out->ptr);
+    else launch_vlap_view_out<2>(c, p[1].path, dss_view_wide(p[1].path, out), ao, nu_ratio, (double*)out->ptr);
     LAUNCH_CHECK();
   }
   if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }

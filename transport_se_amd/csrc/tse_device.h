@@ -171,6 +171,63 @@ __device__ __forceinline__ void laplace_lean_row(const Dvv_t& D, const LapGeo& L
   }
 }
 
+// vlaplace_sphere_wk_contra (derivative_mod.F90:2545-2591: the constant-coefficient vector Laplacian, grad_wk(nu_ratio * div) - curl_wk(vor)
+// + 2 * spheremp * v * rrearth^2) of v = (v1, v2) at the lane's 4 points.  The metric products are folded once per point into 14 tables
+// (k_vec_fold, tse_kernels.h; index a + 2b of a 2x2 entry (a,b) as in Fortran memory):
+//   gDi = rrearth * metdet * Dinv                 divergence_sphere's contravariant flux (:2364-2414)
+//   Dr  = rrearth * D                             vorticity_sphere's covariant components (:2250-2301: D^T v) and the contra -> lat/lon
+//                                                 map of curl_sphere_wk_testcov (:1703-1762)
+//   G   = -Dr * (metdet * metinv)                 gradient_sphere_wk_testcov (:1765-1828) with its contra -> lat/lon map
+//   mr  = mp * rmetdet,  s2 = 2 * spheremp * rrearth^2
+// so that with md = nu_ratio * mr * (d/dx gv1 + d/dy gv2), mv = mr * (d/dx vc2 - d/dy vc1) and X(m,n) = sum_l Dvv(m,l) f(l,n),
+// Y(m,n) = sum_l Dvv(n,l) f(m,l):   lap_c = G_c1 X(md) + G_c2 Y(md) + Dr_c1 Y(mv) - Dr_c2 X(mv) + s2 v_c.
+// No implicit contraction: the stage kernel, the out kernel and any later inlined copy give a point the same bits.
+constexpr int VEC_TABS = 14;
+struct VecGeo { double gDi[4][4], Dr[4][4], G[4][4], mr[4], s2[4], dcol[4], drow[4]; };   // [entry a + 2b][i]
+// tab[e][VEC_TABS][16]: a lane's share of a table is one 32-byte access, a quad's one line
+__device__ __forceinline__ void load_vec_geo(VecGeo& V, const double* __restrict__ dvv, const double* __restrict__ tab, int e, int j) {
+  const double* t = tab + (size_t)e * VEC_TABS * 16 + 4 * j;
+#pragma unroll
+  for (int k = 0; k < 4; k++) { load4(t + k * 16, V.gDi[k]); load4(t + (4 + k) * 16, V.Dr[k]); load4(t + (8 + k) * 16, V.G[k]); }
+  load4(t + 12 * 16, V.mr);
+  load4(t + 13 * 16, V.s2);
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int row = r < 2 ? j : (j ^ 1), m = (r & 1) ? 3 - j : j;   // M(row, m), as in load_row_geo
+    V.dcol[r] = dvv[row * 4 + m]; V.drow[r] = dvv[m * 4 + row];
+  }
+}
+__device__ __forceinline__ void vlaplace_row(const Dvv_t& D, const VecGeo& V, double nu_ratio, const double v1[4], const double v2[4],
+                                             double o1[4], double o2[4]) {
+#pragma clang fp contract(off)
+  double gv1[4], vc2[4], md[4], mv[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    gv1[i] = fma(V.gDi[2][i], v2[i], V.gDi[0][i] * v1[i]);   // contravariant 1 (times rrearth * metdet)
+    vc2[i] = fma(V.Dr[3][i], v2[i], V.Dr[2][i] * v1[i]);     // covariant 2 (times rrearth)
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const double gv2 = fma(V.gDi[3][i], v2[i], V.gDi[1][i] * v1[i]);
+    const double vc1 = fma(V.Dr[1][i], v2[i], V.Dr[0][i] * v1[i]);
+    const double dx = fma(D.d[i * 4 + 3], gv1[3], fma(D.d[i * 4 + 2], gv1[2], fma(D.d[i * 4 + 1], gv1[1], D.d[i * 4] * gv1[0])));
+    const double dvdx = fma(D.d[i * 4 + 3], vc2[3], fma(D.d[i * 4 + 2], vc2[2], fma(D.d[i * 4 + 1], vc2[1], D.d[i * 4] * vc2[0])));
+    const double dy = quad_matvec(V.dcol, gv2);
+    const double dudy = quad_matvec(V.dcol, vc1);
+    md[i] = nu_ratio * (V.mr[i] * (dx + dy));   // mp * nu_ratio * div
+    mv[i] = V.mr[i] * (dvdx - dudy);            // mp * vor
+  }
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    const double X = fma(md[3], D.d[3 * 4 + m], fma(md[2], D.d[2 * 4 + m], fma(md[1], D.d[1 * 4 + m], md[0] * D.d[0 * 4 + m])));
+    const double Xv = fma(mv[3], D.d[3 * 4 + m], fma(mv[2], D.d[2 * 4 + m], fma(mv[1], D.d[1 * 4 + m], mv[0] * D.d[0 * 4 + m])));
+    const double Y = quad_matvec(V.drow, md[m]);
+    const double Yv = quad_matvec(V.drow, mv[m]);
+    o1[m] = fma(V.s2[m], v1[m], fma(-V.Dr[2][m], Xv, fma(V.Dr[0][m], Yv, fma(V.G[2][m], Y, V.G[0][m] * X))));
+    o2[m] = fma(V.s2[m], v2[m], fma(-V.Dr[3][m], Xv, fma(V.Dr[1][m], Yv, fma(V.G[3][m], Y, V.G[1][m] * X))));
+  }
+}
+
 // limiter_optim_iter_full (prim_advection_mod.F90:976-1094) on one slab spread over a quad.
 // x[i] = ptens/dpmass at the lane's 4 points, c[i] = sphweights*dpmass, sumc = sum(c) over the slab.
 // minp/maxp are relaxed in place (intent(inout) in the reference).  The 16-point sums are tree sums

@@ -3145,4 +3145,168 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_lap_view_out(int nelemd, DssVi
 // blocks of k_lap_view_out<0 | 2>: 8 XCD ranges of ceil(nelemd / 8) element slots, one quad per LAP_VIEW_LAYERS layers of an element
 inline long long lap_view_out_blocks(int nelemd, long long nl) { return dss_view_sum_blocks(nelemd, 4 * lap_view_groups(nl)); }
 
+// ---- weak vector Laplacian and biharmonic of a host's own wind through strided views (tse_vlaplace_view) -----------------------------
+// ORDER 1: out = vlaplace_sphere_wk(in) (weak, not summed).  ORDER 2: out = vlaplace_sphere_wk(rspheremp * DSS(vlaplace_sphere_wk(in))),
+// the wind's line of biharmonic_wk_dp3d (viscosity_mod.F90:177-286) before the final DSS, for nk levels of the two components of one view
+// (q axis = component).  The operator is vlaplace_row (tse_device.h) on the tables k_vec_fold leaves; the sum is k_dss_view_sum's
+// (dss_view_point over 2 * nk layers, then one product with rspheremp).  The kernels are k_lap_view_stage / k_lap_view_out with both
+// components of a level in one quad, because the operator couples them: layer c * nk + k of the staging field is component c of level k.
+//   PATH 0, 2  a quad takes VLAP_VIEW_LEVELS consecutive levels of its element (2 levels = 4 layers, the scalar kernels' 4 layers per thread)
+//   PATH 1     block = element; both components pass through LDS images of their own
+// k_vec_fold: one thread per point, tab[e][VEC_TABS][16] from the library's Dinv, metdet, rmetdet, spheremp and the host's D, metinv, mp
+// (src[e][p][9] = D(a + 2b), metinv(a + 2b), mp).  Every product is rounded once, in the order written here.
+constexpr int VLAP_VIEW_LEVELS = 2;
+template <int = 0>
+__global__ __launch_bounds__(256) void k_vec_fold(int nelemd, GeoPtrs G, const double* __restrict__ src, double* __restrict__ tab) {
+#pragma clang fp contract(off)
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)nelemd * 16) return;
+  const size_t e = t >> 4;
+  const int p = (int)(t & 15);
+  const double* s = src + t * 9;
+  double* o = tab + e * VEC_TABS * 16 + p;
+  const double g = G.metdet[t], rg = RREARTH * g;
+  double Dr[4], mg[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    o[k * 16] = rg * G.Dinv[t * 4 + k];
+    Dr[k] = RREARTH * s[k];
+    mg[k] = g * s[4 + k];
+    o[(4 + k) * 16] = Dr[k];
+  }
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    o[(8 + c) * 16] = -fma(Dr[c + 2], mg[2], Dr[c] * mg[0]);    // G(c,1) = -rrearth * metdet * (D(c,1) metinv(1,1) + D(c,2) metinv(1,2))
+    o[(10 + c) * 16] = -fma(Dr[c + 2], mg[3], Dr[c] * mg[1]);   // G(c,2) = -rrearth * metdet * (D(c,1) metinv(2,1) + D(c,2) metinv(2,2))
+  }
+  o[12 * 16] = s[8] * G.rmetdet[t];
+  o[13 * 16] = (2.0 * G.spheremp[t]) * (RREARTH * RREARTH);
+}
+
+template <int PATH, bool WIDE>
+__global__ __launch_bounds__(VIEW_THREADS) void k_vlap_view_stage(int nelemd, DssViewArgs a, Dvv_t D, GeoPtrs G, const double* __restrict__ vtab, double nu_ratio,
+                                                                  const double* __restrict__ view, double* __restrict__ stage) {
+#pragma clang fp contract(off)
+  const int nk = a.nk, nl = 2 * nk, tid = threadIdx.x, j = tid & 3;
+  VecGeo V;
+  if (PATH == 1) {
+    __shared__ __attribute__((aligned(16))) double tile[2][16 * VIEW_PITCH];
+    constexpr int K = NLEV;
+    const int e = (int)blockIdx.x;   // (the grid is nelemd blocks)
+    load_vec_geo(V, G.dvv, vtab, e, j);
+    dss_rows_to_tile<WIDE, K>(view + (long long)e * a.vs[0], a.vs[4], tile[0], tid);
+    dss_rows_to_tile<WIDE, K>(view + (long long)e * a.vs[0] + a.vs[1], a.vs[4], tile[1], tid);
+    __syncthreads();
+    double* S = stage + (size_t)e * nl * 16 + 4 * j;
+    for (int k = tid >> 2; k < K; k += VIEW_THREADS / 4) {
+      double v1[4], v2[4], r1[4], r2[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) { v1[i] = tile[0][(4 * j + i) * VIEW_PITCH + k]; v2[i] = tile[1][(4 * j + i) * VIEW_PITCH + k]; }
+      vlaplace_row(D, V, nu_ratio, v1, v2, r1, r2);
+      store4(S + (size_t)k * 16, r1);
+      store4(S + (size_t)(K + k) * 16, r2);
+    }
+  } else {
+    const int groups = (nk + VLAP_VIEW_LEVELS - 1) / VLAP_VIEW_LEVELS;
+    const size_t qd = ((size_t)blockIdx.x * VIEW_THREADS + tid) >> 2;
+    const size_t eraw = qd / (unsigned)groups;
+    const int grp = (int)(qd - eraw * (unsigned)groups);
+    const bool live = eraw < (size_t)nelemd;
+    const int e = live ? (int)eraw : nelemd - 1;
+    load_vec_geo(V, G.dvv, vtab, e, j);
+    const int k0 = grp * VLAP_VIEW_LEVELS;
+#pragma unroll
+    for (int u = 0; u < VLAP_VIEW_LEVELS; u++) {
+      const int k = min(k0 + u, nk - 1);
+      double v1[4], v2[4], r1[4], r2[4];
+      const double* P = view + (long long)e * a.vs[0] + k * a.vs[2];
+      lap_view_load_row<PATH, WIDE>(P, a, j, v1);
+      lap_view_load_row<PATH, WIDE>(P + a.vs[1], a, j, v2);
+      vlaplace_row(D, V, nu_ratio, v1, v2, r1, r2);
+      if (live && k0 + u < nk) {
+        store4(stage + ((size_t)e * nl + k) * 16 + 4 * j, r1);
+        store4(stage + ((size_t)e * nl + nk + k) * 16 + 4 * j, r2);
+      }
+    }
+  }
+}
+
+template <int PATH, bool WIDE, int ORDER>
+__global__ __launch_bounds__(VIEW_THREADS) void k_vlap_view_out(int nelemd, DssViewArgs a, Dvv_t D, GeoPtrs G, const double* __restrict__ vtab, double nu_ratio,
+                                                                const int2* __restrict__ tab, const double* __restrict__ stage, const double* __restrict__ recvbuf,
+                                                                const int* __restrict__ order, double* __restrict__ view) {
+#pragma clang fp contract(off)
+  const int nk = a.nk, nl = 2 * nk, tid = threadIdx.x, j = tid & 3;
+  const int S8 = (nelemd + 7) >> 3, xcd = blockIdx.x & 7;   // contiguous ranges of `order` per XCD, as in k_dss_view_sum
+  const unsigned it = blockIdx.x >> 3;
+  VecGeo V;
+  if (PATH == 1) {
+    __shared__ __attribute__((aligned(16))) double tile[2][16 * VIEW_PITCH];
+    constexpr int K = NLEV;
+    const int idx = (int)it, slot = xcd * S8 + idx;
+    if (idx >= S8 || slot >= nelemd) return;   // (uniform over the block: before the barrier)
+    const int e = order[slot];
+    if (ORDER == 2) load_vec_geo(V, G.dvv, vtab, e, j);
+    for (int k = tid >> 2; k < K; k += VIEW_THREADS / 4) {
+      double r1[4], r2[4];
+      if (ORDER == 2) {
+        double m1[4], m2[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          double rs;
+          const double x1 = dss_view_point(tab, stage, recvbuf, nl, e, 4 * j + i, k, rs, G.rspheremp);
+          const double x2 = dss_view_point(tab, stage, recvbuf, nl, e, 4 * j + i, K + k, rs, G.rspheremp);
+          m1[i] = rs * x1; m2[i] = rs * x2;
+        }
+        vlaplace_row(D, V, nu_ratio, m1, m2, r1, r2);
+      } else {
+        load4(stage + ((size_t)e * nl + k) * 16 + 4 * j, r1);
+        load4(stage + ((size_t)e * nl + K + k) * 16 + 4 * j, r2);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; i++) { tile[0][(4 * j + i) * VIEW_PITCH + k] = r1[i]; tile[1][(4 * j + i) * VIEW_PITCH + k] = r2[i]; }
+    }
+    __syncthreads();
+    dss_tile_to_rows<WIDE, K>(tile[0], view + (long long)e * a.vs[0], a.vs[4], tid);
+    dss_tile_to_rows<WIDE, K>(tile[1], view + (long long)e * a.vs[0] + a.vs[1], a.vs[4], tid);
+  } else {
+    const int groups = (nk + VLAP_VIEW_LEVELS - 1) / VLAP_VIEW_LEVELS;
+    const long long qd = ((long long)it * VIEW_THREADS + tid) >> 2;
+    const long long idx = qd / groups;
+    const int grp = (int)(qd - idx * groups);
+    const long long slot = (long long)xcd * S8 + idx;
+    const bool live = idx < S8 && slot < nelemd;
+    const int e = order[live ? slot : nelemd - 1];
+    if (ORDER == 2) load_vec_geo(V, G.dvv, vtab, e, j);
+    const int k0 = grp * VLAP_VIEW_LEVELS;
+#pragma unroll
+    for (int u = 0; u < VLAP_VIEW_LEVELS; u++) {
+      const int k = min(k0 + u, nk - 1);
+      double r1[4], r2[4];
+      if (ORDER == 2) {
+        double m1[4], m2[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          double rs;
+          const double x1 = dss_view_point(tab, stage, recvbuf, nl, e, 4 * j + i, k, rs, G.rspheremp);
+          const double x2 = dss_view_point(tab, stage, recvbuf, nl, e, 4 * j + i, nk + k, rs, G.rspheremp);
+          m1[i] = rs * x1; m2[i] = rs * x2;
+        }
+        vlaplace_row(D, V, nu_ratio, m1, m2, r1, r2);
+      } else {
+        load4(stage + ((size_t)e * nl + k) * 16 + 4 * j, r1);
+        load4(stage + ((size_t)e * nl + nk + k) * 16 + 4 * j, r2);
+      }
+      if (live && k0 + u < nk) {
+        double* P = view + (long long)e * a.vs[0] + k * a.vs[2];
+        lap_view_store_row<PATH, WIDE>(P, a, j, r1);
+        lap_view_store_row<PATH, WIDE>(P + a.vs[1], a, j, r2);
+      }
+    }
+  }
+}
+inline long long vlap_view_groups(long long nk) { return (nk + VLAP_VIEW_LEVELS - 1) / VLAP_VIEW_LEVELS; }
+// blocks of k_vlap_view_out<0 | 2>: 8 XCD ranges of ceil(nelemd / 8) element slots, one quad per VLAP_VIEW_LEVELS levels of an element
+inline long long vlap_view_out_blocks(int nelemd, long long nk) { return dss_view_sum_blocks(nelemd, 4 * vlap_view_groups(nk)); }
+
 }  // namespace tse

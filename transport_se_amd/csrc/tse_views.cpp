@@ -164,8 +164,7 @@ int dss_view_plan(int nelemd, int nf, int nk, const tse_view* v, ViewPlan* out, 
 // tse_biharmonic_view's two views: each a view of tse_dss_view (dss_view_plan).  biharmonic_view_overlap: `out` is `in` itself (the same
 // pointer and the same five strides: in place) or its footprint, taken from its ptr, does not meet in's -- the first kernel reads `in`
 // whole before the second writes `out`, but a partial overlap would leave a field that is neither the input nor the result.
-int biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err) {
-  const char* who = "tse_biharmonic_view";
+int biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err, const char* who) {
   if (!in || !out_view || !out) return refuse(err, "%s: null view", who);
   const tse_view* v[2] = {in, out_view};
   for (int i = 0; i < 2; i++) {
@@ -181,14 +180,20 @@ bool biharmonic_view_in_place(const tse_view* in, const tse_view* out) {
   return true;
 }
 
-int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err) {
+int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err, const char* who) {
   if (biharmonic_view_in_place(in, out)) return 0;
   const __int128 f0 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].lo * 8, f1 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].hi * 8;
   const __int128 g0 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].lo * 8, g1 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].hi * 8;
   if (f0 < g1 && g0 < f1)
-    return refuse(err, "tse_biharmonic_view: out [%p%+lld, %p%+lld doubles) overlaps in [%p%+lld, %p%+lld doubles) without being the same view (the same "
-                  "pointer and strides: in place)", out->ptr, plan[1].lo, out->ptr, plan[1].hi, in->ptr, plan[0].lo, in->ptr, plan[0].hi);
+    return refuse(err, "%s: out [%p%+lld, %p%+lld doubles) overlaps in [%p%+lld, %p%+lld doubles) without being the same view (the same "
+                  "pointer and strides: in place)", who, out->ptr, plan[1].lo, out->ptr, plan[1].hi, in->ptr, plan[0].lo, in->ptr, plan[0].hi);
   return 0;
+}
+
+// tse_vlaplace_view's two views: each a view of tse_dss_view with nf = 2, the q axis the wind component; the overlap rule is
+// biharmonic_view_overlap's.
+int vlaplace_view_plan(int nelemd, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err) {
+  return biharmonic_view_plan(nelemd, 2, nk, in, out_view, out, err, "tse_vlaplace_view");
 }
 
 }  // namespace tse
@@ -234,6 +239,20 @@ extern "C" int tse_biharmonic_view_plan(int nelemd, int nf, int nk, const tse_vi
   if (tse::biharmonic_view_plan(nelemd, nf, nk, in, out, p, &err)) return tse::set_last_error(err.c_str());
   // strides alone (both ptr null): nothing is known of where the views lie
   if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err)) return tse::set_last_error(err.c_str());
+  for (int i = 0; i < 2; i++) {
+    if (path) path[i] = p[i].path;
+    if (lo) lo[i] = p[i].lo;
+    if (hi) hi[i] = p[i].hi;
+  }
+  return 0;
+}
+
+extern "C" int tse_vlaplace_view_plan(int nelemd, int nk, const tse_view* in, const tse_view* out, int path[2], long long lo[2], long long hi[2]) {
+  tse::ViewPlan p[2];
+  std::string err;
+  if (tse::vlaplace_view_plan(nelemd, nk, in, out, p, &err)) return tse::set_last_error(err.c_str());
+  // strides alone (both ptr null): nothing is known of where the views lie
+  if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err, "tse_vlaplace_view")) return tse::set_last_error(err.c_str());
   for (int i = 0; i < 2; i++) {
     if (path) path[i] = p[i].path;
     if (lo) lo[i] = p[i].lo;

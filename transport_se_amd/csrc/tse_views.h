@@ -38,9 +38,14 @@ int dss_view_plan(int nelemd, int nf, int nk, const tse_view* field, ViewPlan* o
 // The two views of tse_biharmonic_view / tse_biharmonic_view_plan -> out[0..1] = the plans of in, out: each a view of tse_dss_view.
 // biharmonic_view_in_place: out is the same pointer and the same five strides as in.  biharmonic_view_overlap: otherwise the two
 // footprints, each taken from its ptr, are disjoint (touching is disjoint).
-int biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err);
+// who: the entry the refusals name.
+int biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err,
+                         const char* who = "tse_biharmonic_view");
 bool biharmonic_view_in_place(const tse_view* in, const tse_view* out);
-int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err);
+int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err, const char* who = "tse_biharmonic_view");
+
+// The two views of tse_vlaplace_view / tse_vlaplace_view_plan: those of tse_biharmonic_view with nf = 2 (the q axis is the wind component).
+int vlaplace_view_plan(int nelemd, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err);
 
 // the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
 int set_last_error(const char* msg);

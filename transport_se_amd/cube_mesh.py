@@ -215,6 +215,24 @@ def geometry(ne, topo=None):
                 rspheremp=rspheremp, alpha=alpha)
 
 
+def metinv(D):
+    """elem%metinv(2,2,np,np) from the area-corrected D[...][b][a] (geometry()["D"]), in D's layout: met = D^T D as cube_mod.F90:292-299
+    spells it, metinv = [[met22, -met12], [-met21, met11]] / (detD*detD) (:344-347).  The reference forms metinv before the area
+    correction and divides by alpha afterwards, so its last bits may differ from these; no golden file carries metinv, and the library
+    takes whatever metinv its host gives it (tse_vector_setup)."""
+    D = np.asarray(D, dtype=np.float64)
+    D11, D21, D12, D22 = D[..., 0, 0], D[..., 0, 1], D[..., 1, 0], D[..., 1, 1]
+    m11 = D11 * D11 + D21 * D21
+    m12 = D11 * D12 + D21 * D22
+    m21 = m12
+    m22 = D12 * D12 + D22 * D22
+    det = D11 * D22 - D12 * D21
+    dd = det * det
+    out = np.empty(D.shape)
+    out[..., 0, 0], out[..., 0, 1], out[..., 1, 0], out[..., 1, 1] = m22 / dd, -m21 / dd, -m12 / dd, m11 / dd
+    return out
+
+
 _OFF = np.array([0, 4, 8, 12, 16, 17, 18, 19])
 
 

@@ -61,6 +61,9 @@ module cuda_mod
   ! weak Laplacian / biharmonic of the host's own device-resident scalar fields (tse_biharmonic_view)
   public :: biharmonic_view_hip
   integer, parameter, public :: lap_order1 = 1, lap_order2 = 2   ! TSE_LAPLACE, TSE_BIHARMONIC
+  ! weak vector Laplacian / biharmonic of the host's own device-resident wind (tse_vector_setup, tse_vlaplace_view)
+  public :: vector_setup_hip, vlaplace_view_hip
+  integer, parameter, public :: vlap_order1 = 1, vlap_order2 = 2   ! TSE_VLAPLACE, TSE_VBIHARMONIC
   logical, save :: remap_refused = .false.            ! remap_view_hip / remap_view_status_hip: the master thread's answer, read by every thread
   integer(c_int), save :: remap_nrefused = 0, remap_where(4) = 0
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
@@ -212,6 +215,13 @@ module cuda_mod
      end function
      integer(c_int) function tse_biharmonic_view(ctx, nf, nk, order, vin, vout, stream) bind(C, name='tse_biharmonic_view')
        import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nf, nk, order
+       type(tse_view), intent(in) :: vin, vout
+     end function
+     integer(c_int) function tse_vector_setup(ctx, D, D_stride, metinv, metinv_stride, mp, mp_stride) bind(C, name='tse_vector_setup')
+       import; type(c_ptr), value :: ctx, D, metinv, mp; integer(c_size_t), value :: D_stride, metinv_stride, mp_stride
+     end function
+     integer(c_int) function tse_vlaplace_view(ctx, nk, order, nu_ratio, vin, vout, stream) bind(C, name='tse_vlaplace_view')
+       import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nk, order; real(c_double), value :: nu_ratio
        type(tse_view), intent(in) :: vin, vout
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
@@ -912,5 +922,42 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine biharmonic_view_hip
+
+  ! elem(:)%D, %metinv and %mp -> the device, folded there into the tables of vlaplace_view_hip (include/transport_se_hip.h:
+  ! tse_vector_setup).  Once after cuda_mod_init, before the first vlaplace_view_hip; may be called again.
+  subroutine vector_setup_hip(elem)
+    type(element_t), intent(in), target :: elem(:)
+    integer :: e2
+    e2 = min(2, size(elem))
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_vector_setup(ctx, c_loc(elem(1)%D), stride_of(c_loc(elem(1)%D), c_loc(elem(e2)%D)), &
+                                c_loc(elem(1)%metinv), stride_of(c_loc(elem(1)%metinv), c_loc(elem(e2)%metinv)), &
+                                c_loc(elem(1)%mp), stride_of(c_loc(elem(1)%mp), c_loc(elem(e2)%mp))), 'vector_setup_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine vector_setup_hip
+
+  ! out(:,:,1:2,1:nk) at out_ptr <- vlaplace_sphere_wk of v(:,:,1:2,1:nk) of the host's DEVICE array at ptr (order vlap_order1: weak, not
+  ! summed, no exchange) or vlaplace_sphere_wk(rspheremp * DSS(vlaplace_sphere_wk(v))) (vlap_order2: the wind's line of biharmonic_wk_dp3d
+  ! before its final DSS; include/transport_se_hip.h: tse_vlaplace_view).  nu_ratio multiplies the divergence in every Laplacian.
+  ! strides(1:5) and out_strides(1:5) in doubles for element, component, level, j, i: state%v(np,np,2,nlev,tl) is (/ s_e, 16, 32, 4, 1 /)
+  ! with one call per time level.  out_ptr and out_strides equal to ptr and strides: in place; otherwise the two arrays may not overlap.
+  ! COLLECTIVE for vlap_order2: every rank calls with the same nk.  The host scales by -nu*dt and follows with
+  ! dss_view_hip(2, nk, dss_weak, ...).  stream as in view_put_hip.  A refusal aborts.
+  subroutine vlaplace_view_hip(nk, order, nu_ratio, ptr, strides, out_ptr, out_strides, stream)
+    integer,              intent(in) :: nk, order
+    real(c_double),       intent(in) :: nu_ratio
+    type(c_ptr),          intent(in) :: ptr, out_ptr, stream
+    integer(c_long_long), intent(in) :: strides(5), out_strides(5)
+    type(tse_view) :: vi, vo
+    vi%ptr = ptr; vi%stride = strides
+    vo%ptr = out_ptr; vo%stride = out_strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_vlaplace_view(ctx, int(nk,c_int), int(order,c_int), nu_ratio, vi, vo, stream), 'vlaplace_view_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine vlaplace_view_hip
 
 end module cuda_mod

@@ -249,6 +249,33 @@ def biharmonic_view_plan(nelemd, nf, nk, field, out=None, nlev=None):
     return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
 
 
+VLAP_ORDERS = {"vlaplace": 1, "vbiharmonic": 2}   # TSE_VLAPLACE, TSE_VBIHARMONIC
+
+
+def _vlap_order(order):
+    """the order names, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(order, str):
+        if order not in VLAP_ORDERS:
+            raise TseError("vlaplace_view: unknown order %r (the orders are %s)" % (order, ", ".join(VLAP_ORDERS)))
+        return VLAP_ORDERS[order]
+    return int(order)
+
+
+def vlaplace_view_plan(nelemd, nk, field, out=None, nlev=None):
+    """tse_vlaplace_view_plan: [dict(path=, lo=, hi=)] of the two views of HipMod.vlaplace_view, in and out, given as for
+    biharmonic_view_plan (nf is 2: the q axis is the wind component); out=None: in place.  Needs no device.  Raises TseError for views
+    vlaplace_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    raw = lambda x: _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
+    vi = None if field is None else raw(field)
+    vo = vi if out is None else raw(out)
+    path, lo, hi = (C.c_int * 2)(), (C.c_longlong * 2)(), (C.c_longlong * 2)()
+    if L.tse_vlaplace_view_plan(int(nelemd), int(nk), None if vi is None else C.byref(vi), None if vo is None else C.byref(vo),
+                                C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -663,6 +690,43 @@ class HipMod:
             if (onf, onk) != (nf, nk):
                 raise TseError("%s: out has %d fields of %d levels, field has %d of %d" % (who, onf, onk, nf, nk))
         self._chk(self.L.tse_biharmonic_view(self.h, int(nf), int(nk), _lap_order(order), C.byref(vi), C.byref(vo), _stream_handle(stream)))
+
+    # ---- weak vector Laplacian / biharmonic of the host's own wind (tse_vector_setup, tse_vlaplace_view) ----
+    def vector_setup(self, D, metinv, mp):
+        """elem%D and elem%metinv [nelemd][4][4][2][2] (Fortran memory (a,b,i,j), as cube_mesh.geometry()["D"] and cube_mesh.metinv) and
+        elem%mp [nelemd][4][4] -> device, folded there into the tables of vlaplace_view.  May be called again."""
+        D = np.ascontiguousarray(D, np.float64); metinv = np.ascontiguousarray(metinv, np.float64); mp = np.ascontiguousarray(mp, np.float64)
+        if D.size != self.nelemd * 64 or metinv.size != self.nelemd * 64 or mp.size != self.nelemd * 16:
+            raise TseError("vector_setup: D %s, metinv %s, mp %s for %d elements" % (D.shape, metinv.shape, mp.shape, self.nelemd))
+        self._chk(self.L.tse_vector_setup(self.h, _vp(D), 64 * 8, _vp(metinv), 64 * 8, _vp(mp), 16 * 8))
+
+    def vlaplace_view(self, field, axes, out=None, out_axes=None, order=2, nu_ratio=1.0, stream=None, nk=None):
+        """out <- vlaplace_sphere_wk(field) (order 1 or "vlaplace": weak, not summed, no exchange) or
+        vlaplace_sphere_wk(rspheremp * DSS(vlaplace_sphere_wk(field))) (order 2 or "vbiharmonic": the wind's line of biharmonic_wk_dp3d
+        before the final DSS) on nk levels of the device array `field`, whose axis q (extent 2) is the wind component; nk is the array's
+        extent along the letter k of `axes` (a missing k: 1).  nu_ratio multiplies the divergence in every Laplacian.  out=None: in place;
+        otherwise another device array of the same nk whose axes `out_axes` names (default: `axes`), disjoint from `field`.  The bits are
+        those of order 1 -> dss_view(mode="weak") -> order 1 on every path of either view and on any number of ranks.  Order 2 is
+        COLLECTIVE on a context with neighbour ranks, as dss_view.  Needs vector_setup.  stream orders as in put.  `field` and `out` may
+        also be ready _lib.Views (then nk is needed)."""
+        who = "vlaplace_view"
+        if isinstance(field, _lib.View):
+            if nk is None:
+                raise TseError("%s: nk is needed with a ready view" % who)
+            vi = field
+        else:
+            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=out is None)
+            if nf != 2:
+                raise TseError("%s: the q axis is the wind component and has extent %d, not 2" % (who, nf))
+        if out is None:
+            vo = vi
+        elif isinstance(out, _lib.View):
+            vo = out
+        else:
+            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
+            if (onf, onk) != (2, nk):
+                raise TseError("%s: out has %d components of %d levels, field has 2 of %d" % (who, onf, onk, nk))
+        self._chk(self.L.tse_vlaplace_view(self.h, int(nk), _vlap_order(order), float(nu_ratio), C.byref(vi), C.byref(vo), _stream_handle(stream)))
 
     def last_error(self):
         return self.L.tse_last_error().decode()
