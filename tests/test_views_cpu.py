@@ -198,6 +198,81 @@ def test_plan_refusals_name_the_axis():
     assert L.tse_view_plan(b"dp", 3, 3, C.byref(v), 0, None, None, None) == 0   # the outputs are optional
 
 
+# ---- the 16-bytes-per-lane rule (csrc/tse_views.cpp: view_wide) against the addresses the kernels touch ------------------------
+BUF = 0x7F0000001000   # a 16-byte aligned allocation
+
+
+def _view_wide(path, ptr, strides):
+    L = _lib.lib(_lib.HOOKS_SO)
+    L.tse_test_view_wide.argtypes = [C.c_int, C.POINTER(_lib.View)]
+    v = _lib.View(ptr, (C.c_longlong * 5)(*[int(x) for x in strides]))
+    return bool(L.tse_test_view_wide(path, C.byref(v)))
+
+
+def _misaligned(path, ptr, s, ext):
+    """whether any 16-byte access of a WIDE kernel is not 16-byte aligned, every address enumerated: on path 0 V + 2 * part (8 parts) of every
+    (e, q, k) slab, on path 1 level pair 2 * kp of row p (16 rows at the pitch of the i stride) of every (e, q) tile"""
+    e = np.arange(ext[0], dtype=np.int64).reshape(-1, 1, 1, 1) * int(s[0])
+    q = np.arange(ext[1], dtype=np.int64).reshape(1, -1, 1, 1) * int(s[1])
+    if path == 0:
+        unit, part = np.arange(ext[2], dtype=np.int64) * int(s[2]), 2 * np.arange(8, dtype=np.int64)
+    else:
+        unit, part = np.arange(16, dtype=np.int64) * int(s[4]), 2 * np.arange(max(1, ext[2] // 2), dtype=np.int64)
+    addr = ptr + 8 * (e + q + unit.reshape(1, 1, -1, 1) + part.reshape(1, 1, 1, -1))
+    return bool((addr % 16 != 0).any())
+
+
+def _alignment_cases(nlev):
+    """(path, strides, extents, offset of the view in its buffer in doubles): every layout of _stride_table and of dss_view_model, and
+    views with one odd stride each, which neither enumerates: a dense point-fastest and a dense level-fastest field of 2 x nlev layers on
+    3 elements with the element stride, the q stride or (point-fastest) the level stride made odd and the strides above it nested again"""
+    import dss_view_model as dm
+    for nelemd, qsize in itertools.product((1, 3), (1, 3)):
+        for for_get, fields in ((False, vm.PUT_FIELDS), (True, vm.GET_FIELDS)):
+            for field in fields:
+                ext = vm.extents(field, nelemd, qsize, nlev, for_get)
+                for _, strides, _ in _stride_table(field, ext, vm.has_axes(field, for_get), for_get):
+                    yield view_plan(field, nelemd, qsize, strides, for_get, nlev=nlev)["path"], strides, ext, 0
+    for nf, nk, name in itertools.product((1, 2, 5), (1, nlev, nlev + 1), dm.LAYOUTS):
+        s, base, _ = dm.layout(name, 24, nf, nk)
+        yield hip_mod.dss_view_plan(24, nf, nk, s, nlev=nlev)["path"], s, (24, nf, nk, 4, 4), base
+    even = lambda x: x + x % 2   # noqa: E731
+    E, nf, K = 3, 2, nlev
+    for se, sq, sk in ((1, 0, 0), (0, 1, 0), (0, 0, 1)):
+        k = 16 + sk; q = even(K * k) + sq
+        yield 0, [even(nf * q) + se, q, k, 4, 1], (E, nf, K, 4, 4), 0
+    for se, sq in ((1, 0), (0, 1)):
+        q = 16 * K + sq
+        yield 1, [even(nf * q) + se, q, 1, 4 * K, K], (E, nf, K, 4, 4), 0
+
+
+@pytest.mark.parametrize("nlev", [72, 64, 80])
+def test_wide_rule_against_every_address(nlev):
+    """view_wide says wide: every 16-byte access is aligned, at the view's own extents.  It says narrow on path 0 or 1: some access is
+    misaligned.  The rule sees the strides and not the extents, so a stride it refuses may belong to an axis of extent 1 (a field without
+    q axis on one element, say) and never move an address; narrow is therefore held to the extents with every axis the kernel steps over
+    (element, q, and on path 0 the level) at least 2.  Every one of the rule's conditions is met alone, at extents where it matters: without
+    any one of them some case below is called wide and shows a misaligned address."""
+    alone = set()
+    for path, s, ext, base in _alignment_cases(nlev):
+        for shift in (0, 1):   # the base shifted by 0 and by 8 bytes
+            ptr = BUF + 8 * (base + shift)
+            wide = _view_wide(path, ptr, s)
+            key = (path, list(s), ext, base, shift)
+            if path == 2:
+                assert not wide, key
+                continue
+            unit = 2 if path == 0 else 4
+            odd = [what for what, bad in (("base", ptr % 16), ("element", s[0] % 2), ("q", s[1] % 2), (("level", "i")[path], s[unit] % 2)) if bad]
+            if wide:
+                assert not _misaligned(path, ptr, s, ext), key
+            else:
+                assert _misaligned(path, ptr, s, [max(n, 2) for n in ext]), key
+                if len(odd) == 1 and _misaligned(path, ptr, s, ext):
+                    alone.add((path, odd[0]))
+    assert alone == {(0, "base"), (0, "element"), (0, "q"), (0, "level"), (1, "base"), (1, "element"), (1, "q"), (1, "i")}, alone
+
+
 # ---- the Python view builder -------------------------------------------------------------------------------------------------
 class FakeDeviceArray:
     def __init__(self, shape, strides=None, typestr="<f8", ptr=0x7F0000001000, readonly=False):

@@ -1647,6 +1647,7 @@ int tse_prim_run_subcycle(tse_ctx* c, double tstep, int nsub, int* nstep_io) {
 // tse_view_put / tse_view_get (include/transport_se_hip.h).  The descriptor logic -- fields, extents, path, footprint, overlap -- is
 // host code (tse_views.cpp); here: the checks that need the runtime, the stream ordering and the launch of one conversion kernel
 // (tse_kernels.h: k_view_lines, k_view_levels, k_view_generic) on the compute stream.  Nothing is enqueued before every check has passed.
+static dim3 view_blocks(size_t items) { return dim3((unsigned)((items + VIEW_THREADS - 1) / VIEW_THREADS)); }   // one item per thread
 template <bool PUT>
 static void launch_view(tse_ctx* c, const ViewPlan& p, const tse_view* v, double* lib) {
   double* view = (double*)v->ptr;
@@ -1654,19 +1655,17 @@ static void launch_view(tse_ctx* c, const ViewPlan& p, const tse_view* v, double
   ViewDims d;
   for (int a = 0; a < 5; a++) { d.ext[a] = p.ext[a]; d.lib[a] = p.lib[a]; d.vs[a] = s[a]; }
   const size_t slabs = (size_t)p.ext[0] * p.ext[1] * p.ext[2];
-  const bool base16 = ((uintptr_t)view & 15) == 0;
-  auto blocks = [](size_t items) { return dim3((unsigned)((items + VIEW_THREADS - 1) / VIEW_THREADS)); };
+  const bool wide = view_wide(p.path, v);
   if (p.path == 0) {
-    if (base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0) hipLaunchKernelGGL((k_view_lines<PUT, 2>), blocks(slabs * 8), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
-    else hipLaunchKernelGGL((k_view_lines<PUT, 1>), blocks(slabs * 16), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
+    if (wide) hipLaunchKernelGGL((k_view_lines<PUT, 2>), view_blocks(slabs * 8), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
+    else hipLaunchKernelGGL((k_view_lines<PUT, 1>), view_blocks(slabs * 16), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
   } else if (p.path == 1) {
-    const bool wide = base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
     const dim3 grid((unsigned)((size_t)p.ext[0] * p.ext[1]));
 #define TSE_VIEW_LEVELS(W, K) hipLaunchKernelGGL((k_view_levels<PUT, W, K>), grid, dim3(VIEW_THREADS), 0, c->stream, p.ext[1], p.lib[0], p.lib[1], p.lib[2], s[0], s[1], s[4], lib, view)
     if (p.ext[2] == NLEV) { if (wide) TSE_VIEW_LEVELS(true, NLEV); else TSE_VIEW_LEVELS(false, NLEV); }
     else { if (wide) TSE_VIEW_LEVELS(true, NLEVP); else TSE_VIEW_LEVELS(false, NLEVP); }
 #undef TSE_VIEW_LEVELS
-  } else hipLaunchKernelGGL((k_view_generic<PUT>), blocks(slabs * 16), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
+  } else hipLaunchKernelGGL((k_view_generic<PUT>), view_blocks(slabs * 16), dim3(VIEW_THREADS), 0, c->stream, d, lib, view);
 }
 
 // Everything a view entry (tse_view_put, tse_view_get, tse_apply_forcing) checks before it enqueues: the plan of the view, nt, null and
@@ -1712,6 +1711,39 @@ static int view_runtime_checks(tse_ctx* c, const char* who, const char* field, c
   if (alloc) *alloc = (void*)abase;
   return 0;
 }
+// One view of an entry that works on the host's own arrays (tse_remap_view, tse_dss_view, tse_biharmonic_view, tse_vlaplace_view).
+// who: the name its refusals carry; role: which view of the entry it is ("in", "out"), named by the refusal below alone, or null.
+struct HostView { const char *who, *role; const ViewPlan* p; const tse_view* v; };
+// view_runtime_checks on every view in turn, and none of them inside an allocation of the library.  own_qdp (tse_remap_view): the first
+// view may lie in qdp1 or qdp2, *own_qdp says whether it does.
+static int host_array_checks(tse_ctx* c, std::initializer_list<HostView> views, void* stream, bool* own_qdp = nullptr) {
+  const std::vector<void*> mine = device_allocations(c);
+  for (const HostView& h : views) {
+    void* alloc = nullptr;
+    if (view_runtime_checks(c, h.who, "field", *h.p, h.v, stream, &alloc)) return 1;
+    if (std::find(mine.begin(), mine.end(), alloc) == mine.end()) continue;
+    if (own_qdp && &h == views.begin() && (alloc == c->q(1) || alloc == c->q(2))) { *own_qdp = true; continue; }
+    return fail("%s%s%s: %p lies inside an allocation of the library%s; the call works on the host's own arrays", h.who, h.role ? ": " : "", h.role ? h.role : "", h.v->ptr,
+                own_qdp ? " that is not qdp1 or qdp2 (or is not the field)" : "");
+  }
+  return 0;
+}
+
+// The stream order of every view entry: the caller's stream -> the compute stream (order_in, behind every check and before the first
+// launch) -> the caller's stream (order_out, behind the last launch), with no host synchronisation; without a stream the call is complete
+// on return.  The two events are created by the first call that brings a stream.
+static int order_in(tse_ctx* c, hipStream_t us) {
+  if (!us) return 0;
+  if (!c->view_ev[0])
+    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0));
+  return 0;
+}
+static int order_out(tse_ctx* c, hipStream_t us) {
+  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
+  else HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
 
 static int view_io(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream, bool get) {
   const char* who = get ? "tse_view_get" : "tse_view_put";
@@ -1734,23 +1766,18 @@ static int view_io(tse_ctx* c, const char* field, int nt, const tse_view* v, voi
     case VF_LNPS: lib = c->lnps; break;
   }
   if (!lib) return fail("%s: the library holds no field \"%s\"", who, field);
-  if (us && !c->view_ev[0])
-    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-
+  if (order_in(c, us)) return 1;
   // the side effects of the host entry that writes the same field (tse_copy_qdp_h2d; tse_set_derived)
   if (!get) {
     if (p.field == VF_QDP || p.field == VF_DP) set_bounds_cache(c, 0);
     if (p.field == VF_DP || p.field == VF_OMEGA_P) c->dcmip_static = false;
   }
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
   {
     Scope s(c, "view");
     if (get) launch_view<false>(c, p, v, lib); else launch_view<true>(c, p, v, lib);
     LAUNCH_CHECK();
   }
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
-  else HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  return order_out(c, us);
 }
 int tse_view_put(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream) { return view_io(c, field, nt, v, stream, false); }
 int tse_view_get(tse_ctx* c, const char* field, int nt, const tse_view* v, void* stream) { return view_io(c, field, nt, v, stream, true); }
@@ -1769,41 +1796,34 @@ static int forcing_args(tse_ctx* c, const char* who, int nt, double dt, int mode
 template <int MODE, bool BUDGET>
 static void launch_forcing(tse_ctx* c, const ViewPlan& p, const tse_view* v, int nt, double dt, double* budget_d) {
   const long long* s = v->stride;
-  const bool base16 = ((uintptr_t)v->ptr & 15) == 0;
   const dim3 grid((unsigned)((size_t)c->nelemd * c->qsize));
-#define TSE_FORCING(PATH, W) hipLaunchKernelGGL((k_forcing<MODE, PATH, W, BUDGET>), grid, dim3(VIEW_THREADS), 0, c->stream, c->qsize, s[0], s[1], s[2], s[3], s[4], dt, \
-    (const double*)c->ps_v, (const double*)c->hyai, (const double*)c->hybi, c->ps0, (const double*)c->spheremp, c->q(nt), (const double*)v->ptr, budget_d)
-  if (p.path == 0) {
-    if (base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0) TSE_FORCING(0, true); else TSE_FORCING(0, false);
-  } else if (p.path == 1) {
-    if (base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0) TSE_FORCING(1, true); else TSE_FORCING(1, false);
-  } else TSE_FORCING(2, false);
-#undef TSE_FORCING
+  with_view_path(p.path, view_wide(p.path, v), [&](auto path, auto wide) {
+    hipLaunchKernelGGL((k_forcing<MODE, decltype(path)::value, decltype(wide)::value, BUDGET>), grid, dim3(VIEW_THREADS), 0, c->stream, c->qsize, s[0], s[1], s[2],
+                       s[3], s[4], dt, (const double*)c->ps_v, (const double*)c->hyai, (const double*)c->hybi, c->ps0, (const double*)c->spheremp, c->q(nt),
+                       (const double*)v->ptr, budget_d);
+  });
 }
 // every check has passed: order behind the caller's stream, launch, hand the order back; with a budget (host [nelemd][qsize][2]) the call
 // is complete on return
-static int forcing_run(tse_ctx* c, const char* who, int nt, double dt, int mode, const ViewPlan& p, const tse_view* v, hipStream_t us, double* budget) {
+struct DeviceBuffer { double* p = nullptr; ~DeviceBuffer() { if (p) (void)hipFree(p); } };   // the budget on the device: given back on every return
+static int forcing_run(tse_ctx* c, int nt, double dt, int mode, const ViewPlan& p, const tse_view* v, hipStream_t us, double* budget) {
   const size_t nb = (size_t)c->nelemd * c->qsize * 2;
-  double* bd = nullptr;
-  if (budget && dalloc(&bd, nb)) return 1;
-  auto give_up = [&](int rc) { if (bd) (void)hipFree(bd); return rc; };
-  if (us && !c->view_ev[0])
-    for (hipEvent_t& e : c->view_ev)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return give_up(fail("%s: cannot create an event", who)); }
+  DeviceBuffer b;
+  if (budget && dalloc(&b.p, nb)) return 1;
+  double* const bd = b.p;
+  if (order_in(c, us)) return 1;
   set_bounds_cache(c, 0);   // the side effects of tse_copy_qdp_h2d: the cached element bounds are dropped, Q / lnps are stale
-  int rc = 0;
-  if (us) rc = hipEventRecord(c->view_ev[0], us) != hipSuccess || hipStreamWaitEvent(c->stream, c->view_ev[0], 0) != hipSuccess;
-  if (!rc) {
+  {
     Scope s(c, "forcing");
     if (mode == TSE_FORCING_TENDENCY) { if (bd) launch_forcing<0, true>(c, p, v, nt, dt, bd); else launch_forcing<0, false>(c, p, v, nt, dt, bd); }
     else { if (bd) launch_forcing<1, true>(c, p, v, nt, dt, bd); else launch_forcing<1, false>(c, p, v, nt, dt, bd); }
-    rc = hipGetLastError() != hipSuccess;
+    LAUNCH_CHECK();
   }
-  if (!rc && us) rc = hipEventRecord(c->view_ev[1], c->stream) != hipSuccess || hipStreamWaitEvent(us, c->view_ev[1], 0) != hipSuccess;
-  if (!rc && bd) rc = hipMemcpyAsync(budget, bd, nb * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess;
-  if (!rc && (bd || !us)) rc = hipStreamSynchronize(c->stream) != hipSuccess;
-  if (rc) { (void)hipGetLastError(); rc = fail("%s: launch or copy failed", who); }
-  return give_up(rc);
+  if (!bd) return order_out(c, us);
+  if (us && order_out(c, us)) return 1;
+  HIPCHK(hipMemcpyAsync(budget, bd, nb * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 int tse_apply_forcing(tse_ctx* c, int nt, double dt, int mode, const tse_view* fq, void* stream, double* budget) {
   const char* who = "tse_apply_forcing";
@@ -1814,7 +1834,7 @@ int tse_apply_forcing(tse_ctx* c, int nt, double dt, int mode, const tse_view* f
   const __int128 p0 = (__int128)(uintptr_t)fq->ptr, f0 = p0 + (__int128)p.lo * 8, f1 = p0 + (__int128)p.hi * 8;
   const __int128 q0 = (__int128)(uintptr_t)c->q(nt), q1 = q0 + (__int128)c->trc() * 8;
   if (f0 < q1 && q0 < f1) return fail("%s: the view [%p%+lld, %p%+lld doubles) overlaps Qdp(%d), the field it is applied to", who, fq->ptr, p.lo, fq->ptr, p.hi, nt);
-  return forcing_run(c, who, nt, dt, mode, p, fq, (hipStream_t)stream, budget);
+  return forcing_run(c, nt, dt, mode, p, fq, (hipStream_t)stream, budget);
 }
 int tse_apply_forcing_host(tse_ctx* c, int nt, double dt, int mode, const double* fq1, size_t stride, int qsize_d, double* budget) {
   const char* who = "tse_apply_forcing_host";
@@ -1839,24 +1859,14 @@ int tse_apply_forcing_host(tse_ctx* c, int nt, double dt, int mode, const double
   ViewPlan p;
   std::string err;
   if (view_plan("qdp", c->nelemd, c->qsize, &v, false, &p, &err)) return fail("%s: %s", who, err.c_str());
-  return forcing_run(c, who, nt, dt, mode, p, &v, nullptr, budget);   // (null stream: complete on return, the caller may reuse FQ)
+  return forcing_run(c, nt, dt, mode, p, &v, nullptr, budget);   // (null stream: complete on return, the caller may reuse FQ)
 }
 
 // ---- vertical remap of a resident host's own level fields (k_remap_view_check, k_remap_view: tse_kernels.h) ------------------------
 // The plans and the overlap test are host code (tse_views.cpp: remap_view_plan); here the checks that need the runtime, the stream order
 // of tse_view_put and two launches on the compute stream: the check kernel decides per element whether the bracket search can end on the
-// two grids (the test of check_remap_grids, on the device: the grids never visit the host), the remap kernel leaves a refused element alone.
-static constexpr size_t REMAP_VIEW_LDS = sizeof(RemapLds), REMAP_VIEW_LDS_MEAN = sizeof(RemapLds) + sizeof(double) * NLEV * 16;
-template <class F>
-static int with_remap_view(bool alg2, bool mean, bool wide, F&& f) {
-  if (mean) {
-    if (alg2) return wide ? f(k_remap_view<true, true, true>, REMAP_VIEW_LDS_MEAN) : f(k_remap_view<true, true, false>, REMAP_VIEW_LDS_MEAN);
-    return wide ? f(k_remap_view<false, true, true>, REMAP_VIEW_LDS_MEAN) : f(k_remap_view<false, true, false>, REMAP_VIEW_LDS_MEAN);
-  }
-  if (alg2) return wide ? f(k_remap_view<true, false, true>, REMAP_VIEW_LDS) : f(k_remap_view<true, false, false>, REMAP_VIEW_LDS);
-  return wide ? f(k_remap_view<false, false, true>, REMAP_VIEW_LDS) : f(k_remap_view<false, false, false>, REMAP_VIEW_LDS);
-}
-static_assert(REMAP_VIEW_LDS_MEAN <= 160 * 1024, "RemapLds and the target thicknesses of a layer-mean field fit a CU's LDS");
+// two grids (the test of check_remap_grids, on the device: the grids never visit the host), the remap kernel leaves a refused element alone
+// (its instantiation: with_remap_view, tse_launch.h).
 static int remap_view_buffers(tse_ctx* c) {
   if (c->rv_acc) return 0;
   for (int i = 0; i < 8; i++) {   // (the attribute is per kernel and device; set once per context, before the first launch)
@@ -1883,35 +1893,24 @@ int tse_remap_view(tse_ctx* c, int nf, int mode, int alg, const tse_view* field,
   if (c->nelemd >= (1 << 24)) return fail("%s: %d elements (the status word holds 24 bits of element index)", who, c->nelemd);
   ViewPlan p[3];
   { std::string err; if (remap_view_plan(c->nelemd, nf, field, dp_src, dp_tgt, p, &err)) return fail("%s", err.c_str()); }
-  const tse_view* v[3] = {field, dp_src, dp_tgt};
-  const char* name[3] = {"tse_remap_view: field", "tse_remap_view: dp_src", "tse_remap_view: dp_tgt"};
+  // the library's own memory: only its Qdp, and only as the field (a host with real dynamics remaps the engine's tracers on its own grids)
   bool own_qdp = false;
-  const std::vector<void*> mine = device_allocations(c);
-  for (int i = 0; i < 3; i++) {
-    void* alloc = nullptr;
-    if (view_runtime_checks(c, name[i], i == 0 ? "qdp" : "dp", p[i], v[i], stream, &alloc)) return 1;
-    if (std::find(mine.begin(), mine.end(), alloc) == mine.end()) continue;
-    // the library's own memory: only its Qdp, and only as the field (a host with real dynamics remaps the engine's tracers on its own grids)
-    if (i == 0 && (alloc == c->q(1) || alloc == c->q(2))) own_qdp = true;
-    else return fail("%s: %p lies inside an allocation of the library that is not qdp1 or qdp2 (or is not the field); the call works on the host's own arrays", name[i], v[i]->ptr);
-  }
+  if (host_array_checks(c, {{"tse_remap_view: field", nullptr, &p[0], field}, {"tse_remap_view: dp_src", nullptr, &p[1], dp_src},
+                            {"tse_remap_view: dp_tgt", nullptr, &p[2], dp_tgt}}, stream, &own_qdp)) return 1;
   { std::string err; if (remap_view_overlap(field, dp_src, dp_tgt, p, &err)) return fail("%s", err.c_str()); }
   if (remap_view_buffers(c)) return 1;
   hipStream_t us = (hipStream_t)stream;
-  if (us && !c->view_ev[0])
-    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 
   RemapViewArgs a;
   a.field = (double*)field->ptr; a.src = (const double*)dp_src->ptr; a.tgt = (const double*)dp_tgt->ptr;
   for (int k = 0; k < 5; k++) { a.fs[k] = field->stride[k]; a.ss[k] = dp_src->stride[k]; a.ts[k] = dp_tgt->stride[k]; }
   a.spath = p[1].path; a.tpath = p[2].path;
-  // level-fastest rows whose chunks of CL levels are 16-byte aligned in every column: k_view_levels' WIDE rule
-  const long long* s = field->stride;
-  const bool wide = p[0].path == 1 && ((uintptr_t)field->ptr & 15) == 0 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
+  // level-fastest rows whose chunks of CL levels are 16-byte aligned in every column; the kernel has no wide form of path 0
+  const bool wide = p[0].path == 1 && view_wide(1, field);
   const bool mean = mode == TSE_REMAP_MEAN;
 
+  if (order_in(c, us)) return 1;
   if (own_qdp) set_bounds_cache(c, 0);   // the side effects of tse_copy_qdp_h2d
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
   {
     Scope sc(c, "fieldremap");
     hipLaunchKernelGGL(k_remap_view_check<>, dim3(c->nelemd), dim3(REMAP_CHECK_THREADS), 0, c->stream, a, (int)mean, c->rv_status, c->rv_detail,
@@ -1924,8 +1923,7 @@ int tse_remap_view(tse_ctx* c, int nf, int mode, int alg, const tse_view* field,
   }
   if (us) {
     c->rv_seq++;
-    HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0));
-    return 0;
+    return order_out(c, us);
   }
   // complete on return: the verdicts come back, the lowest refused element is named
   std::vector<int> st((size_t)c->nelemd * REMAP_STATUS);
@@ -1964,9 +1962,10 @@ int tse_remap_view_status(tse_ctx* c, int* nrefused, int where[4]) {
 }
 
 // ---- DSS of a resident host's own fields (k_dss_view_stage, k_dss_view_sum: tse_kernels.h) -----------------------------------------
-// The plan is host code (tse_views.cpp: dss_view_plan); here the checks that need the runtime, the stream order of tse_view_put, and on the
-// compute stream: stage -> (pack -> halo_exchange kind 0 with nf * nk layers, on a rank with neighbours) -> sum.  The staging field and the
-// halo buffers are the call's own; a steady-state call allocates nothing.
+// The plan is host code (tse_views.cpp: dss_view_plan); here the checks that need the runtime and one call of stage_exchange_out, which
+// tse_biharmonic_view and tse_vlaplace_view share: the stream order of tse_view_put, and on the compute stream
+// stage -> (pack -> halo_exchange kind 0 with nl = nf * nk layers, on a rank with neighbours) -> out.  The staging field and the halo
+// buffers are these calls' own; a steady-state call allocates nothing.
 static int dss_view_buffers(tse_ctx* c, size_t nl) {
   if (nl <= c->dv_layers) return 0;
   HIPCHK(hipStreamSynchronize(c->stream));   // (an earlier call may still read the buffers that are given back)
@@ -1978,24 +1977,66 @@ static int dss_view_buffers(tse_ctx* c, size_t nl) {
   c->dv_layers = nl;
   return 0;
 }
+static DssViewArgs dss_view_args(int nf, int nk, const tse_view* v) {
+  DssViewArgs a;
+  for (int k = 0; k < 5; k++) a.vs[k] = v->stride[k];
+  a.nf = nf; a.nk = nk;
+  return a;
+}
+// the staged field's rank-boundary columns to the neighbour ranks and theirs into dv_recv
+static int stage_exchange(tse_ctx* c, size_t nl, unsigned pack_blocks) {
+  CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
+  if (c->ncol_send) {
+    CommScope sc(c, "comm_pack_q", c->stream);
+    hipLaunchKernelGGL(k_pack<>, dim3(pack_blocks), dim3(256), 0, c->stream, c->ncol_send, (int)nl, c->send_src, (const double*)c->dv_stage, (const double*)nullptr,
+                       c->dv_send, (int)nl, 0, (int)nl);
+    LAUNCH_CHECK();
+  }
+  return halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv);
+}
+// What follows the checks of the three entries.  group: the timer group of the two kernels; exchange: whether the staged field goes to
+// the neighbour ranks in between; stage / out: launch the entry's two kernels on the compute stream.
+template <class Stage, class Out>
+static int stage_exchange_out(tse_ctx* c, const char* group, size_t nl, bool exchange, hipStream_t us, Stage&& stage, Out&& out) {
+  unsigned pack_blocks = 0;
+  if (exchange && c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
+  if (dss_view_buffers(c, nl)) return 1;
+  if (order_in(c, us)) return 1;
+  {
+    Scope sc(c, group);
+    stage();
+    LAUNCH_CHECK();
+  }
+  if (exchange && stage_exchange(c, nl, pack_blocks)) return 1;
+  {
+    Scope sc(c, group);
+    out();
+    LAUNCH_CHECK();
+  }
+  return order_out(c, us);
+}
+// the grid of a kernel's level-fastest path: one (element, field) tile per block, for the second kernel the elements padded to groups of 8
+static dim3 view_tiles(int nelemd, int nf, bool padded) { return dim3((unsigned)((padded ? 8ll * ((nelemd + 7) >> 3) : (long long)nelemd) * nf)); }
+
 template <int MODE>
 static void launch_dss_view_stage(tse_ctx* c, int path, bool wide, const DssViewArgs& a, const double* view) {
   const size_t slabs = (size_t)c->nelemd * a.nf * a.nk;
-  auto blocks = [](size_t items) { return dim3((unsigned)((items + VIEW_THREADS - 1) / VIEW_THREADS)); };
-#define TSE_DSS_STAGE(PATH, W, grid) hipLaunchKernelGGL((k_dss_view_stage<PATH, W, MODE>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, (const double*)c->spheremp, view, c->dv_stage)
-  if (path == 0) { if (wide) TSE_DSS_STAGE(0, true, blocks(slabs * 8)); else TSE_DSS_STAGE(0, false, blocks(slabs * 16)); }
-  else if (path == 1) { const dim3 grid((unsigned)((size_t)c->nelemd * a.nf)); if (wide) TSE_DSS_STAGE(1, true, grid); else TSE_DSS_STAGE(1, false, grid); }
-  else TSE_DSS_STAGE(2, false, blocks(slabs * 16));
-#undef TSE_DSS_STAGE
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    constexpr bool W = decltype(wc)::value;
+    const dim3 grid = PATH == 1 ? view_tiles(c->nelemd, a.nf, false) : view_blocks(slabs * (W ? 8 : 16));
+    hipLaunchKernelGGL((k_dss_view_stage<PATH, W, MODE>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, (const double*)c->spheremp, view, c->dv_stage);
+  });
 }
 static void launch_dss_view_sum(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double* view) {
   const long long nl = (long long)a.nf * a.nk;
-#define TSE_DSS_SUM(PATH, W, nblocks) hipLaunchKernelGGL((k_dss_view_sum<PATH, W>), dim3((unsigned)(nblocks)), dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, (const int2*)c->dss_tab, \
-    (const double*)c->rspheremp, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view)
-  if (path == 0) { if (wide) TSE_DSS_SUM(0, true, dss_view_sum_blocks(c->nelemd, nl * 8)); else TSE_DSS_SUM(0, false, dss_view_sum_blocks(c->nelemd, nl * 16)); }
-  else if (path == 1) { const long long nb = 8ll * ((c->nelemd + 7) >> 3) * a.nf; if (wide) TSE_DSS_SUM(1, true, nb); else TSE_DSS_SUM(1, false, nb); }
-  else TSE_DSS_SUM(2, false, dss_view_sum_blocks(c->nelemd, nl * 16));
-#undef TSE_DSS_SUM
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    constexpr bool W = decltype(wc)::value;
+    const dim3 grid = PATH == 1 ? view_tiles(c->nelemd, a.nf, true) : dim3((unsigned)dss_view_sum_blocks(c->nelemd, nl * (W ? 8 : 16)));
+    hipLaunchKernelGGL((k_dss_view_sum<PATH, W>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, (const int2*)c->dss_tab, (const double*)c->rspheremp,
+                       (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view);
+  });
 }
 
 int tse_dss_view(tse_ctx* c, int nf, int nk, int mode, const tse_view* field, void* stream) {
@@ -2006,87 +2047,33 @@ int tse_dss_view(tse_ctx* c, int nf, int nk, int mode, const tse_view* field, vo
   { std::string err; if (dss_view_plan(c->nelemd, nf, nk, field, &p, &err)) return fail("%s", err.c_str()); }
   const size_t nl = (size_t)nf * nk;
   if ((size_t)c->nelemd * nl >= ((size_t)1 << 27)) return fail("%s: %d elements x %zu layers (the launches count 32-bit blocks)", who, c->nelemd, nl);
-  void* alloc = nullptr;
-  if (view_runtime_checks(c, who, "field", p, field, stream, &alloc)) return 1;
-  const std::vector<void*> mine = device_allocations(c);
-  if (std::find(mine.begin(), mine.end(), alloc) != mine.end())
-    return fail("%s: %p lies inside an allocation of the library; the call works on the host's own arrays", who, field->ptr);
-  unsigned pack_blocks = 0;
-  if (c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
-  if (dss_view_buffers(c, nl)) return 1;
-  hipStream_t us = (hipStream_t)stream;
-  if (us && !c->view_ev[0])
-    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-
-  DssViewArgs a;
-  for (int k = 0; k < 5; k++) a.vs[k] = field->stride[k];
-  a.nf = nf; a.nk = nk;
-  // 16 bytes per lane on the view side: k_view_lines' rule on path 0, k_view_levels' on path 1
-  const long long* s = field->stride;
-  const bool base16 = ((uintptr_t)field->ptr & 15) == 0;
-  const bool wide = p.path == 0 ? base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0 : p.path == 1 && base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
-
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
-  {
-    Scope sc(c, "fielddss");
-    if (mode == TSE_DSS_AVERAGE) launch_dss_view_stage<0>(c, p.path, wide, a, (const double*)field->ptr);
-    else launch_dss_view_stage<1>(c, p.path, wide, a, (const double*)field->ptr);
-    LAUNCH_CHECK();
-  }
-  if (c->halo()) {
-    CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
-    if (c->ncol_send) {
-      CommScope sc(c, "comm_pack_q", c->stream);
-      hipLaunchKernelGGL(k_pack<>, dim3(pack_blocks), dim3(256), 0, c->stream, c->ncol_send, (int)nl, c->send_src, (const double*)c->dv_stage, (const double*)nullptr,
-                         c->dv_send, (int)nl, 0, (int)nl);
-      LAUNCH_CHECK();
-    }
-    if (halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv)) return 1;
-  }
-  {
-    Scope sc(c, "fielddss");
-    launch_dss_view_sum(c, p.path, wide, a, (double*)field->ptr);
-    LAUNCH_CHECK();
-  }
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
-  else HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  if (host_array_checks(c, {{who, nullptr, &p, field}}, stream)) return 1;
+  const DssViewArgs a = dss_view_args(nf, nk, field);
+  const bool wide = view_wide(p.path, field);
+  return stage_exchange_out(c, "fielddss", nl, c->halo(), (hipStream_t)stream,
+    [&] { if (mode == TSE_DSS_AVERAGE) launch_dss_view_stage<0>(c, p.path, wide, a, (const double*)field->ptr); else launch_dss_view_stage<1>(c, p.path, wide, a, (const double*)field->ptr); },
+    [&] { launch_dss_view_sum(c, p.path, wide, a, (double*)field->ptr); });
 }
 
 // ---- weak Laplacian / biharmonic of a resident host's own scalar fields (k_lap_view_stage, k_lap_view_out: tse_kernels.h) ------------
-// The plan is host code (tse_views.cpp: biharmonic_view_plan / biharmonic_view_overlap); here the checks that need the runtime, the
-// stream order of tse_view_put, and on the compute stream: stage -> (order 2 on a rank with neighbours: pack -> halo_exchange kind 0 with
-// nf * nk layers) -> out.  The buffers are tse_dss_view's (dss_view_buffers); a steady-state call allocates nothing.
-// 16 bytes per lane on the view side: k_view_lines' rule on path 0, k_view_levels' on path 1
-static bool dss_view_wide(int path, const tse_view* v) {
-  const long long* s = v->stride;
-  const bool base16 = ((uintptr_t)v->ptr & 15) == 0;
-  return path == 0 ? base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[2] % 2 == 0 : path == 1 && base16 && s[0] % 2 == 0 && s[1] % 2 == 0 && s[4] % 2 == 0;
-}
-static DssViewArgs dss_view_args(int nf, int nk, const tse_view* v) {
-  DssViewArgs a;
-  for (int k = 0; k < 5; k++) a.vs[k] = v->stride[k];
-  a.nf = nf; a.nk = nk;
-  return a;
-}
+// The plan is host code (tse_views.cpp: biharmonic_view_plan / biharmonic_view_overlap); here the checks that need the runtime and
+// stage_exchange_out with tse_dss_view's buffers; the exchange for order 2 alone.
 static void launch_lap_view_stage(tse_ctx* c, int path, bool wide, const DssViewArgs& a, const double* view) {
   const long long quads = (long long)c->nelemd * lap_view_groups((long long)a.nf * a.nk);
-  const dim3 flat((unsigned)((quads * 4 + VIEW_THREADS - 1) / VIEW_THREADS)), tiles((unsigned)((size_t)c->nelemd * a.nf));
-#define TSE_LAP_STAGE(PATH, W, grid) hipLaunchKernelGGL((k_lap_view_stage<PATH, W>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), view, c->dv_stage)
-  if (path == 0) { if (wide) TSE_LAP_STAGE(0, true, flat); else TSE_LAP_STAGE(0, false, flat); }
-  else if (path == 1) { if (wide) TSE_LAP_STAGE(1, true, tiles); else TSE_LAP_STAGE(1, false, tiles); }
-  else TSE_LAP_STAGE(2, false, flat);
-#undef TSE_LAP_STAGE
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    const dim3 grid = PATH == 1 ? view_tiles(c->nelemd, a.nf, false) : view_blocks((size_t)quads * 4);
+    hipLaunchKernelGGL((k_lap_view_stage<PATH, decltype(wc)::value>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), view, c->dv_stage);
+  });
 }
 template <int ORDER>
 static void launch_lap_view_out(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double* view) {
-  const dim3 flat((unsigned)lap_view_out_blocks(c->nelemd, (long long)a.nf * a.nk)), tiles((unsigned)(8ll * ((c->nelemd + 7) >> 3) * a.nf));
-#define TSE_LAP_OUT(PATH, W, grid) hipLaunchKernelGGL((k_lap_view_out<PATH, W, ORDER>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), \
-    (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view)
-  if (path == 0) { if (wide) TSE_LAP_OUT(0, true, flat); else TSE_LAP_OUT(0, false, flat); }
-  else if (path == 1) { if (wide) TSE_LAP_OUT(1, true, tiles); else TSE_LAP_OUT(1, false, tiles); }
-  else TSE_LAP_OUT(2, false, flat);
-#undef TSE_LAP_OUT
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    const dim3 grid = PATH == 1 ? view_tiles(c->nelemd, a.nf, true) : dim3((unsigned)lap_view_out_blocks(c->nelemd, (long long)a.nf * a.nk));
+    hipLaunchKernelGGL((k_lap_view_out<PATH, decltype(wc)::value, ORDER>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(),
+                       (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view);
+  });
 }
 
 int tse_biharmonic_view(tse_ctx* c, int nf, int nk, int order, const tse_view* in, const tse_view* out, void* stream) {
@@ -2098,49 +2085,13 @@ int tse_biharmonic_view(tse_ctx* c, int nf, int nk, int order, const tse_view* i
   { std::string err; if (biharmonic_view_plan(c->nelemd, nf, nk, in, out, p, &err)) return fail("%s", err.c_str()); }
   const size_t nl = (size_t)nf * nk;
   if ((size_t)c->nelemd * nl >= ((size_t)1 << 27)) return fail("%s: %d elements x %zu layers (the launches count 32-bit blocks)", who, c->nelemd, nl);
-  const tse_view* v[2] = {in, out};
-  const std::vector<void*> mine = device_allocations(c);
-  for (int i = 0; i < 2; i++) {
-    void* alloc = nullptr;
-    if (view_runtime_checks(c, who, i ? "out" : "in", p[i], v[i], stream, &alloc)) return 1;
-    if (std::find(mine.begin(), mine.end(), alloc) != mine.end())
-      return fail("%s: %s: %p lies inside an allocation of the library; the call works on the host's own arrays", who, i ? "out" : "in", v[i]->ptr);
-  }
+  if (host_array_checks(c, {{who, "in", &p[0], in}, {who, "out", &p[1], out}}, stream)) return 1;
   { std::string err; if (biharmonic_view_overlap(in, out, p, &err)) return fail("%s", err.c_str()); }
-  const bool exchange = order == TSE_BIHARMONIC && c->halo();
-  unsigned pack_blocks = 0;
-  if (exchange && c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
-  if (dss_view_buffers(c, nl)) return 1;
-  hipStream_t us = (hipStream_t)stream;
-  if (us && !c->view_ev[0])
-    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   const DssViewArgs ai = dss_view_args(nf, nk, in), ao = dss_view_args(nf, nk, out);
-
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
-  {
-    Scope sc(c, "fieldlap");
-    launch_lap_view_stage(c, p[0].path, dss_view_wide(p[0].path, in), ai, (const double*)in->ptr);
-    LAUNCH_CHECK();
-  }
-  if (exchange) {
-    CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
-    if (c->ncol_send) {
-      CommScope sc(c, "comm_pack_q", c->stream);
-      hipLaunchKernelGGL(k_pack<>, dim3(pack_blocks), dim3(256), 0, c->stream, c->ncol_send, (int)nl, c->send_src, (const double*)c->dv_stage, (const double*)nullptr,
-                         c->dv_send, (int)nl, 0, (int)nl);
-      LAUNCH_CHECK();
-    }
-    if (halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv)) return 1;
-  }
-  {
-    Scope sc(c, "fieldlap");
-    if (order == TSE_LAPLACE) launch_lap_view_out<1>(c, p[1].path, dss_view_wide(p[1].path, out), ao, (double*)out->ptr);
-    else launch_lap_view_out<2>(c, p[1].path, dss_view_wide(p[1].path, out), ao, (double*)out->ptr);
-    LAUNCH_CHECK();
-  }
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
-  else HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  const bool wi = view_wide(p[0].path, in), wo = view_wide(p[1].path, out);
+  return stage_exchange_out(c, "fieldlap", nl, order == TSE_BIHARMONIC && c->halo(), (hipStream_t)stream,
+    [&] { launch_lap_view_stage(c, p[0].path, wi, ai, (const double*)in->ptr); },
+    [&] { if (order == TSE_LAPLACE) launch_lap_view_out<1>(c, p[1].path, wo, ao, (double*)out->ptr); else launch_lap_view_out<2>(c, p[1].path, wo, ao, (double*)out->ptr); });
 }
 
 // ---- weak vector Laplacian / biharmonic of a resident host's own wind (k_vec_fold, k_vlap_view_stage, k_vlap_view_out: tse_kernels.h) ----
@@ -2169,28 +2120,27 @@ int tse_vector_setup(tse_ctx* c, const double* D, size_t D_stride, const double*
   c->vec_ready = true;
   return 0;
 }
+// (the kernels take both components of a level at once: a tile is an element)
 static void launch_vlap_view_stage(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double nu_ratio, const double* view) {
   const long long quads = (long long)c->nelemd * vlap_view_groups(a.nk);
-  const dim3 flat((unsigned)((quads * 4 + VIEW_THREADS - 1) / VIEW_THREADS)), tiles((unsigned)c->nelemd);
-#define TSE_VLAP_STAGE(PATH, W, grid) hipLaunchKernelGGL((k_vlap_view_stage<PATH, W>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), \
-    (const double*)c->vec_tab, nu_ratio, view, c->dv_stage)
-  if (path == 0) { if (wide) TSE_VLAP_STAGE(0, true, flat); else TSE_VLAP_STAGE(0, false, flat); }
-  else if (path == 1) { if (wide) TSE_VLAP_STAGE(1, true, tiles); else TSE_VLAP_STAGE(1, false, tiles); }
-  else TSE_VLAP_STAGE(2, false, flat);
-#undef TSE_VLAP_STAGE
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    const dim3 grid = PATH == 1 ? view_tiles(c->nelemd, 1, false) : view_blocks((size_t)quads * 4);
+    hipLaunchKernelGGL((k_vlap_view_stage<PATH, decltype(wc)::value>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(),
+                       (const double*)c->vec_tab, nu_ratio, view, c->dv_stage);
+  });
 }
 template <int ORDER>
 static void launch_vlap_view_out(tse_ctx* c, int path, bool wide, const DssViewArgs& a, double nu_ratio, double* view) {
-  const dim3 flat((unsigned)vlap_view_out_blocks(c->nelemd, a.nk)), tiles((unsigned)(8ll * ((c->nelemd + 7) >> 3)));
-#define TSE_VLAP_OUT(PATH, W, grid) hipLaunchKernelGGL((k_vlap_view_out<PATH, W, ORDER>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), \
-    (const double*)c->vec_tab, nu_ratio, (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view)
-  if (path == 0) { if (wide) TSE_VLAP_OUT(0, true, flat); else TSE_VLAP_OUT(0, false, flat); }
-  else if (path == 1) { if (wide) TSE_VLAP_OUT(1, true, tiles); else TSE_VLAP_OUT(1, false, tiles); }
-  else TSE_VLAP_OUT(2, false, flat);
-#undef TSE_VLAP_OUT
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    const dim3 grid = PATH == 1 ? view_tiles(c->nelemd, 1, true) : dim3((unsigned)vlap_view_out_blocks(c->nelemd, a.nk));
+    hipLaunchKernelGGL((k_vlap_view_out<PATH, decltype(wc)::value, ORDER>), grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(),
+                       (const double*)c->vec_tab, nu_ratio, (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, view);
+  });
 }
 
-// As tse_biharmonic_view with nf = 2 (the plan is vlaplace_view_plan, tse_views.cpp); the kernels take both components of a level at once.
+// As tse_biharmonic_view with nf = 2 (the plan is vlaplace_view_plan, tse_views.cpp).
 int tse_vlaplace_view(tse_ctx* c, int nk, int order, double nu_ratio, const tse_view* in, const tse_view* out, void* stream) {
   const char* who = "tse_vlaplace_view";
   if (!c) return fail("%s: null context", who);
@@ -2202,49 +2152,13 @@ int tse_vlaplace_view(tse_ctx* c, int nk, int order, double nu_ratio, const tse_
   { std::string err; if (vlaplace_view_plan(c->nelemd, nk, in, out, p, &err)) return fail("%s", err.c_str()); }
   const size_t nl = (size_t)2 * nk;
   if ((size_t)c->nelemd * nl >= ((size_t)1 << 27)) return fail("%s: %d elements x %zu layers (the launches count 32-bit blocks)", who, c->nelemd, nl);
-  const tse_view* v[2] = {in, out};
-  const std::vector<void*> mine = device_allocations(c);
-  for (int i = 0; i < 2; i++) {
-    void* alloc = nullptr;
-    if (view_runtime_checks(c, who, i ? "out" : "in", p[i], v[i], stream, &alloc)) return 1;
-    if (std::find(mine.begin(), mine.end(), alloc) != mine.end())
-      return fail("%s: %s: %p lies inside an allocation of the library; the call works on the host's own arrays", who, i ? "out" : "in", v[i]->ptr);
-  }
+  if (host_array_checks(c, {{who, "in", &p[0], in}, {who, "out", &p[1], out}}, stream)) return 1;
   { std::string err; if (biharmonic_view_overlap(in, out, p, &err, who)) return fail("%s", err.c_str()); }
-  const bool exchange = order == TSE_VBIHARMONIC && c->halo();
-  unsigned pack_blocks = 0;
-  if (exchange && c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
-  if (dss_view_buffers(c, nl)) return 1;
-  hipStream_t us = (hipStream_t)stream;
-  if (us && !c->view_ev[0])
-    for (hipEvent_t& e : c->view_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   const DssViewArgs ai = dss_view_args(2, nk, in), ao = dss_view_args(2, nk, out);
-
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[0], us)); HIPCHK(hipStreamWaitEvent(c->stream, c->view_ev[0], 0)); }
-  {
-    Scope sc(c, "fieldvlap");
-    launch_vlap_view_stage(c, p[0].path, dss_view_wide(p[0].path, in), ai, nu_ratio, (const double*)in->ptr);
-    LAUNCH_CHECK();
-  }
-  if (exchange) {
-    CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
-    if (c->ncol_send) {
-      CommScope sc(c, "comm_pack_q", c->stream);
-      hipLaunchKernelGGL(k_pack<>, dim3(pack_blocks), dim3(256), 0, c->stream, c->ncol_send, (int)nl, c->send_src, (const double*)c->dv_stage, (const double*)nullptr,
-                         c->dv_send, (int)nl, 0, (int)nl);
-      LAUNCH_CHECK();
-    }
-    if (halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv)) return 1;
-  }
-  {
-    Scope sc(c, "fieldvlap");
-    if (order == TSE_VLAPLACE) launch_vlap_view_out<1>(c, p[1].path, dss_view_wide(p[1].path, out), ao, nu_ratio, (double*)out->ptr);
-    else launch_vlap_view_out<2>(c, p[1].path, dss_view_wide(p[1].path, out), ao, nu_ratio, (double*)out->ptr);
-    LAUNCH_CHECK();
-  }
-  if (us) { HIPCHK(hipEventRecord(c->view_ev[1], c->stream)); HIPCHK(hipStreamWaitEvent(us, c->view_ev[1], 0)); }
-  else HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  const bool wi = view_wide(p[0].path, in), wo = view_wide(p[1].path, out);
+  return stage_exchange_out(c, "fieldvlap", nl, order == TSE_VBIHARMONIC && c->halo(), (hipStream_t)stream,
+    [&] { launch_vlap_view_stage(c, p[0].path, wi, ai, nu_ratio, (const double*)in->ptr); },
+    [&] { if (order == TSE_VLAPLACE) launch_vlap_view_out<1>(c, p[1].path, wo, ao, nu_ratio, (double*)out->ptr); else launch_vlap_view_out<2>(c, p[1].path, wo, ao, nu_ratio, (double*)out->ptr); });
 }
 
 // ---- introspection ------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 //
 // limiter_option and vert_remap_q_alg are fields of tse_ctx, the kernels take them as template parameters (LIM and LOPT of k_advance,
 // LIM of k_lap1; NT, ALG2 and FUSED of k_remap).  The mapping from the one to the other is written here once: a new limiter is one
-// more row of with_limiter, a new remap variant one more row of with_remap.  Host code only: no kernel's signature or arguments change.
+// more row of with_limiter, a new remap variant one more row of with_remap.  The kernels that work on a resident host's own arrays take the
+// path of the view and whether a lane moves 16 bytes as <PATH, WIDE>: with_view_path.  Host code only: no kernel's signature or arguments change.
 #pragma once
 #include <type_traits>
 
@@ -68,6 +69,31 @@ inline int with_every_remap(F&& f) {
       for (int alg2 = 0; alg2 < 2; alg2++)
         if (int rc = with_remap(nt, alg2 != 0, fused != 0, f)) return rc;
   return 0;
+}
+
+// tse_remap_view: (vert_remap_q_alg == 2, the field is a layer mean, 16 bytes per lane) -> f(k_remap_view instantiation, bytes of dynamic
+// LDS); returns what f returns.  A layer-mean field keeps its target thicknesses in LDS behind RemapLds.
+constexpr size_t REMAP_VIEW_LDS = sizeof(RemapLds), REMAP_VIEW_LDS_MEAN = sizeof(RemapLds) + sizeof(double) * NLEV * 16;
+static_assert(REMAP_VIEW_LDS_MEAN <= 160 * 1024, "RemapLds and the target thicknesses of a layer-mean field fit a CU's LDS");
+template <class F>
+inline int with_remap_view(bool alg2, bool mean, bool wide, F&& f) {
+  if (mean) {
+    if (alg2) return wide ? f(k_remap_view<true, true, true>, REMAP_VIEW_LDS_MEAN) : f(k_remap_view<true, true, false>, REMAP_VIEW_LDS_MEAN);
+    return wide ? f(k_remap_view<false, true, true>, REMAP_VIEW_LDS_MEAN) : f(k_remap_view<false, true, false>, REMAP_VIEW_LDS_MEAN);
+  }
+  if (alg2) return wide ? f(k_remap_view<true, false, true>, REMAP_VIEW_LDS) : f(k_remap_view<true, false, false>, REMAP_VIEW_LDS);
+  return wide ? f(k_remap_view<false, false, true>, REMAP_VIEW_LDS) : f(k_remap_view<false, false, false>, REMAP_VIEW_LDS);
+}
+
+// (path of a view's plan, view_wide of that path and view: tse_views.h) -> <PATH, WIDE>, handed to f as two integral constants: the five
+// pairs (0, t) (0, f) (1, t) (1, f) (2, f).  The generic path moves one double per lane whatever `wide` says: <2, true> is never instantiated.
+template <class F>
+inline void with_view_path(int path, bool wide, F&& f) {
+  const std::integral_constant<int, 0> p0{}; const std::integral_constant<int, 1> p1{}; const std::integral_constant<int, 2> p2{};
+  const std::true_type w{}; const std::false_type n{};
+  if (path == 0) { if (wide) f(p0, w); else f(p0, n); }
+  else if (path == 1) { if (wide) f(p1, w); else f(p1, n); }
+  else f(p2, n);
 }
 
 }  // namespace tse

@@ -73,6 +73,12 @@ static int footprint_and_path(const char* who, ViewPlan& p, const long long* s, 
   return 0;
 }
 
+bool view_wide(int path, const tse_view* v) {
+  const long long* s = v->stride;
+  if (path > 1 || ((uintptr_t)v->ptr & 15) || s[0] % 2 || s[1] % 2) return false;
+  return s[path == 0 ? 2 : 4] % 2 == 0;
+}
+
 int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool for_get, ViewPlan* out, std::string* err) {
   const char* who = for_get ? "tse_view_get" : "tse_view_put";
   if (!field || !v || !out) return refuse(err, "%s: null %s", who, !field ? "field name" : !v ? "view" : "plan");
@@ -198,65 +204,60 @@ int vlaplace_view_plan(int nelemd, int nk, const tse_view* in, const tse_view* o
 
 }  // namespace tse
 
+// the C plan entries: an error becomes the message of tse_last_error; n plans go out as path[] / lo[] / hi[], each of them optional
+static int refused(const std::string& err) { return tse::set_last_error(err.c_str()); }
+static int plans_out(const tse::ViewPlan* p, int n, int* path, long long* lo, long long* hi) {
+  for (int i = 0; i < n; i++) {
+    if (path) path[i] = p[i].path;
+    if (lo) lo[i] = p[i].lo;
+    if (hi) hi[i] = p[i].hi;
+  }
+  return 0;
+}
+
 extern "C" int tse_view_plan(const char* field, int nelemd, int qsize, const tse_view* v, int for_get, int* path, long long* lo, long long* hi) {
   tse::ViewPlan p;
   std::string err;
-  if (tse::view_plan(field, nelemd, qsize, v, for_get != 0, &p, &err)) return tse::set_last_error(err.c_str());
-  if (path) *path = p.path;
-  if (lo) *lo = p.lo;
-  if (hi) *hi = p.hi;
-  return 0;
+  if (tse::view_plan(field, nelemd, qsize, v, for_get != 0, &p, &err)) return refused(err);
+  return plans_out(&p, 1, path, lo, hi);
 }
 
 extern "C" int tse_remap_view_plan(int nelemd, int nf, const tse_view* field, const tse_view* dp_src, const tse_view* dp_tgt, int path[3], long long lo[3],
                                    long long hi[3]) {
   tse::ViewPlan p[3];
   std::string err;
-  if (tse::remap_view_plan(nelemd, nf, field, dp_src, dp_tgt, p, &err)) return tse::set_last_error(err.c_str());
+  if (tse::remap_view_plan(nelemd, nf, field, dp_src, dp_tgt, p, &err)) return refused(err);
   // strides alone (all three ptr null): nothing is known of where the views lie
-  if ((field->ptr || dp_src->ptr || dp_tgt->ptr) && tse::remap_view_overlap(field, dp_src, dp_tgt, p, &err)) return tse::set_last_error(err.c_str());
-  for (int i = 0; i < 3; i++) {
-    if (path) path[i] = p[i].path;
-    if (lo) lo[i] = p[i].lo;
-    if (hi) hi[i] = p[i].hi;
-  }
-  return 0;
+  if ((field->ptr || dp_src->ptr || dp_tgt->ptr) && tse::remap_view_overlap(field, dp_src, dp_tgt, p, &err)) return refused(err);
+  return plans_out(p, 3, path, lo, hi);
 }
 
 extern "C" int tse_dss_view_plan(int nelemd, int nf, int nk, const tse_view* field, int* path, long long* lo, long long* hi) {
   tse::ViewPlan p;
   std::string err;
-  if (tse::dss_view_plan(nelemd, nf, nk, field, &p, &err)) return tse::set_last_error(err.c_str());
-  if (path) *path = p.path;
-  if (lo) *lo = p.lo;
-  if (hi) *hi = p.hi;
-  return 0;
+  if (tse::dss_view_plan(nelemd, nf, nk, field, &p, &err)) return refused(err);
+  return plans_out(&p, 1, path, lo, hi);
 }
 
 extern "C" int tse_biharmonic_view_plan(int nelemd, int nf, int nk, const tse_view* in, const tse_view* out, int path[2], long long lo[2], long long hi[2]) {
   tse::ViewPlan p[2];
   std::string err;
-  if (tse::biharmonic_view_plan(nelemd, nf, nk, in, out, p, &err)) return tse::set_last_error(err.c_str());
+  if (tse::biharmonic_view_plan(nelemd, nf, nk, in, out, p, &err)) return refused(err);
   // strides alone (both ptr null): nothing is known of where the views lie
-  if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err)) return tse::set_last_error(err.c_str());
-  for (int i = 0; i < 2; i++) {
-    if (path) path[i] = p[i].path;
-    if (lo) lo[i] = p[i].lo;
-    if (hi) hi[i] = p[i].hi;
-  }
-  return 0;
+  if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err)) return refused(err);
+  return plans_out(p, 2, path, lo, hi);
 }
 
 extern "C" int tse_vlaplace_view_plan(int nelemd, int nk, const tse_view* in, const tse_view* out, int path[2], long long lo[2], long long hi[2]) {
   tse::ViewPlan p[2];
   std::string err;
-  if (tse::vlaplace_view_plan(nelemd, nk, in, out, p, &err)) return tse::set_last_error(err.c_str());
+  if (tse::vlaplace_view_plan(nelemd, nk, in, out, p, &err)) return refused(err);
   // strides alone (both ptr null): nothing is known of where the views lie
-  if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err, "tse_vlaplace_view")) return tse::set_last_error(err.c_str());
-  for (int i = 0; i < 2; i++) {
-    if (path) path[i] = p[i].path;
-    if (lo) lo[i] = p[i].lo;
-    if (hi) hi[i] = p[i].hi;
-  }
-  return 0;
+  if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err, "tse_vlaplace_view")) return refused(err);
+  return plans_out(p, 2, path, lo, hi);
 }
+
+#ifdef TSE_AB_HOOKS
+// view_wide for the CPU test that holds it to the addresses the kernels touch (tests/test_views_cpu.py); not in the product library
+extern "C" int tse_test_view_wide(int path, const tse_view* v) { return tse::view_wide(path, v) ? 1 : 0; }
+#endif

@@ -21,6 +21,13 @@ struct ViewPlan {
   long long lo = 0, hi = 0;   // footprint [lo, hi) of the view in doubles relative to ptr
 };
 
+// Whether a kernel may move 16 bytes per lane on the view side: on path 0 the double2 parts of every (e, q, k) slab, on path 1 the level
+// pairs of every row of every (e, q) tile.  The base 16-byte aligned, the element and q strides even, and the stride between the units
+// even: the level stride on path 0, the i stride (the pitch of the rows) on path 1.  Never on path 2.  The one statement of the rule:
+// every launch of a kernel with a WIDE parameter asks here (tse_launch.h: with_view_path).  It does not see the extents, so it also
+// refuses a view whose only odd stride belongs to an axis of extent 1.
+bool view_wide(int path, const tse_view* v);
+
 // Returns 0, or 1 with the reason in *err (a refused axis is named).
 int view_plan(const char* field, int nelemd, int qsize, const tse_view* v, bool for_get, ViewPlan* out, std::string* err);
 

@@ -665,6 +665,27 @@ class HipMod:
         self._chk(self.L.tse_dss_view(self.h, int(nf), int(nk), _dss_mode(mode), C.byref(v), _stream_handle(stream)))
 
     # ---- weak Laplacian / biharmonic of the host's own scalar fields (tse_biharmonic_view) ----
+    def _view_pair(self, who, field, axes, out, out_axes, nf, nk, wind=False):
+        """(in view, out view, nf, nk) of biharmonic_view and vlaplace_view: `field` and `out` device arrays (build_dss_view) or ready
+        _lib.Views, out=None in place, out_axes=None the axes of `field`; wind: the q axis is the wind component (nf = 2)"""
+        if isinstance(field, _lib.View):
+            if nf is None or nk is None:
+                raise TseError("%s: %s needed with a ready view" % (who, "nk is" if wind else "nf and nk are"))
+            vi = field
+        else:
+            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=out is None)
+            if wind and nf != 2:
+                raise TseError("%s: the q axis is the wind component and has extent %d, not 2" % (who, nf))
+        if out is None:
+            vo = vi
+        elif isinstance(out, _lib.View):
+            vo = out
+        else:
+            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
+            if (onf, onk) != (nf, nk):
+                raise TseError("%s: out has %d %s of %d levels, field has %d of %d" % (who, onf, "components" if wind else "fields", onk, nf, nk))
+        return vi, vo, nf, nk
+
     def biharmonic_view(self, field, axes, out=None, out_axes=None, order=2, stream=None, nf=None, nk=None):
         """out <- laplace_sphere_wk(field) (order 1 or "laplace": weak, not summed, no exchange) or
         laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(field))) (order 2 or "biharmonic": the reference's biharmonic_wk_scalar before
@@ -674,21 +695,7 @@ class HipMod:
         laplace_sphere_wk on every path of either view and on any number of ranks.  Order 2 is COLLECTIVE on a context with neighbour
         ranks, as dss_view.  Nothing of the library's state is touched.  stream orders as in put.  `field` and `out` may also be ready
         _lib.Views (then nf and nk are needed)."""
-        who = "biharmonic_view"
-        if isinstance(field, _lib.View):
-            if nf is None or nk is None:
-                raise TseError("%s: nf and nk are needed with a ready view" % who)
-            vi = field
-        else:
-            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=out is None)
-        if out is None:
-            vo = vi
-        elif isinstance(out, _lib.View):
-            vo = out
-        else:
-            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
-            if (onf, onk) != (nf, nk):
-                raise TseError("%s: out has %d fields of %d levels, field has %d of %d" % (who, onf, onk, nf, nk))
+        vi, vo, nf, nk = self._view_pair("biharmonic_view", field, axes, out, out_axes, nf, nk)
         self._chk(self.L.tse_biharmonic_view(self.h, int(nf), int(nk), _lap_order(order), C.byref(vi), C.byref(vo), _stream_handle(stream)))
 
     # ---- weak vector Laplacian / biharmonic of the host's own wind (tse_vector_setup, tse_vlaplace_view) ----
@@ -709,23 +716,7 @@ class HipMod:
         those of order 1 -> dss_view(mode="weak") -> order 1 on every path of either view and on any number of ranks.  Order 2 is
         COLLECTIVE on a context with neighbour ranks, as dss_view.  Needs vector_setup.  stream orders as in put.  `field` and `out` may
         also be ready _lib.Views (then nk is needed)."""
-        who = "vlaplace_view"
-        if isinstance(field, _lib.View):
-            if nk is None:
-                raise TseError("%s: nk is needed with a ready view" % who)
-            vi = field
-        else:
-            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=out is None)
-            if nf != 2:
-                raise TseError("%s: the q axis is the wind component and has extent %d, not 2" % (who, nf))
-        if out is None:
-            vo = vi
-        elif isinstance(out, _lib.View):
-            vo = out
-        else:
-            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
-            if (onf, onk) != (2, nk):
-                raise TseError("%s: out has %d components of %d levels, field has 2 of %d" % (who, onf, onk, nk))
+        vi, vo, _, nk = self._view_pair("vlaplace_view", field, axes, out, out_axes, 2, nk, wind=True)
         self._chk(self.L.tse_vlaplace_view(self.h, int(nk), _vlap_order(order), float(nu_ratio), C.byref(vi), C.byref(vo), _stream_handle(stream)))
 
     def last_error(self):
