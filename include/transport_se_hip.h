@@ -434,6 +434,37 @@ int tse_vlaplace_view(tse_ctx *ctx, int nk, int order, double nu_ratio, const ts
 /* the paths and footprints of in ([0]) and out ([1]) and every refusal that needs no device, as tse_biharmonic_view_plan with nf = 2 */
 int tse_vlaplace_view_plan(int nelemd, int nk, const tse_view *in, const tse_view *out, int path[2], long long lo[2], long long hi[2]);
 
+/* ---- first-order sphere operators of a GPU-resident host's OWN fields, element-local or continuous (C0): gradient_sphere,
+ * divergence_sphere and vorticity_sphere of derivative_mod.F90 on nk levels of one view, 1 <= nk <= nlev + 1, and with TSE_OP_C0 the
+ * make_C0 / make_C0_vector of viscosity_mod.F90:445-535 behind them -- compute_zeta_C0, compute_div_C0 (:542-745), the continuous
+ * vorticity and divergence of a dycore's history and physics ----
+ *   TSE_OP_LOCAL  out = op(in) on every element by itself: no exchange, not collective
+ *   TSE_OP_C0     out = rspheremp * (((w + c0) + c1) + c2), w = spheremp * op(in) rounded once: the bits of TSE_OP_LOCAL followed by
+ *                 tse_dss_view(TSE_DSS_AVERAGE, nf_out) on the output array.  COLLECTIVE on a context with neighbour ranks, as tse_dss_view.
+ * Views: `in` and `out` are views of tse_dss_view with nf_in, nf_out = 1, 2 (gradient) or 2, 1 (divergence, vorticity); the q axis of the
+ * two-field side is the component (lat/lon, as "vn0"; state%v(np,np,2,nlev,tl) is {elem_stride, 16, 32, 4, 1}), and the q stride of the
+ * one-field side is free (0 will do).  Each view takes its own path.  The shapes differ, so there is no in-place form: the two footprints
+ * must be disjoint (touching is disjoint).  Only addresses of `out` are written.
+ * The routines are compiled without implicit contraction (divergence spells out the operations of tse_divergence_sphere and has its bits), so a point's
+ * result is one fixed sequence of roundings whatever the paths, the other levels of the call and the number of ranks.  Gradient follows the
+ * reference's operations (rrearth * d/dx, rrearth * d/dy, then Dinv^T); vorticity reads the tables rrearth * D of tse_vector_setup.
+ * Refused: everything tse_biharmonic_view refuses, an op outside 0..2, a c0 outside 0|1, TSE_OP_VORTICITY before tse_vector_setup (it needs
+ * elem%D; gradient and divergence need no set-up).  On failure: nonzero, tse_last_error(), nothing enqueued.
+ * Not part of this entry: the _contra variants (contravariant input), ugradv_sphere, curl_sphere and the weak forms (*_wk).
+ * No library state is read but the geometry and the tables of tse_vector_setup, none is written; the staging and halo buffers are
+ * tse_dss_view's ("view_stage", nf_out * nk layers).  stream orders as in tse_dss_view.  Timer group "fieldop", two launches per call
+ * (the stage kernel; then tse_dss_view's sum kernel for C0, tse_biharmonic_view's copy kernel for LOCAL). */
+#define TSE_OP_GRADIENT   0   /* in: 1 scalar field  -> out: 2 components   gradient_sphere   (derivative_mod.F90:1660-1700) */
+#define TSE_OP_DIVERGENCE 1   /* in: 2 components    -> out: 1 scalar field divergence_sphere (:2364-2414) */
+#define TSE_OP_VORTICITY  2   /* in: 2 components    -> out: 1 scalar field vorticity_sphere  (:2250-2301) */
+#define TSE_OP_LOCAL 0        /* out = op(in): element-local, no exchange, not collective */
+#define TSE_OP_C0    1        /* out = rspheremp * DSS(spheremp * op(in)): make_C0 / make_C0_vector, collective like tse_dss_view */
+int tse_sphere_op_view(tse_ctx *ctx, int nk, int op, int c0, const tse_view *in, const tse_view *out, void *stream);
+/* the paths and footprints of in ([0]) and out ([1]) and every refusal that needs no device, the overlap rule included when either
+ * pointer is non-null */
+int tse_sphere_op_view_plan(int nelemd, int nk, int op, const tse_view *in, const tse_view *out,
+                            int path[2], long long lo[2], long long hi[2]);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -475,11 +506,11 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
  * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference),
  * "remap_status" [nelemd][4] ints (null before the first tse_remap_view), "view_stage" [nelemd][layers][16] the staging field tse_dss_view,
- * tse_biharmonic_view and tse_vlaplace_view share (null before the first call of any; it moves only when a call brings more layers than any before) */
+ * tse_biharmonic_view, tse_vlaplace_view and tse_sphere_op_view share (null before the first call of any; it moves only when a call brings more layers than any before) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), "fieldop" (tse_sphere_op_view: its stage kernel and the sum or copy kernel behind it), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -2161,6 +2161,44 @@ int tse_vlaplace_view(tse_ctx* c, int nk, int order, double nu_ratio, const tse_
     [&] { if (order == TSE_VLAPLACE) launch_vlap_view_out<1>(c, p[1].path, wo, ao, nu_ratio, (double*)out->ptr); else launch_vlap_view_out<2>(c, p[1].path, wo, ao, nu_ratio, (double*)out->ptr); });
 }
 
+// ---- gradient, divergence and vorticity of a resident host's own fields, local or C0 (k_sphere_op_stage: tse_kernels.h) ------------
+// The plan is host code (tse_views.cpp: sphere_op_view_plan / sphere_op_view_overlap).  The stage kernel is the entry's own; the out
+// kernel is tse_dss_view's sum (C0) or tse_biharmonic_view's own-line copy (LOCAL), each with the nf_out fields of `out`.
+static void launch_sphere_op_stage(tse_ctx* c, int path, bool wide, int op, bool c0, const DssViewArgs& a, const double* view) {
+  const long long quads = (long long)c->nelemd * sphere_op_groups(a.nk);
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    constexpr bool W = decltype(wc)::value;
+    const dim3 grid = PATH == 1 ? view_tiles(c->nelemd, 1, false) : view_blocks((size_t)quads * 4);
+    auto go = [&](auto k) {
+      hipLaunchKernelGGL(k, grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, a, c->D, c->geo(), (const double*)c->vec_tab, view, c->dv_stage);
+    };
+    if (op == TSE_OP_GRADIENT) { if (c0) go(k_sphere_op_stage<PATH, W, 0, true>); else go(k_sphere_op_stage<PATH, W, 0, false>); }
+    else if (op == TSE_OP_DIVERGENCE) { if (c0) go(k_sphere_op_stage<PATH, W, 1, true>); else go(k_sphere_op_stage<PATH, W, 1, false>); }
+    else { if (c0) go(k_sphere_op_stage<PATH, W, 2, true>); else go(k_sphere_op_stage<PATH, W, 2, false>); }
+  });
+}
+
+int tse_sphere_op_view(tse_ctx* c, int nk, int op, int c0, const tse_view* in, const tse_view* out, void* stream) {
+  const char* who = "tse_sphere_op_view";
+  if (!c) return fail("%s: null context", who);
+  if (c0 != TSE_OP_LOCAL && c0 != TSE_OP_C0) return fail("%s: c0=%d (0: out = op(in); 1: out = rspheremp * DSS(spheremp * op(in)))", who, c0);
+  ViewPlan p[2];
+  { std::string err; if (sphere_op_view_plan(c->nelemd, nk, op, in, out, p, &err)) return fail("%s", err.c_str()); }
+  if (op == TSE_OP_VORTICITY && !c->vec_ready) return fail("%s: TSE_OP_VORTICITY: call tse_vector_setup first (elem%%D is not part of tse_init_args)", who);
+  int nfi = 0, nfo = 0;
+  sphere_op_fields(op, &nfi, &nfo);
+  const size_t nl = (size_t)nfo * nk;
+  if ((size_t)c->nelemd * 2 * nk >= ((size_t)1 << 27)) return fail("%s: %d elements x %d layers (the launches count 32-bit blocks)", who, c->nelemd, 2 * nk);
+  if (host_array_checks(c, {{who, "in", &p[0], in}, {who, "out", &p[1], out}}, stream)) return 1;
+  { std::string err; if (sphere_op_view_overlap(in, out, p, &err)) return fail("%s", err.c_str()); }
+  const DssViewArgs ai = dss_view_args(nfi, nk, in), ao = dss_view_args(nfo, nk, out);
+  const bool wi = view_wide(p[0].path, in), wo = view_wide(p[1].path, out);
+  return stage_exchange_out(c, "fieldop", nl, c0 == TSE_OP_C0 && c->halo(), (hipStream_t)stream,
+    [&] { launch_sphere_op_stage(c, p[0].path, wi, op, c0 == TSE_OP_C0, ai, (const double*)in->ptr); },
+    [&] { if (c0 == TSE_OP_C0) launch_dss_view_sum(c, p[1].path, wo, ao, (double*)out->ptr); else launch_lap_view_out<1>(c, p[1].path, wo, ao, (double*)out->ptr); });
+}
+
 // ---- introspection ------------------------------------------------------------------------------
 void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   struct Ent { const char* n; void* p; size_t b; };

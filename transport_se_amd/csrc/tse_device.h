@@ -228,6 +228,69 @@ __device__ __forceinline__ void vlaplace_row(const Dvv_t& D, const VecGeo& V, do
   }
 }
 
+// divergence_sphere_row with its fused operations spelled out.  The routine above leaves contraction to the compiler, which decides it per
+// inlined copy: two instantiations of one kernel were seen to fuse Di*v1 + Di*v2 differently.  This is the sequence of k_elem_op<0>
+// (tse_divergence_sphere), read from its machine code -- the product with v2 rounded, the one with v1 fused; d/dx a chain of fused
+// multiply-adds from +0.0 in the order i = 1..np -- so that every copy of it, whatever kernel it is inlined into, has the bits of
+// tse_divergence_sphere (tests/test_gpu_sphere_op_view.py holds it to them).
+__device__ __forceinline__ void divergence_sphere_row_spelled(const Dvv_t& D, const RowGeo& g, const double v1[4], const double v2[4], double div[4]) {
+#pragma clang fp contract(off)
+  double gv1[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) gv1[i] = g.metdet[i] * fma(g.Di11[i], v1[i], g.Di12[i] * v2[i]);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const double gv2 = g.metdet[i] * fma(g.Di21[i], v1[i], g.Di22[i] * v2[i]);
+    const double dx = fma(D.d[i * 4 + 3], gv1[3], fma(D.d[i * 4 + 2], gv1[2], fma(D.d[i * 4 + 1], gv1[1], fma(D.d[i * 4], gv1[0], 0.0))));
+    const double dy = quad_matvec(g.dcol, gv2);
+    div[i] = (dx + dy) * (g.rmetdet[i] * RREARTH);
+  }
+}
+
+// gradient_sphere (derivative_mod.F90:1660-1700) of s at the lane's 4 points, in the reference's operations: rrearth * d/dx,
+// rrearth * d/dy, then Dinv^T.  o1, o2: the lat/lon components.  No implicit contraction, as laplace_lean_row.
+__device__ __forceinline__ void gradient_sphere_row(const Dvv_t& D, const RowGeo& g, const double s[4], double o1[4], double o2[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const double dx = fma(D.d[i * 4 + 3], s[3], fma(D.d[i * 4 + 2], s[2], fma(D.d[i * 4 + 1], s[1], D.d[i * 4] * s[0])));
+    const double dy = quad_matvec(g.dcol, s[i]);
+    const double w1 = RREARTH * dx, w2 = RREARTH * dy;
+    o1[i] = fma(g.Di21[i], w2, g.Di11[i] * w1);
+    o2[i] = fma(g.Di22[i], w2, g.Di12[i] * w1);
+  }
+}
+
+// vorticity_sphere (derivative_mod.F90:2250-2301) of v = (v1, v2) at the lane's 4 points: the covariant components D^T v through the
+// tables Dr = rrearth * D of tse_vector_setup (tables 4..7 of tab[e][VEC_TABS][16]), d/dx of the second minus d/dy of the first, times
+// rmetdet -- vlaplace_row's vorticity without its mp.  No implicit contraction.
+struct VorGeo { double Dr[4][4], rmetdet[4], dcol[4]; };   // Dr[entry a + 2b][i]
+__device__ __forceinline__ void load_vor_geo(VorGeo& V, const double* __restrict__ dvv, const double* __restrict__ tab,
+                                             const double* __restrict__ rmetdet, int e, int j) {
+  const double* t = tab + (size_t)e * VEC_TABS * 16 + 4 * j;
+#pragma unroll
+  for (int k = 0; k < 4; k++) load4(t + (4 + k) * 16, V.Dr[k]);
+  load4(rmetdet + (size_t)e * 16 + 4 * j, V.rmetdet);
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int row = r < 2 ? j : (j ^ 1), m = (r & 1) ? 3 - j : j;   // M(row, m), as in load_row_geo
+    V.dcol[r] = dvv[row * 4 + m];
+  }
+}
+__device__ __forceinline__ void vorticity_row(const Dvv_t& D, const VorGeo& V, const double v1[4], const double v2[4], double vor[4]) {
+#pragma clang fp contract(off)
+  double vc2[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) vc2[i] = fma(V.Dr[3][i], v2[i], V.Dr[2][i] * v1[i]);   // covariant 2 (times rrearth)
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const double vc1 = fma(V.Dr[1][i], v2[i], V.Dr[0][i] * v1[i]);
+    const double dvdx = fma(D.d[i * 4 + 3], vc2[3], fma(D.d[i * 4 + 2], vc2[2], fma(D.d[i * 4 + 1], vc2[1], D.d[i * 4] * vc2[0])));
+    const double dudy = quad_matvec(V.dcol, vc1);
+    vor[i] = V.rmetdet[i] * (dvdx - dudy);
+  }
+}
+
 // limiter_optim_iter_full (prim_advection_mod.F90:976-1094) on one slab spread over a quad.
 // x[i] = ptens/dpmass at the lane's 4 points, c[i] = sphweights*dpmass, sumc = sum(c) over the slab.
 // minp/maxp are relaxed in place (intent(inout) in the reference).  The 16-point sums are tree sums

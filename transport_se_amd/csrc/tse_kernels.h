@@ -3309,4 +3309,89 @@ inline long long vlap_view_groups(long long nk) { return (nk + VLAP_VIEW_LEVELS 
 // blocks of k_vlap_view_out<0 | 2>: 8 XCD ranges of ceil(nelemd / 8) element slots, one quad per VLAP_VIEW_LEVELS levels of an element
 inline long long vlap_view_out_blocks(int nelemd, long long nk) { return dss_view_sum_blocks(nelemd, 4 * vlap_view_groups(nk)); }
 
+// ---- first-order sphere operators of a host's own fields through strided views (tse_sphere_op_view) ---------------------------------
+// OP 0: gradient_sphere of a scalar (1 field -> 2 components), OP 1: divergence_sphere, OP 2: vorticity_sphere of a wind (2 components ->
+// 1 field), on nk levels; LOCAL: out = op(in), C0: out = rspheremp * DSS(spheremp * op(in)), make_C0 / make_C0_vector
+// (viscosity_mod.F90:445-535).  One new kernel:
+//   k_sphere_op_stage<PATH, WIDE, OP, C0>  in -> op -> (C0: one product with spheremp) -> stage[e][f_out * nk + k][16]; lane = row j of a
+//                                          quad, a quad writes one 128-byte line per output layer
+// and then C0: k_dss_view_sum on `out` with nf_out fields (tse_dss_view's sum: C0 has the bits of LOCAL -> tse_dss_view(AVERAGE)),
+// LOCAL: k_lap_view_out<PATH, WIDE, 1>, the own-line copy.  PATH and WIDE are those of `in`, as in k_lap_view_stage / k_vlap_view_stage:
+//   PATH 0, 2  a quad keeps its geometry over SPHERE_OP_LEVELS consecutive levels of its element
+//   PATH 1     block = element; every input field passes through an LDS image of its own, quad q takes the levels q, q + 64, ...
+// Whole quads stay active; only the stores are predicated.  a: the args of `in` (a.nf = 1 for OP 0, 2 otherwise).
+#ifndef TSE_SPHERE_OP_LEVELS
+#define TSE_SPHERE_OP_LEVELS 4   // (profiles/sphere_op_rate.txt holds the comparison)
+#endif
+constexpr int SPHERE_OP_LEVELS = TSE_SPHERE_OP_LEVELS;
+struct SphereOpGeo { RowGeo g; VorGeo V; double sm[4]; };   // what an instantiation does not use is never loaded
+template <int OP, bool C0>
+__device__ __forceinline__ void load_sphere_op_geo(SphereOpGeo& S, const GeoPtrs& G, const double* __restrict__ vtab, int e, int j) {
+  if (OP == 2) load_vor_geo(S.V, G.dvv, vtab, G.rmetdet, e, j);
+  else load_row_geo(S.g, G.dvv, G.Dinv, G.metdet, G.rmetdet, G.spheremp, e, j);
+  if (C0) load4(G.spheremp + (size_t)e * 16 + 4 * j, S.sm);
+}
+// x1 (, x2): the lane's row of the input field(s); r1 (, r2): of the output field(s)
+template <int OP, bool C0>
+__device__ __forceinline__ void sphere_op_row(const Dvv_t& D, const SphereOpGeo& S, const double x1[4], const double x2[4], double r1[4], double r2[4]) {
+#pragma clang fp contract(off)
+  if (OP == 0) gradient_sphere_row(D, S.g, x1, r1, r2);
+  else if (OP == 1) divergence_sphere_row_spelled(D, S.g, x1, x2, r1);
+  else vorticity_row(D, S.V, x1, x2, r1);
+  if (C0) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { r1[i] = S.sm[i] * r1[i]; if (OP == 0) r2[i] = S.sm[i] * r2[i]; }
+  }
+}
+
+template <int PATH, bool WIDE, int OP, bool C0>
+__global__ __launch_bounds__(VIEW_THREADS) void k_sphere_op_stage(int nelemd, DssViewArgs a, Dvv_t D, GeoPtrs G, const double* __restrict__ vtab,
+                                                                  const double* __restrict__ view, double* __restrict__ stage) {
+#pragma clang fp contract(off)
+  constexpr int NIN = OP == 0 ? 1 : 2, NOUT = OP == 0 ? 2 : 1;
+  const int nk = a.nk, nl = NOUT * nk, tid = threadIdx.x, j = tid & 3;
+  SphereOpGeo S;
+  if (PATH == 1) {
+    __shared__ __attribute__((aligned(16))) double tile[NIN][16 * VIEW_PITCH];
+    constexpr int K = NLEV;
+    const int e = (int)blockIdx.x;   // (the grid is nelemd blocks)
+    load_sphere_op_geo<OP, C0>(S, G, vtab, e, j);
+#pragma unroll
+    for (int c = 0; c < NIN; c++) dss_rows_to_tile<WIDE, K>(view + (long long)e * a.vs[0] + c * a.vs[1], a.vs[4], tile[c], tid);
+    __syncthreads();
+    double* L = stage + (size_t)e * nl * 16 + 4 * j;
+    for (int k = tid >> 2; k < K; k += VIEW_THREADS / 4) {
+      double x1[4], x2[4], r1[4], r2[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) { x1[i] = tile[0][(4 * j + i) * VIEW_PITCH + k]; x2[i] = tile[NIN - 1][(4 * j + i) * VIEW_PITCH + k]; }
+      sphere_op_row<OP, C0>(D, S, x1, x2, r1, r2);
+      store4(L + (size_t)k * 16, r1);
+      if (NOUT == 2) store4(L + (size_t)(K + k) * 16, r2);
+    }
+  } else {
+    const int groups = (nk + SPHERE_OP_LEVELS - 1) / SPHERE_OP_LEVELS;
+    const size_t qd = ((size_t)blockIdx.x * VIEW_THREADS + tid) >> 2;
+    const size_t eraw = qd / (unsigned)groups;
+    const int grp = (int)(qd - eraw * (unsigned)groups);
+    const bool live = eraw < (size_t)nelemd;
+    const int e = live ? (int)eraw : nelemd - 1;
+    load_sphere_op_geo<OP, C0>(S, G, vtab, e, j);
+    const int k0 = grp * SPHERE_OP_LEVELS;
+#pragma unroll
+    for (int u = 0; u < SPHERE_OP_LEVELS; u++) {
+      const int k = min(k0 + u, nk - 1);
+      double x1[4], x2[4], r1[4], r2[4];
+      const double* P = view + (long long)e * a.vs[0] + k * a.vs[2];
+      lap_view_load_row<PATH, WIDE>(P, a, j, x1);
+      if (NIN == 2) lap_view_load_row<PATH, WIDE>(P + a.vs[1], a, j, x2);
+      sphere_op_row<OP, C0>(D, S, x1, x2, r1, r2);
+      if (live && k0 + u < nk) {
+        store4(stage + ((size_t)e * nl + k) * 16 + 4 * j, r1);
+        if (NOUT == 2) store4(stage + ((size_t)e * nl + nk + k) * 16 + 4 * j, r2);
+      }
+    }
+  }
+}
+inline long long sphere_op_groups(long long nk) { return (nk + SPHERE_OP_LEVELS - 1) / SPHERE_OP_LEVELS; }
+
 }  // namespace tse

@@ -202,6 +202,36 @@ int vlaplace_view_plan(int nelemd, int nk, const tse_view* in, const tse_view* o
   return biharmonic_view_plan(nelemd, 2, nk, in, out_view, out, err, "tse_vlaplace_view");
 }
 
+// tse_sphere_op_view's two views: each a view of tse_dss_view, `in` with nf_in fields and `out` with nf_out.
+bool sphere_op_fields(int op, int* nf_in, int* nf_out) {
+  if (op < TSE_OP_GRADIENT || op > TSE_OP_VORTICITY) return false;
+  *nf_in = op == TSE_OP_GRADIENT ? 1 : 2;
+  *nf_out = op == TSE_OP_GRADIENT ? 2 : 1;
+  return true;
+}
+
+int sphere_op_view_plan(int nelemd, int nk, int op, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err) {
+  const char* who = "tse_sphere_op_view";
+  int nf[2];
+  if (!sphere_op_fields(op, &nf[0], &nf[1])) return refuse(err, "%s: op=%d (0: gradient_sphere, 1: divergence_sphere, 2: vorticity_sphere)", who, op);
+  if (!in || !out_view || !out) return refuse(err, "%s: null view", who);
+  const tse_view* v[2] = {in, out_view};
+  for (int i = 0; i < 2; i++) {
+    std::string e;
+    if (dss_view_plan(nelemd, nf[i], nk, v[i], &out[i], &e, who)) return refuse(err, "%s (%s)", e.c_str(), i == 0 ? "in" : "out");
+  }
+  return 0;
+}
+
+int sphere_op_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err) {
+  const __int128 f0 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].lo * 8, f1 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].hi * 8;
+  const __int128 g0 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].lo * 8, g1 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].hi * 8;
+  if (f0 < g1 && g0 < f1)
+    return refuse(err, "tse_sphere_op_view: out [%p%+lld, %p%+lld doubles) overlaps in [%p%+lld, %p%+lld doubles): the shapes differ, there is no in-place form",
+                  out->ptr, plan[1].lo, out->ptr, plan[1].hi, in->ptr, plan[0].lo, in->ptr, plan[0].hi);
+  return 0;
+}
+
 }  // namespace tse
 
 // the C plan entries: an error becomes the message of tse_last_error; n plans go out as path[] / lo[] / hi[], each of them optional
@@ -254,6 +284,15 @@ extern "C" int tse_vlaplace_view_plan(int nelemd, int nk, const tse_view* in, co
   if (tse::vlaplace_view_plan(nelemd, nk, in, out, p, &err)) return refused(err);
   // strides alone (both ptr null): nothing is known of where the views lie
   if ((in->ptr || out->ptr) && tse::biharmonic_view_overlap(in, out, p, &err, "tse_vlaplace_view")) return refused(err);
+  return plans_out(p, 2, path, lo, hi);
+}
+
+extern "C" int tse_sphere_op_view_plan(int nelemd, int nk, int op, const tse_view* in, const tse_view* out, int path[2], long long lo[2], long long hi[2]) {
+  tse::ViewPlan p[2];
+  std::string err;
+  if (tse::sphere_op_view_plan(nelemd, nk, op, in, out, p, &err)) return refused(err);
+  // strides alone (both ptr null): nothing is known of where the views lie
+  if ((in->ptr || out->ptr) && tse::sphere_op_view_overlap(in, out, p, &err)) return refused(err);
   return plans_out(p, 2, path, lo, hi);
 }
 

@@ -54,6 +54,13 @@ int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewP
 // The two views of tse_vlaplace_view / tse_vlaplace_view_plan: those of tse_biharmonic_view with nf = 2 (the q axis is the wind component).
 int vlaplace_view_plan(int nelemd, int nk, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err);
 
+// The two views of tse_sphere_op_view / tse_sphere_op_view_plan: each a view of tse_dss_view with its own field count, (nf_in, nf_out) =
+// (1, 2) for TSE_OP_GRADIENT and (2, 1) for TSE_OP_DIVERGENCE and TSE_OP_VORTICITY (sphere_op_fields; false: no such op).  The shapes
+// differ, so there is no in-place form: sphere_op_view_overlap asks for disjoint footprints (touching is disjoint).
+bool sphere_op_fields(int op, int* nf_in, int* nf_out);
+int sphere_op_view_plan(int nelemd, int nk, int op, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err);
+int sphere_op_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err);
+
 // the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
 int set_last_error(const char* msg);
 

@@ -64,6 +64,10 @@ module cuda_mod
   ! weak vector Laplacian / biharmonic of the host's own device-resident wind (tse_vector_setup, tse_vlaplace_view)
   public :: vector_setup_hip, vlaplace_view_hip
   integer, parameter, public :: vlap_order1 = 1, vlap_order2 = 2   ! TSE_VLAPLACE, TSE_VBIHARMONIC
+  ! gradient, divergence and vorticity of the host's own device-resident fields, element-local or C0 (tse_sphere_op_view)
+  public :: sphere_op_view_hip
+  integer, parameter, public :: op_gradient = 0, op_divergence = 1, op_vorticity = 2   ! TSE_OP_GRADIENT, TSE_OP_DIVERGENCE, TSE_OP_VORTICITY
+  integer, parameter, public :: op_local = 0, op_c0 = 1                                ! TSE_OP_LOCAL, TSE_OP_C0
   logical, save :: remap_refused = .false.            ! remap_view_hip / remap_view_status_hip: the master thread's answer, read by every thread
   integer(c_int), save :: remap_nrefused = 0, remap_where(4) = 0
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
@@ -222,6 +226,10 @@ module cuda_mod
      end function
      integer(c_int) function tse_vlaplace_view(ctx, nk, order, nu_ratio, vin, vout, stream) bind(C, name='tse_vlaplace_view')
        import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nk, order; real(c_double), value :: nu_ratio
+       type(tse_view), intent(in) :: vin, vout
+     end function
+     integer(c_int) function tse_sphere_op_view(ctx, nk, op, c0, vin, vout, stream) bind(C, name='tse_sphere_op_view')
+       import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nk, op, c0
        type(tse_view), intent(in) :: vin, vout
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
@@ -959,5 +967,28 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine vlaplace_view_hip
+
+  ! out at out_ptr <- op of nk levels of the host's DEVICE array at ptr (include/transport_se_hip.h: tse_sphere_op_view):
+  !   op_gradient    s(:,:,1:nk)     -> out(:,:,1:2,1:nk)   gradient_sphere
+  !   op_divergence  v(:,:,1:2,1:nk) -> out(:,:,1:nk)       divergence_sphere
+  !   op_vorticity   v(:,:,1:2,1:nk) -> out(:,:,1:nk)       vorticity_sphere (needs vector_setup_hip)
+  ! c0 = op_local: on every element by itself, no exchange.  c0 = op_c0: rspheremp * DSS(spheremp * op(...)), the make_C0 of
+  ! viscosity_mod (compute_zeta_C0, compute_div_C0); COLLECTIVE: every rank calls with the same nk and op.
+  ! strides(1:5) and out_strides(1:5) in doubles for element, component, level, j, i: state%v(np,np,2,nlev,tl) is (/ s_e, 16, 32, 4, 1 /)
+  ! with one call per time level; the component stride of the scalar side is free (0).  The two arrays may not overlap: there is no
+  ! in-place form.  stream as in view_put_hip.  A refusal aborts.
+  subroutine sphere_op_view_hip(nk, op, c0, ptr, strides, out_ptr, out_strides, stream)
+    integer,              intent(in) :: nk, op, c0
+    type(c_ptr),          intent(in) :: ptr, out_ptr, stream
+    integer(c_long_long), intent(in) :: strides(5), out_strides(5)
+    type(tse_view) :: vi, vo
+    vi%ptr = ptr; vi%stride = strides
+    vo%ptr = out_ptr; vo%stride = out_strides
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_sphere_op_view(ctx, int(nk,c_int), int(op,c_int), int(c0,c_int), vi, vo, stream), 'sphere_op_view_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine sphere_op_view_hip
 
 end module cuda_mod

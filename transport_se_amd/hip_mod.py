@@ -276,6 +276,34 @@ def vlaplace_view_plan(nelemd, nk, field, out=None, nlev=None):
     return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
 
 
+SPHERE_OPS = {"gradient": 0, "divergence": 1, "vorticity": 2}   # TSE_OP_GRADIENT, TSE_OP_DIVERGENCE, TSE_OP_VORTICITY
+SPHERE_OP_FIELDS = {0: (1, 2), 1: (2, 1), 2: (2, 1)}            # op -> (fields of in, fields of out)
+
+
+def _sphere_op(op):
+    """the operator names, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(op, str):
+        if op not in SPHERE_OPS:
+            raise TseError("sphere_op_view: unknown op %r (the operators are %s)" % (op, ", ".join(SPHERE_OPS)))
+        return SPHERE_OPS[op]
+    return int(op)
+
+
+def sphere_op_view_plan(nelemd, nk, op, field, out, nlev=None):
+    """tse_sphere_op_view_plan: [dict(path=, lo=, hi=)] of the two views of HipMod.sphere_op_view, in and out, given as for
+    biharmonic_view_plan (there is no in-place form: out is needed).  Needs no device.  Raises TseError for views sphere_op_view would
+    refuse."""
+    L = _lib.lib(nlev=nlev)
+    raw = lambda x: _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
+    vi = None if field is None else raw(field)
+    vo = None if out is None else raw(out)
+    path, lo, hi = (C.c_int * 2)(), (C.c_longlong * 2)(), (C.c_longlong * 2)()
+    if L.tse_sphere_op_view_plan(int(nelemd), int(nk), _sphere_op(op), None if vi is None else C.byref(vi), None if vo is None else C.byref(vo),
+                                 C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -718,6 +746,38 @@ class HipMod:
         also be ready _lib.Views (then nk is needed)."""
         vi, vo, _, nk = self._view_pair("vlaplace_view", field, axes, out, out_axes, 2, nk, wind=True)
         self._chk(self.L.tse_vlaplace_view(self.h, int(nk), _vlap_order(order), float(nu_ratio), C.byref(vi), C.byref(vo), _stream_handle(stream)))
+
+    # ---- gradient, divergence, vorticity of the host's own fields, element-local or C0 (tse_sphere_op_view) ----
+    def sphere_op_view(self, field, axes, out, out_axes=None, op="vorticity", c0=False, stream=None, nk=None):
+        """out <- op(field) (c0=False: element-local, no exchange) or rspheremp * DSS(spheremp * op(field)) (c0=True: make_C0, the
+        continuous field; COLLECTIVE on a context with neighbour ranks, as dss_view) on nk levels of the device array `field`; nk is the
+        array's extent along the letter k of `axes` (a missing k: 1).  op "gradient": field is a scalar (the letter q absent or of
+        extent 1), out has the letter q with extent 2, the lat/lon components; "divergence" and "vorticity": field has q with extent 2,
+        out is a scalar.  out is another device array of the same nk whose axes `out_axes` names (default: `axes`), disjoint from
+        `field`.  c0=True has the bits of c0=False followed by dss_view(out, mode="average").  "vorticity" needs vector_setup.  stream
+        orders as in put.  `field` and `out` may also be ready _lib.Views (then nk is needed)."""
+        who = "sphere_op_view"
+        o = _sphere_op(op)
+        nfi, nfo = SPHERE_OP_FIELDS.get(o, (None, None))
+        side = lambda n, want: ("the q axis is the component and has extent %d, not 2" if want == 2 else
+                                "a scalar field has a q axis of extent %d (the letter q is absent or has extent 1)") % n
+        if isinstance(field, _lib.View):
+            if nk is None:
+                raise TseError("%s: nk is needed with a ready view" % who)
+            vi = field
+        else:
+            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=False)
+            if nfi is not None and nf != nfi:
+                raise TseError("%s: field: %s" % (who, side(nf, nfi)))
+        if isinstance(out, _lib.View):
+            vo = out
+        else:
+            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
+            if onk != nk:
+                raise TseError("%s: out has %d levels, field has %d" % (who, onk, nk))
+            if nfo is not None and onf != nfo:
+                raise TseError("%s: out: %s" % (who, side(onf, nfo)))
+        self._chk(self.L.tse_sphere_op_view(self.h, int(nk), o, int(c0), C.byref(vi), C.byref(vo), _stream_handle(stream)))
 
     def last_error(self):
         return self.L.tse_last_error().decode()
