@@ -240,6 +240,31 @@ def read_ops(path):
     return ops, remaps
 
 
+# the per-element records of dump_fieldops after gid and metinv, in file order: name -> fields (1 a scalar, 2 a vector)
+FIELDOPS_RECORDS = (("s", 1), ("v", 2), ("dss_average", 1), ("dss_weak", 1),
+                    ("grad", 2), ("grad_cont", 2), ("div", 1), ("vor", 1),
+                    ("div_c0", 1), ("vor_c0", 1), ("grad_c0", 2), ("grad_cont_c0", 2), ("zeta_c0", 1), ("divergence_c0", 1),
+                    ("lap", 1), ("bih", 1), ("bih_direct", 1),
+                    ("vlap_nu0", 2), ("vlap_nu1", 2), ("vbih_nu0", 2), ("vbih_nu1", 2))
+
+
+def read_fieldops(path):
+    """fieldops_<step>_r<rank>.bin of ref_harness's dump_fieldops -> dict: gid[n], metinv[n][4 j][4 i][2 b][2 a] (as read_static's D),
+    nu_ratio[2], direct (whether bih_direct is biharmonic_wk_scalar's own output), and every field as the view models hold one:
+    [n][nf][nk][4 j][4 i] (Fortran's s(i,j,k) and v(i,j,c,k))"""
+    r = _Rd(path)
+    nelemd, nk, direct, nnu = [int(x) for x in r.i4(4)]
+    d = dict(nk=nk, direct=bool(direct), nu_ratio=r.f8(nnu))
+    acc = {k: [] for k in ("gid", "metinv") + tuple(n for n, _ in FIELDOPS_RECORDS)}
+    for _ in range(nelemd):
+        acc["gid"].append(r.i4(1)[0]); acc["metinv"].append(r.f8(4, 4, 2, 2))
+        for name, nf in FIELDOPS_RECORDS:
+            acc[name].append(r.f8(nk, 4, 4)[None] if nf == 1 else r.f8(nk, 2, 4, 4).transpose(1, 0, 2, 3))
+    assert r.done()
+    d.update({k: np.ascontiguousarray(np.array(v)) for k, v in acc.items()})
+    return d
+
+
 def read_state(path):
     r = _Rd(path)
     istep, nq, nelemd, qsize = [int(x) for x in r.i4(4)]

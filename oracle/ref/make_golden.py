@@ -9,6 +9,7 @@ Only data is written (inputs and expected outputs); no reference source travels.
     python oracle/ref/make_golden.py --long     # + ne8 12-day DCMIP 1-1 / 1-day 1-2 norms (minutes, 6 ranks)
     python oracle/ref/make_golden.py --sfc      # only the space-filling-curve partition fixture (ref_sfc_partition.npz)
     python oracle/ref/make_golden.py --alg2     # only the vert_remap_q_alg=2 fixture (ref_ne2_alg2.npz)
+    python oracle/ref/make_golden.py --fieldops # only the field-operator fixture (ref_ne2_fieldops.npz)
 """
 import argparse
 import json
@@ -110,6 +111,52 @@ def gather_state_with_gid(outdir, tag, nranks, statics):
     return out
 
 
+def gather_fieldops(outdir, nranks):
+    """the ranks' fieldops dumps in the order of GlobalId"""
+    parts = [po.read_fieldops(os.path.join(outdir, "fieldops_000000_r%04d.bin" % r)) for r in range(nranks)]
+    gid = np.concatenate([p["gid"] for p in parts]) - 1
+    assert np.array_equal(np.sort(gid), np.arange(gid.size))
+    out = dict(nk=parts[0]["nk"], direct=parts[0]["direct"], nu_ratio=parts[0]["nu_ratio"])
+    for k, v in parts[0].items():
+        if isinstance(v, np.ndarray) and k != "nu_ratio":
+            cat = np.concatenate([p[k] for p in parts])
+            full = np.empty_like(cat)
+            full[gid] = cat
+            out[k] = full
+    return out
+
+
+def make_fieldops():
+    """ref_ne2_fieldops.npz: the reference's own field operators (derivative_mod, viscosity_mod) on every element of ne2 and fo_nk levels
+    of fieldops_fill's inputs -- ref_harness's dump_fieldops on one rank, and the flag that two ranks give the same bits."""
+    cfg = dict(ne=2, qsize=1, nsteps=0, tstep=1800.0, nu_q=1e19, test=1)
+    env = {"TSE_DUMP_FIELDOPS": "1"}
+    outdir, _ = run(dumpfreq=0, env=env, **cfg)
+    one = gather_fieldops(outdir, 1)
+    st = po.read_static(os.path.join(outdir, "static_000000_r0000.bin"))
+    gold_st = np.load(os.path.join(GOLD, "ref_ne2_static.npz"))
+    for k in ("gid", "lat", "lon", "D", "Dinv", "spheremp", "rspheremp", "mp"):
+        assert np.array_equal(st[k], gold_st[k]), "this run's mesh is not ref_ne2_static.npz's: " + k
+    assert np.array_equal(one["gid"], st["gid"])      # one rank: the local order is the global one
+    assert one["direct"], "biharmonic_wk_scalar did not run (qsize /= 1)"
+    same = bool(np.array_equal(one["bih_direct"], one["bih"]))
+    print("biharmonic_wk_scalar on the full column == lap, pack/exchange/unpack, * rspheremp, lap on its first %d levels, bit for bit: %s"
+          % (one["nk"], same))
+    assert same
+    outdir2, _ = run(dumpfreq=0, nranks=2, env=env, **cfg)
+    two = gather_fieldops(outdir2, 2)
+    fields = [k for k, v in one.items() if isinstance(v, np.ndarray)]
+    differ = [k for k in fields if not np.array_equal(one[k].view(np.uint64) if one[k].dtype == np.float64 else one[k],
+                                                      two[k].view(np.uint64) if two[k].dtype == np.float64 else two[k])]
+    bfb = not differ
+    print("reference field operators 1 rank vs 2 ranks bit-for-bit:", bfb, differ)
+    assert bfb, differ
+    keep = {k: one[k] for k in fields if k != "bih_direct"}
+    path = os.path.join(GOLD, "ref_ne2_fieldops.npz")
+    np.savez_compressed(path, config=json.dumps(dict(cfg, nk=int(one["nk"]))), bfb_1v2=bfb, **keep)
+    print("%s: %d bytes" % (path, os.path.getsize(path)))
+
+
 def make_long(nranks=6):
     """ne8 DCMIP 1-1 (12 d) and 1-2 (1 d) as test/run_ne8_tests.sh runs them: norms + mass of the reference."""
     res = {}
@@ -160,9 +207,13 @@ if __name__ == "__main__":
     ap.add_argument("--long", action="store_true")
     ap.add_argument("--only-long", action="store_true")
     ap.add_argument("--alg2", action="store_true", help="only the vert_remap_q_alg=2 fixture (ref_ne2_alg2.npz)")
+    ap.add_argument("--fieldops", action="store_true", help="only the field-operator fixture (ref_ne2_fieldops.npz)")
     a = ap.parse_args()
     if not os.path.exists(HARNESS):
         subprocess.check_call(["make", "-C", HERE])
+    if a.fieldops:
+        make_fieldops()
+        sys.exit(0)
     if a.sfc:
         make_sfc()
         sys.exit(0)

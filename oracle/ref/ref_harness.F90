@@ -41,7 +41,11 @@ program ref_harness
   use hybvcoord_mod,      only : hvcoord_t, hvcoord_init
   use time_mod,           only : timelevel_t, timelevel_init, timelevel_update, timelevel_qdp, tstep
   use derivative_mod,     only : derivative_t, divergence_sphere, gradient_sphere, laplace_sphere_wk, &
-                                 divergence_sphere_wk
+                                 divergence_sphere_wk, vorticity_sphere, vlaplace_sphere_wk
+  use viscosity_mod,      only : make_C0, make_C0_vector, compute_zeta_C0, compute_div_C0, biharmonic_wk_scalar
+  use edge_mod,           only : EdgeBuffer_t, initEdgeBuffer, FreeEdgeBuffer, edgeVpack, edgeVunpack
+  use bndry_mod,          only : bndry_exchangeV
+  use fieldops_fill,      only : fo_nk, fo_fill
   use filter_mod,         only : filter_t
   use prim_advection_mod, only : prim_advec_init1, prim_advec_init2, prim_advec_tracers_remap, &
                                  vertical_remap, deriv
@@ -75,7 +79,7 @@ program ref_harness
   logical :: rs_ddpdd, rs_recompute
   real(kind=real_kind) :: rs_rel
   integer :: ne_in, qsize_in, nsteps, tcase, dumpfreq, nelem_edge
-  integer :: ie, j, r, ierr, n0_qdp, np1_qdp, istep, isub, nsub
+  integer :: ie, j, r, ierr, n0_qdp, np1_qdp, istep, isub, nsub, want_fieldops
   integer :: nthr_h, ithr_h, nets_h, nete_h, n0q_h, np1q_h      ! TSE_HARNESS_THREADS: the time loop inside !$OMP PARALLEL, as prim_main.F90:143-162
   type (hybrid_t) :: hybrid_h
   integer(kind=8) :: c0, c1, crate
@@ -204,6 +208,9 @@ program ref_harness
   if (dumpfreq >= 0) then
      call dump_static()
      call dump_ops()
+     want_fieldops = 0
+     call env_int('TSE_DUMP_FIELDOPS', want_fieldops)      ! make_golden.py --fieldops
+     if (want_fieldops /= 0) call dump_fieldops()
      call TimeLevel_Qdp(tl, qsplit, n0_qdp, np1_qdp)
      call dump_state(0, n0_qdp, tl%n0)
   endif
@@ -537,6 +544,137 @@ contains
     enddo
     close(31)
   end subroutine dump_ops
+
+  ! rspheremp-free node sum of nl layers, as viscosity_mod writes it: edgeVpack, bndry_exchangeV, edgeVunpack
+  subroutine dss_layers(x, nl)
+    integer, intent(in) :: nl
+    real(kind=real_kind), intent(inout) :: x(np,np,nl,nelemd)
+    type (EdgeBuffer_t) :: edge
+    integer :: ie
+    call initEdgeBuffer(par, edge, nl)
+    do ie = 1, nelemd
+       call edgeVpack(edge, x(:,:,:,ie), nl, 0, elem(ie)%desc)
+    enddo
+    call bndry_exchangeV(hybrid, edge)
+    do ie = 1, nelemd
+       call edgeVunpack(edge, x(:,:,:,ie), nl, 0, elem(ie)%desc)
+    enddo
+    call FreeEdgeBuffer(edge)
+  end subroutine dss_layers
+
+  ! single-call goldens of the field operators a resident host's views are given to (derivative_mod, viscosity_mod) on every element and
+  ! fo_nk levels of fieldops_fill's inputs: fieldops_<step>_r<rank>.bin.  Every rank writes its own elements; the fill depends on the
+  ! global element number alone.  Every result is the reference's own routine on elem(:), deriv(0); the two order-2 chains are composed
+  ! here as biharmonic_wk_scalar and biharmonic_wk_dp3d compose them (lap, pack/exchange/unpack, * rspheremp, lap), and
+  ! biharmonic_wk_scalar itself runs once on the full column where qsize = 1.
+  subroutine dump_fieldops()
+    integer, parameter :: nk = fo_nk
+    real(kind=real_kind), parameter :: nur(2) = (/ 1.0d0, 2.5d0 /)
+    real(kind=real_kind), allocatable :: s(:,:,:,:), sc(:,:,:,:), dw(:,:,:,:), dv(:,:,:,:), vo(:,:,:,:), dvc(:,:,:,:), voc(:,:,:,:), &
+         zc(:,:,:,:), dc(:,:,:,:), lp(:,:,:,:), bh(:,:,:,:), bd(:,:,:,:), z72(:,:,:,:)
+    real(kind=real_kind), allocatable :: v(:,:,:,:,:), gs(:,:,:,:,:), gc(:,:,:,:,:), gsc(:,:,:,:,:), gcc(:,:,:,:,:), v72(:,:,:,:,:), &
+         vsave(:,:,:,:,:), qt(:,:,:,:,:), w(:,:,:,:,:)
+    real(kind=real_kind), allocatable :: vl(:,:,:,:,:,:), vb(:,:,:,:,:,:)
+    real(kind=real_kind) :: tmp(np,np), tv(np,np,2), nu_ratio
+    type (EdgeBuffer_t) :: edgeq
+    integer :: ie, k, c, r, nt, direct
+    allocate(s(np,np,nk,nelemd), sc(np,np,nk,nelemd), dw(np,np,nk,nelemd), dv(np,np,nk,nelemd), vo(np,np,nk,nelemd))
+    allocate(dvc(np,np,nk,nelemd), voc(np,np,nk,nelemd), zc(np,np,nk,nelemd), dc(np,np,nk,nelemd))
+    allocate(lp(np,np,nk,nelemd), bh(np,np,nk,nelemd), bd(np,np,nk,nelemd), z72(np,np,nlev,nelemd))
+    allocate(v(np,np,2,nk,nelemd), gs(np,np,2,nk,nelemd), gc(np,np,2,nk,nelemd), gsc(np,np,2,nk,nelemd), gcc(np,np,2,nk,nelemd))
+    allocate(v72(np,np,2,nlev,nelemd), vsave(np,np,2,nlev,nelemd), qt(np,np,nlev,1,nelemd), w(np,np,2,nk,nelemd))
+    allocate(vl(np,np,2,nk,nelemd,2), vb(np,np,2,nk,nelemd,2))
+    do ie = 1, nelemd
+       call fo_fill(elem(ie)%GlobalId, np, nk, s(:,:,:,ie), v(:,:,:,:,ie))
+    enddo
+    ! the DSS idiom: rspheremp * DSS(spheremp * s) -- a field that is continuous -- and rspheremp * DSS(s)
+    do ie = 1, nelemd; do k = 1, nk
+       sc(:,:,k,ie) = s(:,:,k,ie)*elem(ie)%spheremp(:,:)
+    enddo; enddo
+    call dss_layers(sc, nk)
+    dw = s
+    call dss_layers(dw, nk)
+    do ie = 1, nelemd; do k = 1, nk
+       sc(:,:,k,ie) = sc(:,:,k,ie)*elem(ie)%rspheremp(:,:)
+       dw(:,:,k,ie) = dw(:,:,k,ie)*elem(ie)%rspheremp(:,:)
+    enddo; enddo
+    ! element-local operators
+    do ie = 1, nelemd; do k = 1, nk
+       gs(:,:,:,k,ie) = gradient_sphere(s(:,:,k,ie), deriv(0), elem(ie)%Dinv)
+       gc(:,:,:,k,ie) = gradient_sphere(sc(:,:,k,ie), deriv(0), elem(ie)%Dinv)
+       dv(:,:,k,ie)   = divergence_sphere(v(:,:,:,k,ie), deriv(0), elem(ie))
+       vo(:,:,k,ie)   = vorticity_sphere(v(:,:,:,k,ie), deriv(0), elem(ie))
+    enddo; enddo
+    ! make_C0 / make_C0_vector work on nlev levels: the fixture's are the first nk, the others 0
+    z72 = 0; z72(:,:,1:nk,:) = dv
+    call make_C0(z72, elem, hybrid, 1, nelemd);  dvc = z72(:,:,1:nk,:)
+    z72 = 0; z72(:,:,1:nk,:) = vo
+    call make_C0(z72, elem, hybrid, 1, nelemd);  voc = z72(:,:,1:nk,:)
+    v72 = 0; v72(:,:,:,1:nk,:) = gs
+    call make_C0_vector(v72, elem, hybrid, 1, nelemd);  gsc = v72(:,:,:,1:nk,:)
+    v72 = 0; v72(:,:,:,1:nk,:) = gc
+    call make_C0_vector(v72, elem, hybrid, 1, nelemd);  gcc = v72(:,:,:,1:nk,:)
+    ! compute_zeta_C0 / compute_div_C0 read state%v(:,:,:,:,nt): the wind goes there and what was there comes back
+    nt = tl%np1
+    do ie = 1, nelemd
+       vsave(:,:,:,:,ie) = elem(ie)%state%v(:,:,:,:,nt)
+       elem(ie)%state%v(:,:,:,:,nt) = 0
+       elem(ie)%state%v(:,:,:,1:nk,nt) = v(:,:,:,:,ie)
+    enddo
+    call compute_zeta_C0(z72, elem, hybrid, 1, nelemd, nt);  zc = z72(:,:,1:nk,:)
+    call compute_div_C0(z72, elem, hybrid, 1, nelemd, nt);   dc = z72(:,:,1:nk,:)
+    do ie = 1, nelemd
+       elem(ie)%state%v(:,:,:,:,nt) = vsave(:,:,:,:,ie)
+    enddo
+    ! weak scalar Laplacian and its order 2
+    do ie = 1, nelemd; do k = 1, nk
+       lp(:,:,k,ie) = laplace_sphere_wk(s(:,:,k,ie), deriv(0), elem(ie), .false.)
+    enddo; enddo
+    bh = lp
+    call dss_layers(bh, nk)
+    do ie = 1, nelemd; do k = 1, nk
+       tmp(:,:) = elem(ie)%rspheremp(:,:)*bh(:,:,k,ie)
+       bh(:,:,k,ie) = laplace_sphere_wk(tmp, deriv(0), elem(ie), .false.)
+    enddo; enddo
+    direct = 0
+    bd = 0
+    if (qsize == 1) then
+       direct = 1
+       qt = 0; qt(:,:,1:nk,1,:) = s
+       call initEdgeBuffer(par, edgeq, nlev)
+       call biharmonic_wk_scalar(elem, qt, deriv(0), edgeq, hybrid, 1, nelemd)
+       call FreeEdgeBuffer(edgeq)
+       bd = qt(:,:,1:nk,1,:)
+    endif
+    ! weak vector Laplacian and its order 2 (the state%v line of biharmonic_wk_dp3d), nu_ratio in both Laplacians
+    do r = 1, 2
+       nu_ratio = nur(r)
+       do ie = 1, nelemd; do k = 1, nk
+          vl(:,:,:,k,ie,r) = vlaplace_sphere_wk(v(:,:,:,k,ie), deriv(0), elem(ie), .false., nu_ratio)
+       enddo; enddo
+       w = vl(:,:,:,:,:,r)
+       call dss_layers(w, 2*nk)
+       do ie = 1, nelemd; do k = 1, nk
+          do c = 1, 2
+             tv(:,:,c) = elem(ie)%rspheremp(:,:)*w(:,:,c,k,ie)
+          enddo
+          vb(:,:,:,k,ie,r) = vlaplace_sphere_wk(tv, deriv(0), elem(ie), .false., nu_ratio)
+       enddo; enddo
+    enddo
+    call open_out('fieldops', 0)
+    write(31) int(nelemd,4), int(nk,4), int(direct,4), int(2,4)
+    write(31) nur
+    do ie = 1, nelemd
+       write(31) int(elem(ie)%GlobalId,4)
+       write(31) elem(ie)%metinv
+       write(31) s(:,:,:,ie), v(:,:,:,:,ie), sc(:,:,:,ie), dw(:,:,:,ie)
+       write(31) gs(:,:,:,:,ie), gc(:,:,:,:,ie), dv(:,:,:,ie), vo(:,:,:,ie)
+       write(31) dvc(:,:,:,ie), voc(:,:,:,ie), gsc(:,:,:,:,ie), gcc(:,:,:,:,ie), zc(:,:,:,ie), dc(:,:,:,ie)
+       write(31) lp(:,:,:,ie), bh(:,:,:,ie), bd(:,:,:,ie)
+       write(31) vl(:,:,:,:,ie,1), vl(:,:,:,:,ie,2), vb(:,:,:,:,ie,1), vb(:,:,:,:,ie,2)
+    enddo
+    close(31)
+  end subroutine dump_fieldops
 
   function lcg(seed) result(x)
     integer(kind=8), intent(inout) :: seed

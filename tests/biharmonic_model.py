@@ -24,6 +24,7 @@ LD = np.longdouble
 N_LAP, N_BIH = ld.N_LAP, ld.N_LAP + 3 + 1 + ld.N_LAP
 ORDERS = (1, 2)
 PLANTS = ("dropped", "average", "no_rspheremp", "unsummed")
+TRANSPOSITIONS = ("D_transposed", "ij_transposed")     # errors of index convention, in every Laplacian of either order
 assert N_BIH == 42
 
 
@@ -31,10 +32,25 @@ def steps(order):
     return {1: N_LAP, 2: N_BIH}[order]
 
 
-def _lap(o, x):
-    """x[n][L][4][4] longdouble -> (lap, A) of every layer"""
+class _DinvTransposed:
+    """the mesh with Dinv(a,b) read as Dinv(b,a)"""
+
+    def __init__(self, o):
+        self._o, self.Dinv = o, np.asarray(o.Dinv).swapaxes(-1, -2)
+
+    def __getattr__(self, name):
+        return getattr(self._o, name)
+
+
+def _lap(o, x, plant=None):
+    """x[n][L][4][4] longdouble -> (lap, A) of every layer; plant: one of TRANSPOSITIONS, in the value alone"""
     out = [ld.laplace_sphere_wk(o, x[:, l]) for l in range(x.shape[1])]
-    return np.stack([a for a, _ in out], axis=1), np.stack([b for _, b in out], axis=1)
+    A = np.stack([b for _, b in out], axis=1)
+    if plant == "D_transposed":
+        return np.stack([ld.laplace_sphere_wk(_DinvTransposed(o), x[:, l])[0] for l in range(x.shape[1])], axis=1), A
+    if plant == "ij_transposed":
+        return np.stack([ld.laplace_sphere_wk(o, x[:, l].swapaxes(-1, -2))[0].swapaxes(-1, -2) for l in range(x.shape[1])], axis=1), A
+    return np.stack([a for a, _ in out], axis=1), A
 
 
 def node_sum(o, w):
@@ -59,12 +75,14 @@ def dropped_copy(o):
 def longdouble(o, f, order, plant=None):
     """f[n][nf][nk][4][4] fp64 -> (value, A) longdouble of the same shape.  plant (order 2): "dropped" one neighbour's contribution missing at
     one point of one element (dropped_copy); "average" spheremp applied before the sum; "no_rspheremp" the sum not scaled; "unsummed" the
-    second Laplacian applied to rspheremp * w of the element alone."""
+    second Laplacian applied to rspheremp * w of the element alone.  plant (either order), one of TRANSPOSITIONS: "D_transposed" Dinv read
+    as (b,a) for (a,b); "ij_transposed" every Laplacian reads its field, and writes its result, at (j,i) for (i,j)."""
     f = np.asarray(f, dtype=np.float64)
     n = f.shape[0]
     x = f.reshape(n, -1, 4, 4).astype(LD)
-    w, A = _lap(o, x)
-    assert plant is None or (plant in PLANTS and order == 2)
+    tp = plant if plant in TRANSPOSITIONS else None
+    w, A = _lap(o, x, tp)
+    assert plant is None or tp or (plant in PLANTS and order == 2)
     if order == 2:
         rs = np.asarray(o.rspheremp).astype(LD)[:, None]
         sm = np.asarray(o.spheremp).astype(LD)[:, None]
@@ -77,7 +95,7 @@ def longdouble(o, f, order, plant=None):
             s.reshape(n, -1, 16)[e0, :, p0] -= w.reshape(n, -1, 16)[e1, :, p1]
         if plant != "no_rspheremp":
             s, sA = rs * s, rs * sA
-        w, _ = _lap(o, s)
+        w, _ = _lap(o, s, tp)
         _, A = _lap(o, sA)
     assert order in ORDERS
     return w.reshape(f.shape), A.reshape(f.shape)

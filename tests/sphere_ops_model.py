@@ -6,7 +6,8 @@ Fields are [n][nf][nk][4 j][4 i]: nf = 1 for a scalar, 2 for a wind or a gradien
 
 reference(g, op, x)      the three routines in their source order of operations (the serial sums of the loops from 0.0, the products left
                          to right) for any numpy float type: in fp64 it has the bits of the oracle's gradient_sphere and
-                         divergence_sphere (test_sphere_ops_cpu.py), which have the reference's; vorticity_sphere has no oracle.
+                         divergence_sphere (test_sphere_ops_cpu.py), which have the reference's; vorticity_sphere has no oracle, and is held to the
+                         reference's own output in test_reference_fieldops_cpu.py (as are the other two, and the C0 forms).
 device_order(o, D, op, x)  the order of operations of csrc/tse_device.h: the x-derivative a product and three fused multiply-adds, the
                          y-derivative quad_matvec's two-stage sum, the metric maps a product and a fused multiply-add, vorticity through
                          the tables Dr = rrearth * D.  A fused multiply-add is restated as one longdouble multiply-add rounded to fp64,
@@ -40,16 +41,21 @@ N_GRAD, N_DIV, N_VOR, N_C0 = 1 + 3 + 1 + 1 + 1, ld.N_DIV, 1 + 1 + 1 + 7 + 1 + 1,
 assert (N_GRAD, N_DIV, N_VOR, N_C0) == (7, 13, 12, 5)
 NF = {"gradient": (1, 2), "divergence": (2, 1), "vorticity": (2, 1)}      # op -> (fields of in, fields of out)
 PLANTS = ("D_swapped", "no_rmetdet", "dudy_sign")                        # errors planted into the vorticity
+TRANSPOSITIONS = ("D_transposed", "ij_transposed")                       # errors of index convention, planted into any of the three ops
 
 
 def steps(op, c0=False):
     return {"gradient": N_GRAD, "divergence": N_DIV, "vorticity": N_VOR}[op] + (N_C0 if c0 else 0)
 
 
-def geo(o, D, T=np.float64):
-    """the metric terms at [n][1][4 j][4 i] in type T: 2x2 entries M[a][b] = M(a+1,b+1), Dvv[l][i] = Dvv(i+1,l+1)"""
+def geo(o, D, T=np.float64, plant=None):
+    """the metric terms at [n][1][4 j][4 i] in type T: 2x2 entries M[a][b] = M(a+1,b+1), Dvv[l][i] = Dvv(i+1,l+1).
+    plant "D_transposed": M[a][b] = M(b+1,a+1) for D and Dinv"""
     t = lambda x: np.asarray(x).astype(T)[:, None]
-    m22 = lambda x: [[t(np.asarray(x)[..., b, a]) for b in range(2)] for a in range(2)]
+    if plant == "D_transposed":
+        m22 = lambda x: [[t(np.asarray(x)[..., a, b]) for b in range(2)] for a in range(2)]
+    else:
+        m22 = lambda x: [[t(np.asarray(x)[..., b, a]) for b in range(2)] for a in range(2)]
     return dict(D=m22(D), Dinv=m22(o.Dinv), metdet=t(o.metdet), rmetdet=t(o.rmetdet), Dvv=np.asarray(o.Dvv).astype(T), rr=T(ld.RREARTH))
 
 
@@ -152,10 +158,16 @@ def _c0_ld(o, w):
 
 
 def longdouble(o, D, op, f, c0=False, plant=None):
-    """f[n][nf_in][nk][4][4] fp64 -> (value, A) longdouble [n][nf_out][nk][4][4]"""
+    """f[n][nf_in][nk][4][4] fp64 -> (value, A) longdouble [n][nf_out][nk][4][4].  plant: one of PLANTS (vorticity) or of TRANSPOSITIONS:
+    "D_transposed" the 2x2 matrices D and Dinv read as (b,a) for (a,b); "ij_transposed" the field read, and the result written, at
+    (j,i) for (i,j)"""
     g = geo(o, D, LD)
     x = np.asarray(f, dtype=np.float64).astype(LD)
-    w, A = reference(g, op, x, False, plant), reference(g, op, x, True)
+    A = reference(g, op, x, True)
+    if plant == "ij_transposed":
+        w = reference(g, op, x.swapaxes(-1, -2), False).swapaxes(-1, -2)
+    else:
+        w = reference(geo(o, D, LD, plant), op, x, False, plant)
     if c0:
         w, A = _c0_ld(o, w), _c0_ld(o, A)
     return w, A

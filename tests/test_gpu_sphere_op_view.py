@@ -14,8 +14,8 @@ held by the bound against sphere_ops_model's longdouble chain, and for the diver
  7 stream        producer -> sphere_op_view -> consumer on one side stream; a stream under capture is refused
  8 ranks         2 and 3 contexts on one GPU through the callback exchange == one context, bit for bit; LOCAL exchanges nothing
  9 refusals      nothing launched, the arrays unchanged
-The Fortran routine sphere_op_view_hip is checked by compilation in both builds of the module only (tests/fortran_resident would need
-its harness edited)."""
+The Fortran routine sphere_op_view_hip is called by tests/fortran_resident/views_harness.F90 (test_gpu_fortran_views.py); what the
+numbers are against the reference's own Fortran is held by test_gpu_reference_fieldops.py."""
 import ctypes as C
 import functools
 

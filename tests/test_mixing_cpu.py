@@ -225,7 +225,7 @@ def test_header_loader_and_libraries_declare_the_entry():
 
 
 def test_fortran_seam_has_the_wrapper():
-    """(compiled by the two Fortran builds of the module; no Fortran host calls it yet)"""
+    """(compiled by the two Fortran builds of the module; tests/fortran_resident/views_harness.F90 calls it on a GPU, test_gpu_fortran_views.py)"""
     src = open(os.path.join(ROOT, "transport_se_amd", "fortran", "cuda_mod_hip.F90")).read().lower()
     assert "name='tse_mix_partials'" in src
     assert re.search(r"subroutine\s+mix_partials_hip\s*\(\s*nt, qa, qb, xmin, xmax, c0, c2, tau, ntau, out\s*\)", src)

@@ -51,6 +51,7 @@ assert (N_VLAP, N_VBIH) == (28, 60)
 ORDERS = (1, 2)
 PLANTS1 = ("no_rr", "curl_added", "D_for_DT", "nu_on_vor")     # in the operator
 PLANTS2 = bm.PLANTS                                            # in the node sum of order 2: dropped, average, no_rspheremp, unsummed
+TRANSPOSITIONS = ("D_transposed", "ij_transposed")             # errors of index convention, in every Laplacian of either order
 
 
 def steps(order):
@@ -64,10 +65,14 @@ def host_fields(o):
     return D, cm.metinv(D), np.array(o.mp)
 
 
-def _geo(o, D, metinv, mp, T):
-    """everything in Fortran's index order [n][i][j] and type T: 2x2 entries M[a][b] = M(a+1,b+1), Dvv[i][l] = Dvv(i+1,l+1)"""
+def _geo(o, D, metinv, mp, T, plant=None):
+    """everything in Fortran's index order [n][i][j] and type T: 2x2 entries M[a][b] = M(a+1,b+1), Dvv[i][l] = Dvv(i+1,l+1).
+    plant "D_transposed": M[a][b] = M(b+1,a+1) for D and Dinv (and metinv, which is symmetric)"""
     t = lambda x: np.asarray(x).astype(T).transpose(0, 2, 1)
-    m22 = lambda x: [[t(np.asarray(x)[..., b, a]) for b in range(2)] for a in range(2)]
+    if plant == "D_transposed":
+        m22 = lambda x: [[t(np.asarray(x)[..., a, b]) for b in range(2)] for a in range(2)]
+    else:
+        m22 = lambda x: [[t(np.asarray(x)[..., b, a]) for b in range(2)] for a in range(2)]
     return dict(D=m22(D), Dinv=m22(o.Dinv), metinv=m22(metinv), mp=t(mp), metdet=t(o.metdet), rmetdet=t(o.rmetdet), spheremp=t(o.spheremp),
                 Dvv=np.asarray(o.Dvv).astype(T).T, rr=T(ld.RREARTH))
 
@@ -154,14 +159,20 @@ def reference_chain_fp64(o, D, metinv, mp, f, order, nu_ratio=1.0):
 
 def longdouble(o, D, metinv, mp, f, order, nu_ratio=1.0, plant=None):
     """f[n][2][nk][4][4] fp64 -> (value, A) longdouble of the same shape.  plant: one of PLANTS1 (an error in the operator, either order) or
-    of PLANTS2 (biharmonic_model's errors in the node sum, order 2)."""
-    assert order in ORDERS and (plant is None or plant in PLANTS1 or (plant in PLANTS2 and order == 2)), (order, plant)
+    of PLANTS2 (biharmonic_model's errors in the node sum, order 2) or of TRANSPOSITIONS: "D_transposed" the 2x2 matrices read as (b,a) for
+    (a,b); "ij_transposed" every Laplacian reads its field, and writes its result, at (j,i) for (i,j)."""
+    assert order in ORDERS and (plant is None or plant in PLANTS1 + TRANSPOSITIONS or (plant in PLANTS2 and order == 2)), (order, plant)
     g = _geo(o, D, metinv, mp, LD)
     f = np.asarray(f, dtype=np.float64)
     n, nk = f.shape[0], f.shape[2]
     x = f.astype(LD)
     p1 = plant if plant in PLANTS1 else None
-    w, A = _levels(g, x, nu_ratio, False, p1), _levels(g, x, nu_ratio, True)
+    gp = _geo(o, D, metinv, mp, LD, plant)
+    if plant == "ij_transposed":
+        planted = lambda y: _levels(g, y.swapaxes(-1, -2), nu_ratio).swapaxes(-1, -2)
+    else:
+        planted = lambda y: _levels(gp, y, nu_ratio, False, p1)
+    w, A = planted(x), _levels(g, x, nu_ratio, True)
     if order == 2:
         rs = np.asarray(o.rspheremp).astype(LD)[:, None, None]
         sm = np.asarray(o.spheremp).astype(LD)[:, None, None]
@@ -175,7 +186,7 @@ def longdouble(o, D, metinv, mp, f, order, nu_ratio=1.0, plant=None):
             s.reshape(n, -1, 16)[e0, :, p0] -= w.reshape(n, -1, 16)[e1, :, p1_]
         if plant != "no_rspheremp":
             s, sA = rs * s, rs * sA
-        w, A = _levels(g, s, nu_ratio, False, p1), _levels(g, sA, nu_ratio, True)
+        w, A = planted(s), _levels(g, sA, nu_ratio, True)
     return w, A
 
 

@@ -218,8 +218,9 @@ def geometry(ne, topo=None):
 def metinv(D):
     """elem%metinv(2,2,np,np) from the area-corrected D[...][b][a] (geometry()["D"]), in D's layout: met = D^T D as cube_mod.F90:292-299
     spells it, metinv = [[met22, -met12], [-met21, met11]] / (detD*detD) (:344-347).  The reference forms metinv before the area
-    correction and divides by alpha afterwards, so its last bits may differ from these; no golden file carries metinv, and the library
-    takes whatever metinv its host gives it (tse_vector_setup)."""
+    correction and divides by alpha afterwards, so its last bits may differ from these (tests/test_reference_fieldops_cpu.py: within
+    1e-15 of the field's maximum of the reference's own, tests/golden/ref_ne2_fieldops.npz); the library takes whatever metinv its host
+    gives it (tse_vector_setup)."""
     D = np.asarray(D, dtype=np.float64)
     D11, D21, D12, D22 = D[..., 0, 0], D[..., 0, 1], D[..., 1, 0], D[..., 1, 1]
     m11 = D11 * D11 + D21 * D21
