@@ -465,6 +465,50 @@ int tse_sphere_op_view(tse_ctx *ctx, int nk, int op, int c0, const tse_view *in,
 int tse_sphere_op_view_plan(int nelemd, int nk, int op, const tse_view *in, const tse_view *out,
                             int path[2], long long lo[2], long long hi[2]);
 
+/* ---- min, max, sums and integrals of a GPU-resident host's fields from element partials: what prim_printstate prints at every statefreq
+ * (prim_state_mod.F90:186-348: MIN, MAX and SUM of u, v, T, ps, dp3d, omega and the forcings, and the mass M = global_integral(ps_v)) and
+ * what global_integral, global_maximum, l1_snorm, l2_snorm and linf_snorm of global_norms_mod.F90 are made of, without the field crossing
+ * to the host.  The device forms every ELEMENT's share in one fixed order that depends on the element's own data alone; the host adds the
+ * shares exactly (math.fsum, repro_sum) and gets the same digits on any number of ranks (diagnostics.stats_from_partials).
+ * field: nf fields of nk levels, 1 <= nk <= nlev + 1, under the view rules of tse_dss_view.  ref (may be NULL): a view of the same nf and
+ * nk, the "true solution" ht of the *_snorm functions.  weight (may be NULL): a view of ONE field of nk levels, such as dp3d; its q stride
+ * is not looked at and every field uses the same weight.  Each view takes its own path (tse_stats_view_plan).
+ * out (HOST memory): [nelemd][nf][TSE_STATS] for per_level = 0, [nelemd][nf][nk][TSE_STATS] for per_level = 1.  For one (element, field,
+ * level) slab, h the field, ht the reference, d = h - ht, m = spheremp[e][p] without a weight and spheremp[e][p] * w with one (one
+ * product per point and level; spheremp is the context's own), every term one rounded operation per arithmetic sign, nothing contracted:
+ *    0 min h            1 max h              2 sum h (unweighted whatever `weight` is: prim_printstate's SUM)
+ *    3 sum m*h (global_integral's J_tmp: the host divides by 4 pi)     4 sum m*fabs(h)      5 sum m*(h*h)      6 max fabs(h)
+ *    7 the number of values of h that are NaN or +-inf, an exact double
+ *    8 sum m*fabs(d)    9 sum m*fabs(ht)    10 sum m*(d*d)    11 sum m*(ht*ht)    12 max fabs(d)    13 max fabs(ht)    (0 without ref)
+ *   14 sum m (the area, or the mass when weight = dp)                 15 0
+ * A NaN is skipped by the extrema (fmin / fmax): a slab of NaNs gives +inf, -inf for entries 0, 1 and 0 for 6, 12, 13; it does enter the
+ * sums.  Where an extremum is zero and zeros of both signs occur, its sign is not specified.
+ * THE ORDER OF ADDITION (csrc/tse_kernels.h: k_stats_view; tests/stats_model.py adds in the same one):
+ *   level share L(k): the 16 terms of the slab, points in memory order p = 4j + i, as the pairwise tree
+ *     (((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7))) + (((t8 + t9) + (t10 + t11)) + ((t12 + t13) + (t14 + t15)));
+ *   element share (per_level = 0): S = L(0); S = S + L(1); ... ascending in k.  Extrema take the same route.
+ * So every number is a function of that element's own values and of spheremp[e] and of nothing else -- not of the path of a view, of the
+ * block index, of the other elements or of how elements are dealt to ranks -- and the per_level = 0 output is the ascending sum of the
+ * per_level = 1 output, bit for bit.
+ * Nothing on the device is written except the call's own partials buffer ("stats_partials": allocated by the first call, grown when a
+ * call needs more, freed by tse_finalize).  No library state is read or written.  The views are read-only, so they may overlap each other,
+ * and unlike the in-place entries a view may lie inside an allocation of the library (tse_device_ptr: "ps_v", "dp3d", "qdp1", ...): the
+ * library's own fields can be looked at the same way.
+ * Refused, with nonzero, tse_last_error() and nothing enqueued: a null field or out, nf < 1, nk outside 1..nlev+1, per_level outside 0|1,
+ * and everything else tse_dss_view refuses of a view (a zero stride on an extent above 1, a view that may overlap itself, memory that is
+ * not device memory of the context's device, a footprint that leaves its allocation, a stream that is being captured or belongs to another
+ * device), and a view inside the partials buffer itself.
+ * stream: not null: waited for, as in tse_view_put.  The call is complete on return whatever stream is: it returns host data, as
+ * tse_apply_forcing does with a budget.  Not collective, no exchange.  Timer group "fieldstats", one launch per call. */
+#define TSE_STATS 16
+int tse_stats_view(tse_ctx *ctx, int nf, int nk, int per_level,
+                   const tse_view *field, const tse_view *ref /* may be NULL */, const tse_view *weight /* may be NULL */,
+                   void *stream, double *out /* HOST */);
+/* the paths and footprints of field ([0]), ref ([1]) and weight ([2]) and every refusal that needs no device; an absent view gives path -1
+ * and lo = hi = 0.  No context, no device. */
+int tse_stats_view_plan(int nelemd, int nf, int nk, const tse_view *field, const tse_view *ref, const tse_view *weight,
+                        int path[3], long long lo[3], long long hi[3]);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -506,11 +550,12 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
  * "eta_dot_dpdn", "omega_p", "dp3d", "ps_v", "qmin", "qmax", "sendbuf", "recvbuf", "q" [nelemd][qsize][nlev][16] and "lnps" [nelemd][16]
  * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference),
  * "remap_status" [nelemd][4] ints (null before the first tse_remap_view), "view_stage" [nelemd][layers][16] the staging field tse_dss_view,
- * tse_biharmonic_view, tse_vlaplace_view and tse_sphere_op_view share (null before the first call of any; it moves only when a call brings more layers than any before) */
+ * tse_biharmonic_view, tse_vlaplace_view and tse_sphere_op_view share (null before the first call of any; it moves only when a call brings more layers than any before),
+ * "stats_partials" the partials buffer of tse_stats_view (null before its first call; it moves only when a call needs more than any before) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), "fieldop" (tse_sphere_op_view: its stage kernel and the sum or copy kernel behind it), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), "fieldop" (tse_sphere_op_view: its stage kernel and the sum or copy kernel behind it), "fieldstats" (tse_stats_view: its one kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -148,7 +148,7 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchr
            "tse_view_put", "tse_view_get", "tse_view_plan", "tse_apply_forcing", "tse_apply_forcing_host",
            "tse_remap_view", "tse_remap_view_status", "tse_remap_view_plan", "tse_dss_view", "tse_dss_view_plan",
            "tse_biharmonic_view", "tse_biharmonic_view_plan", "tse_vector_setup", "tse_vlaplace_view", "tse_vlaplace_view_plan",
-           "tse_sphere_op_view", "tse_sphere_op_view_plan"]
+           "tse_sphere_op_view", "tse_sphere_op_view_plan", "tse_stats_view", "tse_stats_view_plan"]
 COMM_ID_BYTES = 128
 
 
@@ -246,6 +246,8 @@ def lib(path=None, nlev=None):
     L.tse_vlaplace_view_plan.argtypes = [i, i, C.POINTER(View), C.POINTER(View), C.POINTER(i * 2), C.POINTER(C.c_longlong * 2), C.POINTER(C.c_longlong * 2)]
     L.tse_sphere_op_view.argtypes = [vp, i, i, i, C.POINTER(View), C.POINTER(View), vp]
     L.tse_sphere_op_view_plan.argtypes = [i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(i * 2), C.POINTER(C.c_longlong * 2), C.POINTER(C.c_longlong * 2)]
+    L.tse_stats_view.argtypes = [vp, i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(View), vp, vp]
+    L.tse_stats_view_plan.argtypes = [i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(View), C.POINTER(i * 3), C.POINTER(C.c_longlong * 3), C.POINTER(C.c_longlong * 3)]
     if hasattr(L, "tse_test_dcmip_point"):   # the -DTSE_AB_HOOKS twin only (HipMod.test_dcmip_point)
         L.tse_test_dcmip_point.argtypes = [vp, i, d, vp, vp]
     _libs[path] = L

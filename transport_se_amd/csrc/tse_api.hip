@@ -108,6 +108,9 @@ struct tse_ctx {
   // rank with neighbours, its own send and receive buffers [columns][dv_layers] -- the context's own are sized by qsize
   double *dv_stage = nullptr, *dv_send = nullptr, *dv_recv = nullptr;
   size_t dv_layers = 0;
+  // tse_stats_view (allocated by its first call, grown when a call needs more): the element or level shares before they go to the host
+  double* st_part = nullptr;
+  size_t st_cap = 0;   // doubles
   // tse_vector_setup: the per-point tables of the vector Laplacian, [nelemd][VEC_TABS][16] (k_vec_fold; allocated by its first call)
   double* vec_tab = nullptr;
   bool vec_ready = false;
@@ -502,7 +505,7 @@ static std::vector<void*> device_allocations(const tse_ctx* c) {
                   c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
                   c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->norm_owner, c->norm_colw, c->norm_dh, c->qref, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
                   c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int,
-                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc, c->dv_stage, c->dv_send, c->dv_recv, c->vec_tab};
+                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc, c->dv_stage, c->dv_send, c->dv_recv, c->vec_tab, c->st_part};
   std::vector<void*> out;
   for (void* p : ptrs) if (p) out.push_back(p);
   return out;
@@ -2199,6 +2202,60 @@ int tse_sphere_op_view(tse_ctx* c, int nk, int op, int c0, const tse_view* in, c
     [&] { if (c0 == TSE_OP_C0) launch_dss_view_sum(c, p[1].path, wo, ao, (double*)out->ptr); else launch_lap_view_out<1>(c, p[1].path, wo, ao, (double*)out->ptr); });
 }
 
+// ---- min, max, sums and integrals of a resident host's fields (k_stats_view: tse_kernels.h) ------------------------------------------
+// The plans are host code (tse_views.cpp: stats_view_plan); here the checks that need the runtime -- those of tse_dss_view, except that a
+// view may lie inside an allocation of the library (nothing is written through it) -- the stream order of tse_view_put, one launch on the
+// compute stream and the copy of the shares to the host: the call is complete on return.  The partials buffer is the call's own.
+int tse_stats_view(tse_ctx* c, int nf, int nk, int per_level, const tse_view* field, const tse_view* ref, const tse_view* weight, void* stream, double* out) {
+  const char* who = "tse_stats_view";
+  if (!c) return fail("%s: null context", who);
+  if (!out) return fail("%s: null out", who);
+  if (per_level != 0 && per_level != 1) return fail("%s: per_level=%d (0: one share per element and field, 1: one per level)", who, per_level);
+  ViewPlan p[3];
+  { std::string err; if (stats_view_plan(c->nelemd, nf, nk, field, ref, weight, p, &err)) return fail("%s", err.c_str()); }
+  const size_t n = (size_t)c->nelemd * nf * (per_level ? nk : 1) * STATS_N;
+  if ((size_t)c->nelemd * nf >= ((size_t)1 << 31)) return fail("%s: %d elements x %d fields (the launch counts 32-bit blocks)", who, c->nelemd, nf);
+  const tse_view* v[3] = {field, ref, weight};
+  const std::vector<void*> mine = device_allocations(c);
+  bool in_library = false;
+  const char* const role[3] = {"tse_stats_view (field)", "tse_stats_view (ref)", "tse_stats_view (weight)"};   // the name a runtime refusal carries
+  for (int i = 0; i < 3; i++) {
+    if (!v[i]) continue;
+    void* alloc = nullptr;
+    if (view_runtime_checks(c, role[i], "field", p[i], v[i], stream, &alloc)) return 1;
+    if (alloc == c->st_part) return fail("%s: %p lies inside the call's own partials buffer", role[i], v[i]->ptr);
+    in_library = in_library || std::find(mine.begin(), mine.end(), alloc) != mine.end();
+  }
+  if (n > c->st_cap) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->st_part) (void)hipFree(c->st_part);
+    c->st_part = nullptr; c->st_cap = 0;
+    if (dalloc(&c->st_part, n)) return 1;
+    c->st_cap = n;
+  }
+  StatsViewArgs a;
+  for (int i = 0; i < 3; i++) {
+    a.ptr[i] = v[i] ? (const double*)v[i]->ptr : nullptr;
+    a.form[i] = v[i] ? stats_form(p[i].path, view_wide(p[i].path, v[i])) : STATS_POINTS;
+    for (int k = 0; k < 5; k++) a.vs[i][k] = v[i] ? v[i]->stride[k] : 0;
+  }
+  a.nf = nf; a.nk = nk; a.per_level = per_level;
+  hipStream_t us = (hipStream_t)stream;
+  if (order_in(c, us)) return 1;
+  if (in_library && join_inputs(c)) return 1;   // (a library field the auxiliary stream may still be writing)
+  {
+    Scope s(c, "fieldstats");
+    with_stats_view(ref != nullptr, weight != nullptr, [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((size_t)c->nelemd * nf)), dim3(VIEW_THREADS), 0, c->stream, a, (const double*)c->spheremp, c->st_part);
+    });
+    LAUNCH_CHECK();
+  }
+  if (us && order_out(c, us)) return 1;
+  HIPCHK(hipMemcpyAsync(out, c->st_part, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // ---- introspection ------------------------------------------------------------------------------
 void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   struct Ent { const char* n; void* p; size_t b; };
@@ -2210,7 +2267,8 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
                 {"qmax", c->qmax, mm}, {"sendbuf", c->sendbuf, (size_t)c->ncol_send * c->nlyr_halo * 8},
                 {"recvbuf", c->recvbuf, (size_t)c->ncol_recv * c->nlyr_halo * 8}, {"sendbuf_mm", c->sendbuf_mm, (size_t)c->nmm_send * m2},
                 {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}, {"remap_status", c->rv_status, (size_t)c->nelemd * REMAP_STATUS * sizeof(int)},
-                {"view_stage", c->dv_stage, (size_t)c->nelemd * c->dv_layers * 16 * 8}};   // (the staging field of tse_dss_view / tse_biharmonic_view: null before their first call)
+                {"view_stage", c->dv_stage, (size_t)c->nelemd * c->dv_layers * 16 * 8},   // (the staging field of tse_dss_view / tse_biharmonic_view: null before their first call)
+                {"stats_partials", c->st_part, c->st_cap * 8}};                           // (the partials buffer of tse_stats_view: null before its first call)
   for (auto& e : ents) if (!strcmp(e.n, name)) { if (nbytes) *nbytes = e.p ? e.b : 0; return e.p; }
   if (nbytes) *nbytes = 0;
   return nullptr;

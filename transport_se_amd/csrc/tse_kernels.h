@@ -3394,4 +3394,204 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_sphere_op_stage(int nelemd, Ds
 }
 inline long long sphere_op_groups(long long nk) { return (nk + SPHERE_OP_LEVELS - 1) / SPHERE_OP_LEVELS; }
 
+// ---- min, max, sums and integrals of a host's own fields through strided views (tse_stats_view) -----------------------------------
+// The element shares of prim_printstate's MIN / MAX / SUM lines and of global_integral, global_maximum, l1_snorm, l2_snorm and linf_snorm
+// (prim_state_mod.F90:186-348, global_norms_mod.F90) for nf fields of nk levels: STATS_N = TSE_STATS doubles per (element, field, level)
+// slab, or per (element, field).  h the field, ht the reference (REF), d = h - ht, m = spheremp[e][p] (or spheremp[e][p] * w: WGT), every
+// term one rounded operation per arithmetic sign, nothing contracted:
+//   0 min h   1 max h   2 sum h   3 sum m*h   4 sum m*fabs(h)   5 sum m*(h*h)   6 max fabs(h)   7 count of NaN / +-inf   14 sum m
+//   8 sum m*fabs(d)   9 sum m*fabs(ht)   10 sum m*(d*d)   11 sum m*(ht*ht)   12 max fabs(d)   13 max fabs(ht)   (0 without REF)   15: 0
+// A NaN does not enter an extremum (it enters as the extremum's identity: +inf for 0, -inf for 1, 0 for 6, 12 and 13); it does enter the
+// sums.  NaN and +-inf are told by their bits, so the extrema never see a NaN whatever the compiler assumes about them.
+//
+// THE ORDER (tests/stats_model.py adds in the same one).
+//   1. level share L(k): the 16 terms t0..t15 of the slab, points in memory order p = 4j + i, as the pairwise tree
+//        (((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7))) + (((t8 + t9) + (t10 + t11)) + ((t12 + t13) + (t14 + t15)))
+//      -- what an xor-butterfly over the lane strides 1, 2, 4, 8 gives in every lane.  Here one lane adds the whole tree of its level.
+//   2. element share (per_level = 0): S = L(0); S = S + L(1); ... ascending in k.
+// Extrema take the same route.  Every number is a function of the element's own values and of spheremp[e] alone: not of the path of a
+// view, of wide or narrow, of the block index, of the other elements or of how elements are dealt to ranks; and the element share is the
+// ascending sum of the level shares in every bit.
+//
+// block = (element, field).  Each view's nk x 16 slab is brought into the LDS image img[v][p][VIEW_PITCH] by that view's own loader, chosen
+// by a block-uniform switch on StatsViewArgs::form: the rows of path 1 by dss_rows_to_tile (nk == NLEV), the lines of path 0 and the
+// single entries of path 2 with the addressing of k_dss_view_stage.  The arithmetic is one body over the image: lane = level, lanes
+// 0..127 the entries without the reference, lanes 128..255 (REF) entries 8 to 13.  One pass over each input; only `out` is written.
+constexpr int STATS_N = 16;
+enum StatsForm { STATS_LINES_WIDE = 0, STATS_POINTS = 1, STATS_ROWS_WIDE = 2, STATS_ROWS = 3 };
+struct StatsViewArgs { const double* ptr[3]; long long vs[3][5]; int form[3]; int nf, nk, per_level; };   // 0 field, 1 ref, 2 weight
+
+__device__ __forceinline__ void stats_load_image(const double* __restrict__ V, const long long* vs, int form, int nk, double* __restrict__ img, int tid) {
+  if (form == STATS_ROWS_WIDE) dss_rows_to_tile<true, NLEV>(V, vs[4], img, tid);
+  else if (form == STATS_ROWS) dss_rows_to_tile<false, NLEV>(V, vs[4], img, tid);
+  else if (form == STATS_LINES_WIDE) {
+    constexpr int NI = (NLEVP * 8 + VIEW_THREADS - 1) / VIEW_THREADS;
+    const int n = nk * 8;
+    double2 r[NI];
+#pragma unroll
+    for (int u = 0; u < NI; u++) { const int it = min(u * VIEW_THREADS + tid, n - 1); r[u] = *(const double2*)(V + (it >> 3) * vs[2] + 2 * (it & 7)); }
+#pragma unroll
+    for (int u = 0; u < NI; u++) view_keep(r[u]);
+#pragma unroll
+    for (int u = 0; u < NI; u++) {
+      const int it = u * VIEW_THREADS + tid;
+      if (it < n) { double* s = img + 2 * (it & 7) * VIEW_PITCH + (it >> 3); s[0] = r[u].x; s[VIEW_PITCH] = r[u].y; }
+    }
+  } else {
+    constexpr int NI = (NLEVP * 16 + VIEW_THREADS - 1) / VIEW_THREADS;
+    const int n = nk * 16;
+    double r[NI];
+#pragma unroll
+    for (int u = 0; u < NI; u++) { const int it = min(u * VIEW_THREADS + tid, n - 1), p = it & 15; r[u] = V[(it >> 4) * vs[2] + (p >> 2) * vs[3] + (p & 3) * vs[4]]; }
+#pragma unroll
+    for (int u = 0; u < NI; u++) view_keep(r[u]);
+#pragma unroll
+    for (int u = 0; u < NI; u++) {
+      const int it = u * VIEW_THREADS + tid;
+      if (it < n) img[(it & 15) * VIEW_PITCH + (it >> 4)] = r[u];
+    }
+  }
+}
+
+// Whether x is NaN or +-inf / whether it is NaN, from its bits.  The library is built with -fno-honor-nans, and the compiler reads an
+// exponent test of a double's bits as a floating-point class test, from which it then drops the NaN: the two words pass through an empty
+// statement (as view_keep) so that they are integers of unknown origin.
+__device__ __forceinline__ void stats_words(double x, unsigned& hi, unsigned& lo) {
+  hi = (unsigned)__double2hiint(x); lo = (unsigned)__double2loint(x);
+  asm volatile("" : "+v"(hi), "+v"(lo));
+}
+__device__ __forceinline__ bool stats_nonfinite(double x) {
+  unsigned hi, lo;
+  stats_words(x, hi, lo);
+  return (hi & 0x7ff00000u) == 0x7ff00000u;
+}
+__device__ __forceinline__ bool stats_nan(double x) {
+  unsigned hi, lo;
+  stats_words(x, hi, lo);
+  return (hi & 0x7ff00000u) == 0x7ff00000u && ((hi & 0x000fffffu) | lo) != 0u;
+}
+// entry i of a group of N: 0 a sum, 1 a minimum, 2 a maximum
+template <int N>
+struct StatsAcc {
+  double v[N];
+  template <class Kind>
+  __device__ __forceinline__ StatsAcc plus(const StatsAcc& b, Kind kind) const {
+#pragma clang fp contract(off)
+    StatsAcc r;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.v[i] = kind(i) == 0 ? v[i] + b.v[i] : kind(i) == 1 ? fmin(v[i], b.v[i]) : fmax(v[i], b.v[i]);
+    return r;
+  }
+};
+// the tree of THE ORDER over the 16 points of one level; term(p) gives the N terms of point p
+template <int N, class Term, class Kind>
+__device__ __forceinline__ StatsAcc<N> stats_tree(Term term, Kind kind) {
+  StatsAcc<N> o[2];
+#pragma unroll
+  for (int hf = 0; hf < 2; hf++) {
+    StatsAcc<N> q[2];
+#pragma unroll
+    for (int qd = 0; qd < 2; qd++) {
+      const int p = 8 * hf + 4 * qd;
+      q[qd] = term(p).plus(term(p + 1), kind).plus(term(p + 2).plus(term(p + 3), kind), kind);
+    }
+    o[hf] = q[0].plus(q[1], kind);
+  }
+  return o[0].plus(o[1], kind);
+}
+constexpr int STATS_RED_PITCH = NLEVP;   // the level shares of one entry in the LDS image of the element sum (odd: entries on different banks)
+static_assert(9 * STATS_RED_PITCH <= 16 * VIEW_PITCH && 15 * STATS_RED_PITCH <= 2 * 16 * VIEW_PITCH, "the level shares fit the images they replace");
+static_assert(NLEVP <= 128, "one lane per level in each half of the block");
+
+template <bool REF, bool WGT>
+__global__ __launch_bounds__(VIEW_THREADS) void k_stats_view(StatsViewArgs a, const double* __restrict__ spheremp, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  constexpr int NV = 1 + (REF ? 1 : 0) + (WGT ? 1 : 0), IMG = 16 * VIEW_PITCH, IW = REF ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) double img[NV * IMG];
+  const int tid = threadIdx.x, nk = a.nk;
+  const int f = (int)(blockIdx.x % (unsigned)a.nf);
+  const long long e = (long long)(blockIdx.x / (unsigned)a.nf);
+  stats_load_image(a.ptr[0] + e * a.vs[0][0] + f * a.vs[0][1], a.vs[0], a.form[0], nk, img, tid);
+  if (REF) stats_load_image(a.ptr[1] + e * a.vs[1][0] + f * a.vs[1][1], a.vs[1], a.form[1], nk, img + IMG, tid);
+  if (WGT) stats_load_image(a.ptr[2] + e * a.vs[2][0], a.vs[2], a.form[2], nk, img + IW * IMG, tid);
+  __syncthreads();
+
+  const double inf = __builtin_huge_val();
+  const double* sm = spheremp + (size_t)e * 16;
+  const int k = tid & 127, half = tid >> 7;
+  const bool live = k < nk && (half == 0 || REF);
+  const int kc = min(k, nk - 1);
+  auto mass = [&](int p) { const double s = sm[p]; return WGT ? s * img[IW * IMG + p * VIEW_PITCH + kc] : s; };
+  // entries 0..7 and 14 (lanes 0..127), entries 8..13 (lanes 128..255)
+  auto kind0 = [](int i) { return i == 0 ? 1 : (i == 1 || i == 6) ? 2 : 0; };
+  auto kind1 = [](int i) { return i >= 4 ? 2 : 0; };
+  StatsAcc<9> s0;
+  StatsAcc<6> s1;
+  if (half == 0) {
+    s0 = stats_tree<9>([&](int p) {
+#pragma clang fp contract(off)
+      const double h = img[p * VIEW_PITCH + kc], m = mass(p), ah = fabs(h);
+      const bool nan = stats_nan(h);
+      StatsAcc<9> t;
+      t.v[0] = nan ? inf : h; t.v[1] = nan ? -inf : h; t.v[2] = h; t.v[3] = m * h; t.v[4] = m * ah; t.v[5] = m * (h * h);
+      t.v[6] = nan ? 0.0 : ah; t.v[7] = stats_nonfinite(h) ? 1.0 : 0.0; t.v[8] = m;
+      return t;
+    }, kind0);
+  } else if (REF) {
+    s1 = stats_tree<6>([&](int p) {
+#pragma clang fp contract(off)
+      const double h = img[p * VIEW_PITCH + kc], ht = img[IMG + p * VIEW_PITCH + kc], m = mass(p);
+      const double d = h - ht, ad = fabs(d), at = fabs(ht);
+      StatsAcc<6> t;
+      t.v[0] = m * ad; t.v[1] = m * at; t.v[2] = m * (d * d); t.v[3] = m * (ht * ht);
+      t.v[4] = stats_nan(d) ? 0.0 : ad; t.v[5] = stats_nan(ht) ? 0.0 : at;
+      return t;
+    }, kind1);
+  }
+
+  if (a.per_level) {
+    if (!live) return;
+    double* o = out + (((size_t)e * a.nf + f) * nk + k) * STATS_N;
+    if (half == 0) {
+#pragma unroll
+      for (int i = 0; i < 8; i++) o[i] = s0.v[i];
+      o[14] = s0.v[8]; o[15] = 0.0;
+      if (!REF) {
+#pragma unroll
+        for (int i = 8; i < 14; i++) o[i] = 0.0;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 6; i++) o[8 + i] = s1.v[i];
+    }
+    return;
+  }
+  // the element share: the level shares go where the images were, red[entry][k]; lane i < 16 adds entry i ascending in k
+  __syncthreads();
+  double* red = img;
+  if (live) {
+    if (half == 0) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) red[i * STATS_RED_PITCH + k] = s0.v[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 6; i++) red[(9 + i) * STATS_RED_PITCH + k] = s1.v[i];
+    }
+  }
+  __syncthreads();
+  if (tid < STATS_N) {
+    // entry tid sits in row: 0..7 -> 0..7, 14 -> 8, 8..13 -> 9..14 (REF), 15 and the absent ones: none
+    const int row = tid < 8 ? tid : tid == 14 ? 8 : (REF && tid < 14) ? tid + 1 : -1;
+    const int kd = tid == 0 ? 1 : (tid == 1 || tid == 6 || tid == 12 || tid == 13) ? 2 : 0;
+    double S = 0.0;
+    if (row >= 0) {
+      const double* L = red + row * STATS_RED_PITCH;
+      S = L[0];
+#pragma unroll 8
+      for (int kk = 1; kk < nk; kk++) S = kd == 0 ? S + L[kk] : kd == 1 ? fmin(S, L[kk]) : fmax(S, L[kk]);   // (unrolled: eight LDS reads in flight, the additions in order)
+    }
+    out[((size_t)e * a.nf + f) * STATS_N + tid] = S;
+  }
+}
+
 }  // namespace tse

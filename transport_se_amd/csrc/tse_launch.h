@@ -96,4 +96,18 @@ inline void with_view_path(int path, bool wide, F&& f) {
   else f(p2, n);
 }
 
+// tse_stats_view: (has a reference view, has a weight view) -> f(k_stats_view instantiation).  The paths of the views are no template
+// parameters: each view's loader is chosen inside the kernel by stats_form.
+template <class F>
+inline void with_stats_view(bool ref, bool weight, F&& f) {
+  if (ref) { if (weight) f(k_stats_view<true, true>); else f(k_stats_view<true, false>); }
+  else { if (weight) f(k_stats_view<false, true>); else f(k_stats_view<false, false>); }
+}
+// (path of a view's plan, view_wide of that path and view) -> the loader of that view in k_stats_view; the generic loader also serves a
+// point-fastest view that may not move 16 bytes per lane
+inline int stats_form(int path, bool wide) {
+  if (path == 1) return wide ? STATS_ROWS_WIDE : STATS_ROWS;
+  return path == 0 && wide ? STATS_LINES_WIDE : STATS_POINTS;
+}
+
 }  // namespace tse

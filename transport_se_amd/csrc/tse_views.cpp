@@ -232,6 +232,24 @@ int sphere_op_view_overlap(const tse_view* in, const tse_view* out, const ViewPl
   return 0;
 }
 
+// tse_stats_view's up to three views, all read-only: `field` and `ref` views of tse_dss_view with nf fields of nk levels, `weight` one
+// with a single field whose q stride is not looked at (every field reads the same weight).  An absent view (null) leaves path -1 and an
+// empty footprint.  The views may overlap each other.
+int stats_view_plan(int nelemd, int nf, int nk, const tse_view* field, const tse_view* ref, const tse_view* weight, ViewPlan out[3], std::string* err) {
+  const char* who = "tse_stats_view";
+  if (!field || !out) return refuse(err, "%s: null %s", who, !field ? "view" : "plan");
+  const tse_view* v[3] = {field, ref, weight};
+  const char* role[3] = {"field", "ref", "weight"};
+  for (int i = 0; i < 3; i++) {
+    out[i] = ViewPlan();
+    out[i].path = -1;
+    if (!v[i]) continue;
+    std::string e;
+    if (dss_view_plan(nelemd, i == 2 ? 1 : nf, nk, v[i], &out[i], &e, who)) return refuse(err, "%s (%s)", e.c_str(), role[i]);
+  }
+  return 0;
+}
+
 }  // namespace tse
 
 // the C plan entries: an error becomes the message of tse_last_error; n plans go out as path[] / lo[] / hi[], each of them optional
@@ -294,6 +312,14 @@ extern "C" int tse_sphere_op_view_plan(int nelemd, int nk, int op, const tse_vie
   // strides alone (both ptr null): nothing is known of where the views lie
   if ((in->ptr || out->ptr) && tse::sphere_op_view_overlap(in, out, p, &err)) return refused(err);
   return plans_out(p, 2, path, lo, hi);
+}
+
+extern "C" int tse_stats_view_plan(int nelemd, int nf, int nk, const tse_view* field, const tse_view* ref, const tse_view* weight, int path[3], long long lo[3],
+                                   long long hi[3]) {
+  tse::ViewPlan p[3];
+  std::string err;
+  if (tse::stats_view_plan(nelemd, nf, nk, field, ref, weight, p, &err)) return refused(err);
+  return plans_out(p, 3, path, lo, hi);
 }
 
 #ifdef TSE_AB_HOOKS

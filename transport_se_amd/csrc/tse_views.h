@@ -61,6 +61,11 @@ bool sphere_op_fields(int op, int* nf_in, int* nf_out);
 int sphere_op_view_plan(int nelemd, int nk, int op, const tse_view* in, const tse_view* out_view, ViewPlan out[2], std::string* err);
 int sphere_op_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err);
 
+// The up to three read-only views of tse_stats_view / tse_stats_view_plan -> out[0..2] = the plans of field, ref, weight: each a view of
+// tse_dss_view, field and ref with nf fields, weight with one (its q stride is not looked at).  ref and weight may be null: path -1 and an
+// empty footprint.  No overlap rule: nothing is written through a view.
+int stats_view_plan(int nelemd, int nf, int nk, const tse_view* field, const tse_view* ref, const tse_view* weight, ViewPlan out[3], std::string* err);
+
 // the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
 int set_last_error(const char* msg);
 

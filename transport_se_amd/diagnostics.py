@@ -11,6 +11,9 @@
 * `tracer_mass`: the conserved integral behind the "Q,Q diss" line (prim_state_mod.F90:352-385 through
   global_integral, global_norms_mod.F90:39-86).
 * `printstate_lines`: the `qv=  min max sum` lines of prim_printstate (prim_state_mod.F90:341-347).
+* `stats_from_partials` / `printstate_field_lines` / `fortran_e`: min, max, sum, integral, mean and the l1 / l2 / linf norms of a resident
+  host's own fields from the element shares the device forms (tse_stats_view), added exactly, and prim_printstate's `u = `, `v = `,
+  `T = `, `ps= `, `M = ` lines in its format 100 from them.
 * `global_sum` / `gather_by_gid`: the multi-rank forms.  The reference makes its global integrals independent of the task
   count with a fixed-point reproducible sum (repro_sum_mod.F90:216-632; "independent of thread count and task count",
   global_norms_mod.F90:66-68).  Here every ELEMENT's partial sum is formed in a fixed order (on the device:
@@ -225,6 +228,85 @@ def printstate_lines(qdp, dp):
     """(min, max, sum) of Q = Qdp/dp per tracer, as the `qv=` lines print them"""
     q = qdp / dp[:, None]
     return [(float(q[:, t].min()), float(q[:, t].max()), float(q[:, t].sum())) for t in range(q.shape[1])]
+
+
+STATS = 16                                                       # TSE_STATS
+STATS_SUMS = (2, 3, 4, 5, 7, 8, 9, 10, 11, 14)                   # the entries of a tse_stats_view share that are sums
+STATS_MINS, STATS_MAXS = (0,), (1, 6, 12, 13)
+
+
+def stats_from_partials(parts, ref=False):
+    """parts: the shares HipMod.stats_view returned, [n][nf][16] or [n][nf][nk][16] -- one array, or a list with one per rank -> dict of
+    arrays [nf] or [nf][nk]: min, max, sum (prim_printstate's MIN, MAX, SUM), integral (global_integral: entry 3 over 4 pi), absmax,
+    nonfinite (an int), mean (entry 3 over entry 14), area (entry 14 over 4 pi) and, with ref=True, l1, l2, linf combined exactly as
+    l1_snorm, l2_snorm, linf_snorm combine their integrals and maxima (global_norms_mod.F90).  Sums over elements and ranks are
+    math.fsum's (exact, then rounded once; a column that holds a NaN or inf, or whose sum overflows, is added by numpy and gives NaN or
+    inf), extrema min / max: the same digits however the elements are dealt to ranks."""
+    if isinstance(parts, np.ndarray):
+        parts = [parts]
+    x = np.concatenate([np.asarray(p, dtype=np.float64) for p in parts], axis=0)
+    if x.ndim not in (3, 4) or x.shape[-1] != STATS:
+        raise ValueError("stats_from_partials: shares of shape %s (want [n][nf][16] or [n][nf][nk][16])" % (x.shape,))
+    shape = x.shape[1:-1]
+    flat = x.reshape(x.shape[0], -1, STATS)
+    tot = np.zeros((flat.shape[1], STATS))
+    for c in range(flat.shape[1]):
+        for j in STATS_SUMS:
+            col = flat[:, c, j]
+            try:
+                tot[c, j] = math.fsum(col.tolist()) if np.isfinite(col).all() else col.sum()
+            except OverflowError:          # finite shares whose sum is not: fsum raises where an addition gives inf
+                with np.errstate(over="ignore"):
+                    tot[c, j] = col.sum()
+        for j in STATS_MINS:
+            tot[c, j] = flat[:, c, j].min()
+        for j in STATS_MAXS:
+            tot[c, j] = flat[:, c, j].max()
+    tot = tot.reshape(shape + (STATS,))
+    four_pi = 4.0 * math.pi
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = dict(min=tot[..., 0], max=tot[..., 1], sum=tot[..., 2], integral=tot[..., 3] / four_pi, absmax=tot[..., 6],
+                   nonfinite=tot[..., 7].astype(np.int64), mean=tot[..., 3] / tot[..., 14], area=tot[..., 14] / four_pi)
+        if ref:
+            out["l1"] = (tot[..., 8] / four_pi) / (tot[..., 9] / four_pi)
+            out["l2"] = np.sqrt(tot[..., 10] / four_pi) / np.sqrt(tot[..., 11] / four_pi)
+            out["linf"] = tot[..., 12] / tot[..., 13]
+    return out
+
+
+def fortran_e(x, w=23, d=15):
+    """Fortran's Ew.d of x: 0.ddd...E+ee right-justified in w columns, the d digits correctly rounded (Python's own '%.*e' conversion;
+    only the point is moved).  A three-digit exponent drops the E (0.ddd+100), as Fortran does; -0.0 keeps its sign."""
+    x = float(x)
+    if x != x:
+        body = "NaN"
+    elif x in (math.inf, -math.inf):
+        body = "Infinity" if x > 0 else "-Infinity"
+    else:
+        mant, exp = ("%.*e" % (d - 1, x)).split("e")
+        sign = "-" if mant.startswith("-") else ""
+        digits = mant.lstrip("-").replace(".", "")
+        e = int(exp) + 1 if x != 0 else 0
+        body = sign + "0." + digits + ("E%+03d" % e if abs(e) < 100 else "%+04d" % e)
+    return body.rjust(w) if len(body) <= w else "*" * w
+
+
+PRINTSTATE_LABELS = dict(u="u     = ", v="v     = ", T="T     = ", ps="ps= ", dp3d="dp3d  = ", omega="omega = ")
+
+
+def printstate_field_lines(fields, mass=None, scale=1.0 / G):
+    """prim_printstate's lines (prim_state_mod.F90:340-347, format 100 = A10,3(E23.15)) from device statistics.  fields: (name, stats)
+    pairs in the order to print, stats a dict of stats_from_partials for ONE field without levels (min, max, sum scalars or arrays of
+    one value); name one of u, v, T, ps, dp3d, omega or any label of up to 10 characters.  mass: the integral of ps_v
+    (stats_from_partials(...)["integral"]) for the line "      M = " Mass kg/m^2 Mass2 mb, Mass = Mass2 * scale (scale = 1/g)."""
+    lines = []
+    for name, st in fields:
+        label = PRINTSTATE_LABELS.get(name, name)
+        lines.append("%10s" % label[:10] + "".join(fortran_e(np.asarray(st[k]).reshape(-1)[0]) for k in ("min", "max", "sum")))
+    if mass is not None:
+        m2 = float(np.asarray(mass).reshape(-1)[0])
+        lines.append("      M = " + fortran_e(m2 * scale) + " kg/m^2" + fortran_e(m2) + " mb     ")
+    return lines
 
 
 def gather_by_gid(local, gid, nelem, dist_mod, rank, world):

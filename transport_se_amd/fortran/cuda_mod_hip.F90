@@ -68,6 +68,9 @@ module cuda_mod
   public :: sphere_op_view_hip
   integer, parameter, public :: op_gradient = 0, op_divergence = 1, op_vorticity = 2   ! TSE_OP_GRADIENT, TSE_OP_DIVERGENCE, TSE_OP_VORTICITY
   integer, parameter, public :: op_local = 0, op_c0 = 1                                ! TSE_OP_LOCAL, TSE_OP_C0
+  ! min, max, sums and integrals of the host's own device-resident fields from element partials (tse_stats_view)
+  public :: stats_view_hip
+  integer, parameter, public :: tse_stats = 16   ! TSE_STATS
   logical, save :: remap_refused = .false.            ! remap_view_hip / remap_view_status_hip: the master thread's answer, read by every thread
   integer(c_int), save :: remap_nrefused = 0, remap_where(4) = 0
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
@@ -231,6 +234,10 @@ module cuda_mod
      integer(c_int) function tse_sphere_op_view(ctx, nk, op, c0, vin, vout, stream) bind(C, name='tse_sphere_op_view')
        import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nk, op, c0
        type(tse_view), intent(in) :: vin, vout
+     end function
+     integer(c_int) function tse_stats_view(ctx, nf, nk, per_level, field, ref, weight, stream, out) bind(C, name='tse_stats_view')
+       import; type(c_ptr), value :: ctx, ref, weight, stream, out; integer(c_int), value :: nf, nk, per_level
+       type(tse_view), intent(in) :: field
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -910,6 +917,34 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine dss_view_hip
+
+  ! out(1:16, [1:nk,] 1:nf, 1:nelemd) <- the element shares of min, max, sum, integral, norms and the non-finite count of
+  ! field(:,:,1:nk,1:nf) of the host's DEVICE array at ptr (include/transport_se_hip.h: tse_stats_view names the 16 entries and the order
+  ! of addition): what prim_printstate and global_integral / l1_snorm / l2_snorm / linf_snorm need, without the field leaving the device.
+  ! out is HOST memory, tse_stats * nf * nelemd doubles (per_level = 0) or tse_stats * nk * nf * nelemd (per_level = 1); the host adds the
+  ! shares of all elements and ranks (repro_sum).  strides(1:5) in doubles for element, q, level, j, i.  ref_ptr / ref_strides: the true
+  ! solution ht of the *_snorm functions, a view of the same nf and nk, or c_null_ptr for none; w_ptr / w_strides: ONE field of nk levels
+  ! that multiplies spheremp (dp3d), its q stride not looked at, or c_null_ptr for none.  Nothing is written on the device; the arrays may
+  ! be the library's own.  Not collective.  stream is waited for; the call is complete on return.  A refusal aborts.
+  subroutine stats_view_hip(nf, nk, per_level, ptr, strides, ref_ptr, ref_strides, w_ptr, w_strides, stream, out)
+    integer,              intent(in) :: nf, nk, per_level
+    type(c_ptr),          intent(in) :: ptr, ref_ptr, w_ptr, stream
+    integer(c_long_long), intent(in) :: strides(5), ref_strides(5), w_strides(5)
+    real(c_double), intent(out), target :: out(*)
+    type(tse_view), target :: v, r, w
+    type(c_ptr) :: rp, wp
+    v%ptr = ptr; v%stride = strides
+    r%ptr = ref_ptr; r%stride = ref_strides
+    w%ptr = w_ptr; w%stride = w_strides
+    rp = c_null_ptr; wp = c_null_ptr
+    if (c_associated(ref_ptr)) rp = c_loc(r)
+    if (c_associated(w_ptr)) wp = c_loc(w)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_stats_view(ctx, int(nf,c_int), int(nk,c_int), int(per_level,c_int), v, rp, wp, stream, c_loc(out)), 'stats_view_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine stats_view_hip
 
   ! out(:,:,1:nk,1:nf) at out_ptr <- laplace_sphere_wk of field(:,:,1:nk,1:nf) of the host's DEVICE array at ptr (order lap_order1: weak,
   ! not summed, no exchange) or laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(field))) (lap_order2: biharmonic_wk_scalar before its

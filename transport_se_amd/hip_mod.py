@@ -304,6 +304,21 @@ def sphere_op_view_plan(nelemd, nk, op, field, out, nlev=None):
     return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
 
 
+STATS = 16   # TSE_STATS: doubles per share of HipMod.stats_view
+
+
+def stats_view_plan(nelemd, nf, nk, field, ref=None, weight=None, nlev=None):
+    """tse_stats_view_plan: [dict(path=, lo=, hi=)] of the three views of HipMod.stats_view -- field, ref, weight, each a _lib.View or its
+    five strides (doubles, in the order of VIEW_AXES); an absent ref or weight gives None in its place.  Needs no device.  Raises TseError
+    for views stats_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    v = [None if x is None else _raw_view(x) for x in (field, ref, weight)]
+    path, lo, hi = (C.c_int * 3)(), (C.c_longlong * 3)(), (C.c_longlong * 3)()
+    if L.tse_stats_view_plan(int(nelemd), int(nf), int(nk), *[None if x is None else C.byref(x) for x in v], C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return [None if v[i] is None else dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(3)]
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -778,6 +793,41 @@ class HipMod:
             if nfo is not None and onf != nfo:
                 raise TseError("%s: out: %s" % (who, side(onf, nfo)))
         self._chk(self.L.tse_sphere_op_view(self.h, int(nk), o, int(c0), C.byref(vi), C.byref(vo), _stream_handle(stream)))
+
+    # ---- min, max, sums and integrals of the host's fields from element partials (tse_stats_view) ----
+    def stats_view(self, field, axes, ref=None, ref_axes=None, weight=None, weight_axes=None, per_level=False, stream=None, nf=None, nk=None):
+        """The element shares [nelemd][nf][16] (per_level: [nelemd][nf][nk][16]) of min, max, sum, integral, norms and the non-finite
+        count of the device array `field`: nf fields of nk levels, the array's own extents along the letters q and k of `axes` (a missing
+        letter: extent 1).  ref: another device array of the same nf and nk (axes `ref_axes`, default `axes`), the true solution of
+        l1 / l2 / linf; weight: a device array of ONE field of nk levels (axes `weight_axes`, default `axes` without q), such as dp3d.
+        The 16 entries and the order of addition are those of tse_stats_view in the header; diagnostics.stats_from_partials turns the
+        shares of all elements and ranks into numbers.  Nothing is written on the device but the call's own buffer; the arrays may be
+        the library's own (device_ptr).  Not collective.  A stream is waited for; the call is complete on return.  The arrays may also be
+        ready _lib.Views (then nf and nk are needed)."""
+        who = "stats_view"
+        if isinstance(field, _lib.View):
+            if nf is None or nk is None:
+                raise TseError("%s: nf and nk are needed with a ready view" % who)
+            vf = field
+        else:
+            vf, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=False)
+        vr = vw = None
+        if isinstance(ref, _lib.View):
+            vr = ref
+        elif ref is not None:
+            vr, rnf, rnk = build_dss_view(ref, axes if ref_axes is None else ref_axes, self.nelemd, who=who, written=False)
+            if (rnf, rnk) != (nf, nk):
+                raise TseError("%s: ref has %d fields of %d levels, field has %d of %d" % (who, rnf, rnk, nf, nk))
+        if isinstance(weight, _lib.View):
+            vw = weight
+        elif weight is not None:
+            vw, wnf, wnk = build_dss_view(weight, str(axes).replace("q", "") if weight_axes is None else weight_axes, self.nelemd, who=who, written=False)
+            if (wnf, wnk) != (1, nk):
+                raise TseError("%s: weight has %d fields of %d levels, one field of %d is needed" % (who, wnf, wnk, nk))
+        out = np.empty((self.nelemd, int(nf)) + ((int(nk),) if per_level else ()) + (STATS,), dtype=np.float64)
+        self._chk(self.L.tse_stats_view(self.h, int(nf), int(nk), int(bool(per_level)), C.byref(vf), None if vr is None else C.byref(vr),
+                                        None if vw is None else C.byref(vw), _stream_handle(stream), _vp(out)))
+        return out
 
     def last_error(self):
         return self.L.tse_last_error().decode()
