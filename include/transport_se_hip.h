@@ -509,6 +509,53 @@ int tse_stats_view(tse_ctx *ctx, int nf, int nk, int per_level,
 int tse_stats_view_plan(int nelemd, int nf, int nk, const tse_view *field, const tse_view *ref, const tse_view *weight,
                         int path[3], long long lo[3], long long hi[3]);
 
+/* ---- the three vertical scans of the primitive equations on a GPU-resident host's columns: pressure from dp3d, the hydrostatic
+ * geopotential (preq_hydrostatic, src/asp_tests.F90:1708-1757) and omega / p (E3SM's preq_omega_ps), without dp3d or T crossing to the
+ * host.  Levels count from 0 at the model top, n = tse_nlev().  One op per call:
+ *   op              dp           p                    a                 b                                        out
+ *   TSE_COL_PINT    n levels     NULL                 NULL              NULL                                     n + 1 levels
+ *   TSE_COL_PMID    n levels     NULL                 NULL              NULL                                     n levels
+ *   TSE_COL_PHI     n levels     n levels or NULL     T_v, n levels     phis, ONE level (level stride not read)  n levels
+ *   TSE_COL_OMEGA   iff p NULL   n levels or NULL     vgrad_p, n        divdp, n levels                          n levels
+ * A view where the table says NULL is refused, and so is a NULL where it says a view; TSE_COL_OMEGA takes dp exactly when p is NULL.
+ * The q axis has extent 1 in every view: its stride is not read.  ptop = hyai(1) * ps0 is read by every op that forms a pressure (all but
+ * PHI and OMEGA with p given), rgas by PHI alone.  No library state is read or written: not the cached bounds, not the freshness of
+ * q / lnps, not the prescribed-wind state.
+ * THE ARITHMETIC: one rounded fp64 operation per arithmetic sign, left to right, nothing contracted; every / a true division; *0.5 and 2*
+ * are exact (csrc/tse_kernels.h: k_column_view; tests/column_model.py follows the same lines).
+ *   PINT   pi[0] = ptop;  pi[k+1] = pi[k] + dp[k]
+ *   PMID   p[0] = ptop + dp[0]*0.5;  p[k] = (p[k-1] + dp[k-1]*0.5) + dp[k]*0.5        (E3SM: p(k) = p(k-1) + dp(k-1)/2 + dp(k)/2)
+ *   PHI    hkk = (dp[k]*0.5)/p[k], hkl = 2*hkk, t = rgas*T_v[k]:
+ *          phii[n-1] = t*hkl,  phi[n-1] = phis + t*hkk;   k = n-2 .. 1: phii[k] = phii[k+1] + t*hkl,  phi[k] = (phis + phii[k+1]) + t*hkk;
+ *          phi[0] = (phis + phii[1]) + t*hkk  (no phii[0] is formed)
+ *   OMEGA  ckk = 0.5/p[k], ckl = 2*ckk, term = divdp[k]:
+ *          om[0] = vgrad_p[0]/p[0] - ckk*term,  s = term;   0 < k < n: om[k] = (vgrad_p[k]/p[k] - ckl*s) - ckk*term,  then s = s + term
+ * With p NULL, PHI and OMEGA use PMID's p, formed inside the kernel with PMID's roundings: PHI(p = NULL) has the bits of PMID followed by
+ * PHI(p = that output), and the pressure need never exist in memory.  With p given the host's own pressure is used (an Eulerian
+ * coordinate's p = hyam*ps0 + hybm*ps is no prefix sum).  Inputs are finite and pressures positive: a NaN propagates, nothing is checked
+ * on the device.
+ * VIEWS: every view takes its own path of tse_dss_view_plan with nf = 1 and nk = n, 1 (phis) or n + 1 (PINT's out; level-fastest it takes
+ * the generic path, as in tse_dss_view for nk != nlev).  An input may carry stride 0 on an axis of extent 1 only (so phis's level stride
+ * may be 0); out follows the rules of a get view (no zero stride on an extent above 1, no two index tuples on one address).  Only
+ * addresses of out are written, and out's footprint must not meet that of any input (refused by the plan when any pointer is given, and
+ * by the entry from the real addresses).  Inputs may lie in the library's own fields (tse_device_ptr: "dp3d", "ps_v", "omega_p", "divdp",
+ * ...), as in tse_stats_view; out may not lie in any allocation of the library.
+ * Refused, with nonzero, tse_last_error() and nothing enqueued: an op outside 0..3, a view against the table, a ptop that is not finite
+ * or is negative, an rgas that is not finite, and everything tse_view_put refuses of a view or a stream (memory that is not device memory
+ * of the context's device, a footprint that leaves its allocation, a stream that is being captured or belongs to another device).
+ * stream orders as in tse_view_put.  Not collective, no exchange.  Timer group "fieldcol", one launch per call. */
+#define TSE_COL_PINT  0   /* dp -> interface pressure, nlev + 1 levels */
+#define TSE_COL_PMID  1   /* dp -> mid-point pressure, nlev levels */
+#define TSE_COL_PHI   2   /* T_v, dp, phis [, p] -> geopotential at mid-points */
+#define TSE_COL_OMEGA 3   /* vgrad_p, divdp, dp | p -> omega / p at mid-points */
+int tse_column_view(tse_ctx *ctx, int op, double ptop, double rgas,
+                    const tse_view *dp, const tse_view *p, const tse_view *a, const tse_view *b,
+                    const tse_view *out, void *stream);
+/* the paths and footprints of dp ([0]), p ([1]), a ([2]), b ([3]) and out ([4]) and every refusal that needs no device, the overlap rule
+ * included when any pointer is non-null; an absent view gives path -1 and lo = hi = 0.  No context, no device. */
+int tse_column_view_plan(int nelemd, int op, const tse_view *dp, const tse_view *p, const tse_view *a,
+                         const tse_view *b, const tse_view *out, int path[5], long long lo[5], long long hi[5]);
+
 /* ---- the DCMIP error norms from element partials (test/dcmip1-1/dcmip1-1_error_norm_ng.ncl:39-77: the line L1 L2 Linf q_max q_min) ----
  * The norm line is four sums and four extrema over the unique GLL columns and the levels.  The device forms every ELEMENT's share over the
  * points that element owns, in one fixed order (csrc/tse_kernels.h: k_norm_partials) that depends on the element's own data alone; the host
@@ -555,7 +602,7 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), "fieldop" (tse_sphere_op_view: its stage kernel and the sum or copy kernel behind it), "fieldstats" (tse_stats_view: its one kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), "fieldop" (tse_sphere_op_view: its stage kernel and the sum or copy kernel behind it), "fieldstats" (tse_stats_view: its one kernel), "fieldcol" (tse_column_view: its one kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -10,11 +10,12 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libtransport_se_hip.so")
-SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_tables.cpp", "tse_views.cpp", "tse_kernels.h", "tse_device.h",
+SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_column.hip", "tse_tables.cpp", "tse_views.cpp", "tse_kernels.h", "tse_device.h",
                                              "tse_launch.h", "tse_layout.h", "tse_tables.h", "tse_views.h", "tse_remap_check.h")]
-# the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own;
+# the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own,
+# tse_column.hip why k_column_view has a code object of its own;
 # tse_tables.cpp and tse_views.cpp are host C++, which hipcc would otherwise compile as HIP)
-UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_tables.cpp", ["-x", "c++"]),
+UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_column.hip", []), ("tse_tables.cpp", ["-x", "c++"]),
          ("tse_views.cpp", ["-x", "c++"])]
 # -fno-honor-nans: value-preserving (no reassociation, no reciprocal tricks); it only lets the compiler drop the
 # v_max_f64 x,x "canonicalize" it otherwise puts in front of every fmin/fmax operand (6 per limiter iteration)
@@ -148,7 +149,8 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchr
            "tse_view_put", "tse_view_get", "tse_view_plan", "tse_apply_forcing", "tse_apply_forcing_host",
            "tse_remap_view", "tse_remap_view_status", "tse_remap_view_plan", "tse_dss_view", "tse_dss_view_plan",
            "tse_biharmonic_view", "tse_biharmonic_view_plan", "tse_vector_setup", "tse_vlaplace_view", "tse_vlaplace_view_plan",
-           "tse_sphere_op_view", "tse_sphere_op_view_plan", "tse_stats_view", "tse_stats_view_plan"]
+           "tse_sphere_op_view", "tse_sphere_op_view_plan", "tse_stats_view", "tse_stats_view_plan",
+           "tse_column_view", "tse_column_view_plan"]
 COMM_ID_BYTES = 128
 
 
@@ -248,6 +250,8 @@ def lib(path=None, nlev=None):
     L.tse_sphere_op_view_plan.argtypes = [i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(i * 2), C.POINTER(C.c_longlong * 2), C.POINTER(C.c_longlong * 2)]
     L.tse_stats_view.argtypes = [vp, i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(View), vp, vp]
     L.tse_stats_view_plan.argtypes = [i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(View), C.POINTER(i * 3), C.POINTER(C.c_longlong * 3), C.POINTER(C.c_longlong * 3)]
+    L.tse_column_view.argtypes = [vp, i, d, d] + [C.POINTER(View)] * 5 + [vp]
+    L.tse_column_view_plan.argtypes = [i, i] + [C.POINTER(View)] * 5 + [C.POINTER(i * 5), C.POINTER(C.c_longlong * 5), C.POINTER(C.c_longlong * 5)]
     if hasattr(L, "tse_test_dcmip_point"):   # the -DTSE_AB_HOOKS twin only (HipMod.test_dcmip_point)
         L.tse_test_dcmip_point.argtypes = [vp, i, d, vp, vp]
     _libs[path] = L

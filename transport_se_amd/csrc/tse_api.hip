@@ -2256,6 +2256,50 @@ int tse_stats_view(tse_ctx* c, int nf, int nk, int per_level, const tse_view* fi
   return 0;
 }
 
+// ---- pressure, geopotential and omega / p of a resident host's columns (k_column_view: tse_kernels.h) --------------------------------
+// The plans and the overlap rule are host code (tse_views.cpp: column_view_plan / column_view_overlap); here the checks that need the
+// runtime -- an input may lie inside an allocation of the library as in tse_stats_view, `out` may not (host_array_checks) -- the stream
+// order of tse_view_put and one launch on the compute stream (launch_column_view: the kernel's instantiations are tse_column.hip's).
+static_assert(COL_PINT == TSE_COL_PINT && COL_PMID == TSE_COL_PMID && COL_PHI == TSE_COL_PHI && COL_OMEGA == TSE_COL_OMEGA, "the ops of the header");
+int tse_column_view(tse_ctx* c, int op, double ptop, double rgas, const tse_view* dp, const tse_view* p, const tse_view* a, const tse_view* b, const tse_view* out,
+                    void* stream) {
+  const char* who = "tse_column_view";
+  if (!c) return fail("%s: null context", who);
+  ViewPlan pl[5];
+  { std::string err; if (column_view_plan(c->nelemd, op, dp, p, a, b, out, pl, &err)) return fail("%s", err.c_str()); }
+  if (!std::isfinite(ptop) || ptop < 0.0) return fail("%s: ptop = %g (the pressure at the model top: finite and not negative)", who, ptop);
+  if (!std::isfinite(rgas)) return fail("%s: rgas = %g is not finite", who, rgas);
+  const tse_view* v[5] = {dp, p, a, b, out};
+  const std::vector<void*> mine = device_allocations(c);
+  bool in_library = false;
+  const char* const role[4] = {"tse_column_view (dp)", "tse_column_view (p)", "tse_column_view (a)", "tse_column_view (b)"};   // the name a runtime refusal carries
+  for (int i = 0; i < 4; i++) {
+    if (!v[i]) continue;
+    void* alloc = nullptr;
+    if (view_runtime_checks(c, role[i], "field", pl[i], v[i], stream, &alloc)) return 1;
+    in_library = in_library || std::find(mine.begin(), mine.end(), alloc) != mine.end();
+  }
+  if (host_array_checks(c, {{who, "out", &pl[4], out}}, stream)) return 1;
+  { std::string err; if (column_view_overlap(v, pl, &err)) return fail("%s", err.c_str()); }
+  ColumnViewArgs ka;
+  for (int i = 0; i < 4; i++) {
+    ka.ptr[i] = v[i] ? (const double*)v[i]->ptr : nullptr;
+    ka.form[i] = v[i] ? stats_form(pl[i].path, view_wide(pl[i].path, v[i])) : STATS_POINTS;
+    for (int k = 0; k < 5; k++) ka.vs[i][k] = v[i] ? v[i]->stride[k] : 0;
+  }
+  ka.out = dss_view_args(1, pl[4].ext[2], out);
+  ka.ptop = ptop; ka.rgas = rgas;
+  hipStream_t us = (hipStream_t)stream;
+  if (order_in(c, us)) return 1;
+  if (in_library && join_inputs(c)) return 1;   // (a library field the auxiliary stream may still be writing)
+  {
+    Scope s(c, "fieldcol");
+    launch_column_view(c->stream, c->nelemd, op, p != nullptr, pl[4].path, view_wide(pl[4].path, out), ka, (double*)out->ptr);   // (tse_column.hip)
+    LAUNCH_CHECK();
+  }
+  return order_out(c, us);
+}
+
 // ---- introspection ------------------------------------------------------------------------------
 void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
   struct Ent { const char* n; void* p; size_t b; };

@@ -3594,4 +3594,176 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_stats_view(StatsViewArgs a, co
   }
 }
 
+// ---- pressure, geopotential and omega / p of a host's columns through strided views (tse_column_view) ------------------------------
+// The three vertical scans of the primitive equations, levels from 0 at the model top, n = NLEV (include/transport_se_hip.h states the
+// arithmetic; one rounded operation per sign, nothing contracted, tests/column_model.py follows the same lines):
+//   COL_PINT   pi[0] = ptop;  pi[k+1] = pi[k] + dp[k]
+//   COL_PMID   p[0] = ptop + dp[0]*0.5;  p[k] = (p[k-1] + dp[k-1]*0.5) + dp[k]*0.5
+//   COL_PHI    preq_hydrostatic: hkk = (dp*0.5)/p, hkl = 2*hkk, t = rgas*T_v;  phii[n-1] = t*hkl, phii[k] = phii[k+1] + t*hkl;
+//              phi[n-1] = phis + t*hkk, phi[k] = (phis + phii[k+1]) + t*hkk
+//   COL_OMEGA  preq_omega_ps: ckk = 0.5/p, ckl = 2*ckk;  om[0] = vgrad_p/p - ckk*divdp;  om[k] = (vgrad_p/p - ckl*s) - ckk*divdp with
+//              s = divdp[0] + ... + divdp[k-1] added ascending
+// PGIVEN: p is a view of the host's; otherwise PHI and OMEGA form PMID's p in LDS with PMID's roundings and it never reaches memory.
+//
+// block = element.  Each input slab enters an LDS image img[p][VIEW_PITCH] through the loader of its own path (stats_load_image and its
+// block-uniform `form`); phis, one level, goes to column NLEV + 1 of the third image.  The work is split by dependence:
+//   scans    lanes 0..15, one per point, walk the levels in the image: the additions of pi / p, of phii (upward from the bottom, in place
+//            over t*hkl) and of s (an exclusive prefix in place over divdp), eight LDS reads in flight (the rows are read in chunks);
+//   points   all 256 lanes, item = p * NLEV + k (consecutive lanes on consecutive doubles of a row: no bank conflict), before a scan the
+//            divisions and products -- t*hkl into the image, t*hkk, vgrad_p/p, ckl and ckk*divdp kept in registers across the barrier --
+//            and behind it the final combination into the image that leaves.
+// The result leaves through the store side of out's path <OPATH, OWIDE>: dss_tile_to_rows for level-fastest rows (n levels alone: the
+// n + 1 levels of PINT take the generic path, as tse_dss_view_plan says), lap_view_store_row for lines and points.
+// LDS: one image for PINT / PMID, three for PHI / OMEGA.
+constexpr int COL_PINT = 0, COL_PMID = 1, COL_PHI = 2, COL_OMEGA = 3;
+constexpr int COL_IMG = 16 * VIEW_PITCH, COL_NI = (16 * NLEV + VIEW_THREADS - 1) / VIEW_THREADS, COL_CHUNK = 8;
+struct ColumnViewArgs { const double* ptr[4]; long long vs[4][5]; int form[4]; DssViewArgs out; double ptop, rgas; };   // 0 dp, 1 p, 2 a, 3 b
+static_assert(3 * COL_IMG * sizeof(double) <= 64 * 1024, "the three images of PHI / OMEGA fit the static LDS of a block");
+static_assert(VIEW_PITCH >= NLEV + 2, "a row holds the n + 1 levels of PINT, and phis beside the n levels of T_v");
+static_assert(NLEV % COL_CHUNK == 0, "the scans read whole chunks");
+
+// row[k] = dp[k] -> row[k] = pi[k], k = 0..NLEV
+__device__ __forceinline__ void col_scan_pint(double* row, double ptop) {
+#pragma clang fp contract(off)
+  double s = ptop;
+  for (int k0 = 0; k0 < NLEV; k0 += COL_CHUNK) {
+    double d[COL_CHUNK];
+#pragma unroll
+    for (int u = 0; u < COL_CHUNK; u++) d[u] = row[k0 + u];
+#pragma unroll
+    for (int u = 0; u < COL_CHUNK; u++) { row[k0 + u] = s; s = s + d[u]; }
+  }
+  row[NLEV] = s;
+}
+// row[k] = dp[k] -> dst[k] = p[k]; dst may be row
+__device__ __forceinline__ void col_scan_pmid(const double* row, double* dst, double ptop) {
+#pragma clang fp contract(off)
+  double s = ptop, h = 0.0;
+  for (int k0 = 0; k0 < NLEV; k0 += COL_CHUNK) {
+    double d[COL_CHUNK];
+#pragma unroll
+    for (int u = 0; u < COL_CHUNK; u++) d[u] = row[k0 + u] * 0.5;
+#pragma unroll
+    for (int u = 0; u < COL_CHUNK; u++) {
+      s = (k0 + u == 0) ? s + d[u] : (s + h) + d[u];
+      h = d[u];
+      dst[k0 + u] = s;
+    }
+  }
+}
+// row[k] = t*hkl of level k -> row[k] = phii[k] for k = NLEV-1 .. 1 (row[0] keeps its product: no phii[0] is formed)
+__device__ __forceinline__ void col_scan_phii(double* row) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+  for (int k0 = NLEV - COL_CHUNK; k0 >= 0; k0 -= COL_CHUNK) {
+    double d[COL_CHUNK];
+#pragma unroll
+    for (int u = 0; u < COL_CHUNK; u++) d[u] = row[k0 + u];
+#pragma unroll
+    for (int u = COL_CHUNK - 1; u >= 0; u--) {
+      if (k0 + u == 0) break;
+      s = (k0 + u == NLEV - 1) ? d[u] : s + d[u];
+      row[k0 + u] = s;
+    }
+  }
+}
+// row[k] = divdp[k] -> row[k] = s of level k = divdp[0] + ... + divdp[k-1] for k = 1..NLEV-1 (row[0] is not used)
+__device__ __forceinline__ void col_scan_s(double* row) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+  for (int k0 = 0; k0 < NLEV; k0 += COL_CHUNK) {
+    double d[COL_CHUNK];
+#pragma unroll
+    for (int u = 0; u < COL_CHUNK; u++) d[u] = row[k0 + u];
+#pragma unroll
+    for (int u = 0; u < COL_CHUNK; u++) {
+      if (k0 + u > 0) row[k0 + u] = s;
+      if (k0 + u < NLEV - 1) s = (k0 + u == 0) ? d[u] : s + d[u];
+    }
+  }
+}
+
+template <int OP, bool PGIVEN, int OPATH, bool OWIDE>
+__global__ __launch_bounds__(VIEW_THREADS) void k_column_view(ColumnViewArgs a, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  static_assert(OP >= COL_PHI || !PGIVEN, "PINT and PMID take no p");
+  static_assert(OP != COL_PINT || OPATH != 1, "the n + 1 levels of PINT never take path 1");
+  constexpr int NIMG = OP <= COL_PMID ? 1 : 3, NKO = OP == COL_PINT ? NLEVP : NLEV, PHIS = NLEV + 1;
+  __shared__ __attribute__((aligned(16))) double img[NIMG * COL_IMG];
+  double* const I0 = img;                                   // PINT / PMID: dp -> the result;  PHI: dp -> t*hkl -> phii;  OMEGA: vgrad_p -> om
+  double* const I1 = img + (NIMG > 1 ? COL_IMG : 0);        // PHI: p -> phi;  OMEGA: p (or dp -> p)
+  double* const I2 = img + (NIMG > 1 ? 2 * COL_IMG : 0);    // PHI: T_v, phis in column PHIS;  OMEGA: divdp -> s
+  const int tid = threadIdx.x;
+  const long long e = blockIdx.x;
+  auto load = [&](int i, int nk, double* dst) { stats_load_image(a.ptr[i] + e * a.vs[i][0], a.vs[i], a.form[i], nk, dst, tid); };
+  double* row = nullptr;   // the row of a scanning lane
+  const bool scans = tid < 16;
+
+  if (OP <= COL_PMID) {
+    load(0, NLEV, I0);
+    __syncthreads();
+    if (scans) { row = I0 + tid * VIEW_PITCH; if (OP == COL_PINT) col_scan_pint(row, a.ptop); else col_scan_pmid(row, row, a.ptop); }
+  } else {
+    if (OP == COL_PHI) { load(0, NLEV, I0); if (PGIVEN) load(1, NLEV, I1); load(2, NLEV, I2); load(3, 1, I2 + PHIS); }
+    else { load(2, NLEV, I0); load(PGIVEN ? 1 : 0, NLEV, I1); load(3, NLEV, I2); }
+    __syncthreads();
+    if (!PGIVEN) {
+      if (scans) col_scan_pmid((OP == COL_PHI ? I0 : I1) + tid * VIEW_PITCH, I1 + tid * VIEW_PITCH, a.ptop);
+      __syncthreads();
+    }
+    // the independent part in front of the scan; x, y, z: PHI t*hkk | OMEGA vgrad_p/p, ckl, ckk*divdp
+    double x[COL_NI], y[COL_NI], z[COL_NI];
+#pragma unroll
+    for (int u = 0; u < COL_NI; u++) {
+      const int it = min(u * VIEW_THREADS + tid, 16 * NLEV - 1), idx = (it / NLEV) * VIEW_PITCH + it % NLEV;
+      const double p = I1[idx];
+      if (OP == COL_PHI) {
+        const double hkk = (I0[idx] * 0.5) / p, hkl = 2.0 * hkk, t = a.rgas * I2[idx];
+        x[u] = t * hkk; y[u] = t * hkl;
+      } else {
+        const double ckk = 0.5 / p;
+        x[u] = I0[idx] / p; y[u] = 2.0 * ckk; z[u] = ckk * I2[idx];
+      }
+    }
+    if (OP == COL_PHI) {
+#pragma unroll
+      for (int u = 0; u < COL_NI; u++) {
+        const int it = u * VIEW_THREADS + tid;
+        if (it < 16 * NLEV) I0[(it / NLEV) * VIEW_PITCH + it % NLEV] = y[u];
+      }
+    }
+    __syncthreads();
+    if (scans) { if (OP == COL_PHI) col_scan_phii(I0 + tid * VIEW_PITCH); else col_scan_s(I2 + tid * VIEW_PITCH); }
+    __syncthreads();
+    // the final combination: PHI into I1 (p is done with), OMEGA into I0 (vgrad_p is in x)
+#pragma unroll
+    for (int u = 0; u < COL_NI; u++) {
+      const int it = u * VIEW_THREADS + tid, pt = it / NLEV, k = it % NLEV, idx = pt * VIEW_PITCH + k;
+      if (it >= 16 * NLEV) continue;
+      if (OP == COL_PHI) {
+        const double phis = I2[pt * VIEW_PITCH + PHIS];
+        const double base = k == NLEV - 1 ? phis : phis + I0[idx + 1];
+        I1[idx] = base + x[u];
+      } else {
+        const double s = I2[idx];
+        I0[idx] = k == 0 ? x[u] - z[u] : (x[u] - y[u] * s) - z[u];
+      }
+    }
+  }
+  __syncthreads();
+
+  const double* O = OP == COL_PHI ? I1 : I0;
+  double* V = out + e * a.out.vs[0];
+  if (OPATH == 1) dss_tile_to_rows<OWIDE, NLEV>(O, V, a.out.vs[4], tid);
+  else {
+    for (int it = tid; it < 4 * NKO; it += VIEW_THREADS) {
+      const int j = it & 3, k = it >> 2;
+      double r[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) r[i] = O[(4 * j + i) * VIEW_PITCH + k];
+      lap_view_store_row<OPATH, OWIDE>(V + k * a.out.vs[2], a.out, j, r);
+    }
+  }
+}
+
 }  // namespace tse

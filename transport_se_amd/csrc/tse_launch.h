@@ -110,4 +110,20 @@ inline int stats_form(int path, bool wide) {
   return path == 0 && wide ? STATS_LINES_WIDE : STATS_POINTS;
 }
 
+// tse_column_view: (op, p is a view of the host's, path and view_wide of `out`) -> f(k_column_view instantiation).  The paths of the
+// inputs are no template parameters (stats_form, as in k_stats_view).  PINT's out has NLEVP levels and never takes path 1 (dss_view_plan).
+// Used by launch_column_view alone: the instantiations live in tse_column.hip, which says why.
+template <class F>
+inline void with_column_view(int op, bool pgiven, int path, bool wide, F&& f) {
+  with_view_path(path, wide, [&](auto pc, auto wc) {
+    constexpr int PATH = decltype(pc)::value;
+    constexpr bool W = decltype(wc)::value;
+    if (op == COL_PINT) { if constexpr (PATH != 1) f(k_column_view<COL_PINT, false, PATH, W>); }
+    else if (op == COL_PMID) f(k_column_view<COL_PMID, false, PATH, W>);
+    else if (op == COL_PHI) { if (pgiven) f(k_column_view<COL_PHI, true, PATH, W>); else f(k_column_view<COL_PHI, false, PATH, W>); }
+    else { if (pgiven) f(k_column_view<COL_OMEGA, true, PATH, W>); else f(k_column_view<COL_OMEGA, false, PATH, W>); }
+  });
+}
+void launch_column_view(hipStream_t stream, int nelemd, int op, bool pgiven, int path, bool wide, const ColumnViewArgs& a, double* out);
+
 }  // namespace tse

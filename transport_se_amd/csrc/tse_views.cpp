@@ -250,6 +250,49 @@ int stats_view_plan(int nelemd, int nf, int nk, const tse_view* field, const tse
   return 0;
 }
 
+// tse_column_view's up to five views -- dp, p, a, b, out -- each a view of tse_dss_view with one field: which of them the op needs, may
+// take or refuses (the table of the header), and the level count of each: NLEV, 1 for the surface view b of PHI (whose level stride is
+// not looked at), NLEVP for the out of PINT.  An absent view leaves path -1 and an empty footprint.
+static const char* const COLUMN_ROLE[5] = {"dp", "p", "a", "b", "out"};
+
+int column_view_plan(int nelemd, int op, const tse_view* dp, const tse_view* p, const tse_view* a, const tse_view* b, const tse_view* out_view, ViewPlan out[5],
+                     std::string* err) {
+  const char* who = "tse_column_view";
+  if (op < TSE_COL_PINT || op > TSE_COL_OMEGA)
+    return refuse(err, "%s: op=%d (0: interface pressure, 1: mid-point pressure, 2: geopotential, 3: omega / p)", who, op);
+  if (!out) return refuse(err, "%s: null plan", who);
+  const tse_view* v[5] = {dp, p, a, b, out_view};
+  // 1 needed, 0 must be null, 2 optional
+  const bool scan = op <= TSE_COL_PMID;
+  const int want[5] = {op == TSE_COL_OMEGA ? (p ? 0 : 1) : 1, scan ? 0 : 2, scan ? 0 : 1, scan ? 0 : 1, 1};
+  static const char* const opname[4] = {"TSE_COL_PINT", "TSE_COL_PMID", "TSE_COL_PHI", "TSE_COL_OMEGA"};
+  for (int i = 0; i < 5; i++) {
+    if (want[i] == 1 && !v[i]) return refuse(err, "%s: %s needs the view %s%s", who, opname[op], COLUMN_ROLE[i], op == TSE_COL_OMEGA && i == 0 ? " when p is null" : "");
+    if (want[i] == 0 && v[i]) return refuse(err, "%s: %s takes no view %s%s: pass null", who, opname[op], COLUMN_ROLE[i], op == TSE_COL_OMEGA && i == 0 ? " beside p" : "");
+  }
+  for (int i = 0; i < 5; i++) {
+    out[i] = ViewPlan();
+    out[i].path = -1;
+    if (!v[i]) continue;
+    const int nk = i == 4 && op == TSE_COL_PINT ? NLEVP : i == 3 && op == TSE_COL_PHI ? 1 : NLEV;
+    std::string e;
+    if (dss_view_plan(nelemd, 1, nk, v[i], &out[i], &e, who)) return refuse(err, "%s (%s)", e.c_str(), COLUMN_ROLE[i]);
+  }
+  return 0;
+}
+
+int column_view_overlap(const tse_view* const v[5], const ViewPlan plan[5], std::string* err) {
+  const __int128 g0 = (__int128)(uintptr_t)v[4]->ptr + (__int128)plan[4].lo * 8, g1 = (__int128)(uintptr_t)v[4]->ptr + (__int128)plan[4].hi * 8;
+  for (int i = 0; i < 4; i++) {
+    if (!v[i]) continue;
+    const __int128 f0 = (__int128)(uintptr_t)v[i]->ptr + (__int128)plan[i].lo * 8, f1 = (__int128)(uintptr_t)v[i]->ptr + (__int128)plan[i].hi * 8;
+    if (f0 < g1 && g0 < f1)
+      return refuse(err, "tse_column_view: out [%p%+lld, %p%+lld doubles) overlaps %s [%p%+lld, %p%+lld doubles): a column is read while it is written", v[4]->ptr,
+                    plan[4].lo, v[4]->ptr, plan[4].hi, COLUMN_ROLE[i], v[i]->ptr, plan[i].lo, v[i]->ptr, plan[i].hi);
+  }
+  return 0;
+}
+
 }  // namespace tse
 
 // the C plan entries: an error becomes the message of tse_last_error; n plans go out as path[] / lo[] / hi[], each of them optional
@@ -320,6 +363,19 @@ extern "C" int tse_stats_view_plan(int nelemd, int nf, int nk, const tse_view* f
   std::string err;
   if (tse::stats_view_plan(nelemd, nf, nk, field, ref, weight, p, &err)) return refused(err);
   return plans_out(p, 3, path, lo, hi);
+}
+
+extern "C" int tse_column_view_plan(int nelemd, int op, const tse_view* dp, const tse_view* p, const tse_view* a, const tse_view* b, const tse_view* out,
+                                    int path[5], long long lo[5], long long hi[5]) {
+  tse::ViewPlan pl[5];
+  std::string err;
+  if (tse::column_view_plan(nelemd, op, dp, p, a, b, out, pl, &err)) return refused(err);
+  // strides alone (every ptr null): nothing is known of where the views lie
+  const tse_view* v[5] = {dp, p, a, b, out};
+  bool placed = false;
+  for (const tse_view* x : v) placed = placed || (x && x->ptr);
+  if (placed && tse::column_view_overlap(v, pl, &err)) return refused(err);
+  return plans_out(pl, 5, path, lo, hi);
 }
 
 #ifdef TSE_AB_HOOKS

@@ -66,6 +66,14 @@ int sphere_op_view_overlap(const tse_view* in, const tse_view* out, const ViewPl
 // empty footprint.  No overlap rule: nothing is written through a view.
 int stats_view_plan(int nelemd, int nf, int nk, const tse_view* field, const tse_view* ref, const tse_view* weight, ViewPlan out[3], std::string* err);
 
+// The up to five views of tse_column_view / tse_column_view_plan -> out[0..4] = the plans of dp, p, a, b, out: each a view of tse_dss_view
+// with one field of NLEV levels, except b of TSE_COL_PHI (the surface field: one level) and out of TSE_COL_PINT (NLEVP).  Which views an
+// op needs, may take and refuses is the table of the header; an absent view: path -1 and an empty footprint.  column_view_overlap: the
+// footprint of out (v[4]), taken from its ptr, meets that of no input.
+int column_view_plan(int nelemd, int op, const tse_view* dp, const tse_view* p, const tse_view* a, const tse_view* b, const tse_view* out_view, ViewPlan out[5],
+                     std::string* err);
+int column_view_overlap(const tse_view* const v[5], const ViewPlan plan[5], std::string* err);
+
 // the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
 int set_last_error(const char* msg);
 

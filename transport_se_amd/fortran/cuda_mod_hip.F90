@@ -71,6 +71,9 @@ module cuda_mod
   ! min, max, sums and integrals of the host's own device-resident fields from element partials (tse_stats_view)
   public :: stats_view_hip
   integer, parameter, public :: tse_stats = 16   ! TSE_STATS
+  ! pressure, geopotential and omega / p of the host's own device-resident columns (tse_column_view)
+  public :: column_view_hip
+  integer, parameter, public :: col_pint = 0, col_pmid = 1, col_phi = 2, col_omega = 3   ! TSE_COL_PINT, TSE_COL_PMID, TSE_COL_PHI, TSE_COL_OMEGA
   logical, save :: remap_refused = .false.            ! remap_view_hip / remap_view_status_hip: the master thread's answer, read by every thread
   integer(c_int), save :: remap_nrefused = 0, remap_where(4) = 0
   real(kind=8), save :: t_res(3) = 0d0    ! 1 dcmip_init_hip, 2 prim_run_subcycle_hip, 3 copy_state_d2h_hip
@@ -238,6 +241,10 @@ module cuda_mod
      integer(c_int) function tse_stats_view(ctx, nf, nk, per_level, field, ref, weight, stream, out) bind(C, name='tse_stats_view')
        import; type(c_ptr), value :: ctx, ref, weight, stream, out; integer(c_int), value :: nf, nk, per_level
        type(tse_view), intent(in) :: field
+     end function
+     integer(c_int) function tse_column_view(ctx, op, ptop, rgas, dp, p, a, b, out, stream) bind(C, name='tse_column_view')
+       import; type(c_ptr), value :: ctx, dp, p, a, b, stream; integer(c_int), value :: op; real(c_double), value :: ptop, rgas
+       type(tse_view), intent(in) :: out
      end function
      ! HIP runtime (libamdhip64): staging copies of the packed slots for a non-GPU-aware MPI
      integer(c_int) function hipMemcpy(dst, src, nbytes, kind) bind(C, name='hipMemcpy')
@@ -945,6 +952,42 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine stats_view_hip
+
+  ! out at out_ptr <- one vertical scan of the host's DEVICE arrays, levels from 1 at the model top (include/transport_se_hip.h:
+  ! tse_column_view states the arithmetic):
+  !   col_pint   dp3d(:,:,1:nlev)                                  -> p_i(:,:,1:nlev+1), p_i(1) = ptop
+  !   col_pmid   dp3d(:,:,1:nlev)                                  -> p(:,:,1:nlev)
+  !   col_phi    a = T_v(:,:,1:nlev), b = phis(:,:), dp3d [, p]    -> phi(:,:,1:nlev)      preq_hydrostatic; rgas = Rgas
+  !   col_omega  a = vgrad_p(:,:,1:nlev), b = divdp(:,:,1:nlev), p or else dp3d -> omega_p(:,:,1:nlev)   preq_omega_ps
+  ! An absent view is c_null_ptr (its strides are not read): p, a and b of col_pint / col_pmid; p of col_phi and col_omega when the
+  ! mid-point pressure is to be formed from dp3d on the fly; dp of col_omega when p is given.  ptop = hvcoord%hyai(1) * hvcoord%ps0.
+  ! strides(1:5) in doubles for element, q, level, j, i; the q stride is never stepped, nor the level stride of phis:
+  ! state%dp3d(np,np,nlev,timelevels) at time level n0 is (/ s_e, 0, 16, 4, 1 /) from the address of dp3d(1,1,1,n0).  The inputs may be
+  ! the library's own fields; out may not, and may not overlap an input.  Not collective.  stream as in view_put_hip.  A refusal aborts.
+  subroutine column_view_hip(op, ptop, rgas, dp_ptr, dp_strides, p_ptr, p_strides, a_ptr, a_strides, b_ptr, b_strides, out_ptr, out_strides, stream)
+    integer,              intent(in) :: op
+    real(c_double),       intent(in) :: ptop, rgas
+    type(c_ptr),          intent(in) :: dp_ptr, p_ptr, a_ptr, b_ptr, out_ptr, stream
+    integer(c_long_long), intent(in) :: dp_strides(5), p_strides(5), a_strides(5), b_strides(5), out_strides(5)
+    type(tse_view), target :: vd, vp, va, vb
+    type(tse_view) :: vo
+    type(c_ptr) :: d, p, a, b
+    vd%ptr = dp_ptr; vd%stride = dp_strides
+    vp%ptr = p_ptr;  vp%stride = p_strides
+    va%ptr = a_ptr;  va%stride = a_strides
+    vb%ptr = b_ptr;  vb%stride = b_strides
+    vo%ptr = out_ptr; vo%stride = out_strides
+    d = c_null_ptr; p = c_null_ptr; a = c_null_ptr; b = c_null_ptr
+    if (c_associated(dp_ptr)) d = c_loc(vd)
+    if (c_associated(p_ptr)) p = c_loc(vp)
+    if (c_associated(a_ptr)) a = c_loc(va)
+    if (c_associated(b_ptr)) b = c_loc(vb)
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_column_view(ctx, int(op,c_int), ptop, rgas, d, p, a, b, vo, stream), 'column_view_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine column_view_hip
 
   ! out(:,:,1:nk,1:nf) at out_ptr <- laplace_sphere_wk of field(:,:,1:nk,1:nf) of the host's DEVICE array at ptr (order lap_order1: weak,
   ! not summed, no exchange) or laplace_sphere_wk(rspheremp * DSS(laplace_sphere_wk(field))) (lap_order2: biharmonic_wk_scalar before its

@@ -319,6 +319,32 @@ def stats_view_plan(nelemd, nf, nk, field, ref=None, weight=None, nlev=None):
     return [None if v[i] is None else dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(3)]
 
 
+COLUMN_OPS = {"pint": 0, "pmid": 1, "phi": 2, "omega": 3}   # TSE_COL_PINT, TSE_COL_PMID, TSE_COL_PHI, TSE_COL_OMEGA
+COLUMN_VIEWS = ("dp", "p", "a", "b", "out")
+
+
+def _column_op(op):
+    """the op names, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(op, str):
+        if op not in COLUMN_OPS:
+            raise TseError("column_view: unknown op %r (the ops are %s)" % (op, ", ".join(COLUMN_OPS)))
+        return COLUMN_OPS[op]
+    return int(op)
+
+
+def column_view_plan(nelemd, op, dp=None, p=None, a=None, b=None, out=None, nlev=None):
+    """tse_column_view_plan: dict(dp=, p=, a=, b=, out=) of dict(path=, lo=, hi=), None for an absent view -- each view a _lib.View, its
+    five strides (doubles, in the order of VIEW_AXES), or a pair (strides, address) so that the overlap rule is tested as well.  Needs no
+    device.  Raises TseError for views column_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    raw = lambda x: None if x is None else _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
+    v = [raw(x) for x in (dp, p, a, b, out)]
+    path, lo, hi = (C.c_int * 5)(), (C.c_longlong * 5)(), (C.c_longlong * 5)()
+    if L.tse_column_view_plan(int(nelemd), _column_op(op), *[None if x is None else C.byref(x) for x in v], C.byref(path), C.byref(lo), C.byref(hi)):
+        raise TseError(L.tse_last_error().decode())
+    return {n: None if v[i] is None else dict(path=path[i], lo=lo[i], hi=hi[i]) for i, n in enumerate(COLUMN_VIEWS)}
+
+
 class HipMod:
     def __init__(self, elem, deriv_Dvv, hvcoord, qsize, nu_q, limiter_option=8, rsplit=3, device=-1,
                  schedule=None, exchange=None, vert_remap_q_alg=0, lib_path=None, nlev=None):
@@ -828,6 +854,38 @@ class HipMod:
         self._chk(self.L.tse_stats_view(self.h, int(nf), int(nk), int(bool(per_level)), C.byref(vf), None if vr is None else C.byref(vr),
                                         None if vw is None else C.byref(vw), _stream_handle(stream), _vp(out)))
         return out
+
+    # ---- pressure, geopotential and omega / p of the host's columns (tse_column_view) ----
+    def column_view(self, op, dp=None, dp_axes="ekji", p=None, a=None, b=None, out=None, ptop=0.0, rgas=0.0, stream=None,
+                    p_axes=None, a_axes=None, b_axes=None, out_axes=None):
+        """out <- one vertical scan of the device arrays, op by name: "pint" (dp -> interface pressure, nlev + 1 levels), "pmid" (dp ->
+        mid-point pressure), "phi" (a = T_v, b = phis a surface field, dp and optionally p -> hydrostatic geopotential) or "omega"
+        (a = vgrad_p, b = divdp, and p or else dp -> omega / p); the header states the arithmetic.  With p=None "phi" and "omega" form
+        the mid-point pressure of "pmid" from dp on the fly; "omega" takes dp only then.  ptop = hyai(1) * ps0, rgas the gas constant of
+        "phi".  Every array names its axes over e k j i (`dp_axes`; the others default to it, `b_axes` of "phi" to it without k) and
+        may also be a ready _lib.View; inputs may be the library's own fields (device_ptr), out may not, and out may not overlap an
+        input.  Not collective.  stream orders as in put."""
+        who = "column_view"
+        o = _column_op(op)
+        nlev = self.nlev
+        surface = o == COLUMN_OPS["phi"]
+        want = dict(dp=nlev, p=nlev, a=nlev, b=1 if surface else nlev, out=nlev + 1 if o == COLUMN_OPS["pint"] else nlev)
+        axes = dict(dp=dp_axes, p=p_axes or dp_axes, a=a_axes or dp_axes, out=out_axes or dp_axes,
+                    b=b_axes or (str(dp_axes).replace("k", "") if surface else dp_axes))
+        views = {}
+        for name, x in (("dp", dp), ("p", p), ("a", a), ("b", b), ("out", out)):
+            if x is None or isinstance(x, _lib.View):
+                views[name] = x
+                continue
+            v, nf, nk = build_dss_view(x, axes[name], self.nelemd, who=who, written=name == "out")
+            if nf != 1:
+                raise TseError("%s: %s: a q axis of extent %d (one field per call)" % (who, name, nf))
+            if nk != want[name]:
+                raise TseError("%s: %s has %d levels, %s wants %d" % (who, name, nk, op, want[name]))
+            views[name] = v
+        ref = lambda x: None if x is None else C.byref(x)
+        self._chk(self.L.tse_column_view(self.h, o, float(ptop), float(rgas), ref(views["dp"]), ref(views["p"]), ref(views["a"]), ref(views["b"]),
+                                         ref(views["out"]), _stream_handle(stream)))
 
     def last_error(self):
         return self.L.tse_last_error().decode()
