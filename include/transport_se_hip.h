@@ -483,7 +483,7 @@ int tse_sphere_op_view_plan(int nelemd, int nk, int op, const tse_view *in, cons
  *   14 sum m (the area, or the mass when weight = dp)                 15 0
  * A NaN is skipped by the extrema (fmin / fmax): a slab of NaNs gives +inf, -inf for entries 0, 1 and 0 for 6, 12, 13; it does enter the
  * sums.  Where an extremum is zero and zeros of both signs occur, its sign is not specified.
- * THE ORDER OF ADDITION (csrc/tse_kernels.h: k_stats_view; tests/stats_model.py adds in the same one):
+ * THE ORDER OF ADDITION (csrc/tse_view_kernels.h: k_stats_view; tests/stats_model.py adds in the same one):
  *   level share L(k): the 16 terms of the slab, points in memory order p = 4j + i, as the pairwise tree
  *     (((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7))) + (((t8 + t9) + (t10 + t11)) + ((t12 + t13) + (t14 + t15)));
  *   element share (per_level = 0): S = L(0); S = S + L(1); ... ascending in k.  Extrema take the same route.
@@ -522,7 +522,7 @@ int tse_stats_view_plan(int nelemd, int nf, int nk, const tse_view *field, const
  * PHI and OMEGA with p given), rgas by PHI alone.  No library state is read or written: not the cached bounds, not the freshness of
  * q / lnps, not the prescribed-wind state.
  * THE ARITHMETIC: one rounded fp64 operation per arithmetic sign, left to right, nothing contracted; every / a true division; *0.5 and 2*
- * are exact (csrc/tse_kernels.h: k_column_view; tests/column_model.py follows the same lines).
+ * are exact (csrc/tse_view_kernels.h: k_column_view; tests/column_model.py follows the same lines).
  *   PINT   pi[0] = ptop;  pi[k+1] = pi[k] + dp[k]
  *   PMID   p[0] = ptop + dp[0]*0.5;  p[k] = (p[k-1] + dp[k-1]*0.5) + dp[k]*0.5        (E3SM: p(k) = p(k-1) + dp(k-1)/2 + dp(k)/2)
  *   PHI    hkk = (dp[k]*0.5)/p[k], hkl = 2*hkk, t = rgas*T_v[k]:

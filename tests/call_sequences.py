@@ -1,7 +1,7 @@
 """Call sequences against a fresh context: the harness and the vocabulary of tests/test_gpu_call_sequences.py.
 
 The property:  THE VISIBLE STATE AFTER A CALL, AND EVERYTHING THE CALL RETURNS, DEPEND ONLY ON THE VISIBLE STATE BEFORE IT, NEVER ON HOW THE
-CONTEXT GOT THERE.  tse_ctx (csrc/tse_api.hip) carries hidden state that decides what the next call launches -- the cached element bounds and
+CONTEXT GOT THERE.  tse_ctx (csrc/tse_ctx.h) carries hidden state that decides what the next call launches -- the cached element bounds and
 their prefetched halo, the freshness of Q / lnps, dcmip_static, a deferred final DSS, T's zero slots, the forked step inputs, the twin level
 buffers, the qmin/qmin2 swaps, the size of the view staging field (DESIGN.md section 5 tabulates who sets and who drops each) -- and every
 public entry has to set or drop the right subset.  replay() walks a sequence of calls on one warm context A and repeats every single call on a

@@ -1,4 +1,4 @@
-"""numpy model of the tracer forcing (tse_apply_forcing; csrc/tse_kernels.h: forcing_rule, k_forcing): the rule operation for operation, the
+"""numpy model of the tracer forcing (tse_apply_forcing; csrc/tse_view_kernels.h: forcing_rule, k_forcing): the rule operation for operation, the
 budget in THE ORDER of k_norm_partials, an exact referee for the budget's sums, and the generator of the fields the tests use.
 
 The rule, for every value of Qdp = Qdp(nt), each operation rounded once (numpy never contracts):

@@ -3,7 +3,7 @@ that follows from the order.  Plain numpy; no HIP import.
 
 Shapes: h, ht [E][nf][nk][4][4] (or [...][16]); w [E][nk][4][4]; spheremp [E][4][4].  Points in memory order p = 4j + i.
 
-THE ORDER (include/transport_se_hip.h, csrc/tse_kernels.h: k_stats_view):
+THE ORDER (include/transport_se_hip.h, csrc/tse_view_kernels.h: k_stats_view):
   level share   the 16 terms of a slab as the pairwise tree (((t0+t1)+(t2+t3))+((t4+t5)+(t6+t7))) + (the same of t8..t15): four pairwise
                 reshapes (tree16);
   element share S = L(0); S = S + L(1); ... ascending in k.

@@ -32,8 +32,8 @@ def test_the_80_level_library_builds_exports_every_symbol_and_reports_its_level_
         _lib._check_nlev(L80, so, 72)
 
 
-def _syntax_only(tmp_path, nlev):
-    src = os.path.join(ROOT, "transport_se_amd", "csrc", "tse_api.hip")
+def _syntax_only(tmp_path, nlev, unit="tse_api.hip"):
+    src = os.path.join(ROOT, "transport_se_amd", "csrc", unit)
     res = subprocess.run(["hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-DNLEV=%d" % nlev, src],
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=str(tmp_path), timeout=600)
     return res.returncode, res.stdout.decode()
@@ -47,8 +47,9 @@ def test_every_other_count_above_72_still_fails_to_compile(tmp_path, nlev):
 
 @pytest.mark.parametrize("nlev", [80, 72, 64])
 def test_the_built_counts_pass_the_rules(tmp_path, nlev):
-    rc, out = _syntax_only(tmp_path, nlev)
-    assert rc == 0 and "static assertion" not in out, out[-2000:]
+    for unit in ("tse_api.hip", "tse_views_api.hip"):   # (the view unit: the level rules of tse_view_kernels.h and tse_view_launch.h)
+        rc, out = _syntax_only(tmp_path, nlev, unit)
+        assert rc == 0 and "static assertion" not in out, (unit, out[-2000:])
 
 
 def test_the_80_level_fixtures_are_what_the_formula_gives():

@@ -122,10 +122,10 @@ def main():
              "levels = %d layers, %.3f GB" % (args.ne, n, nf, K, nf * K, nbytes / 1e9),
              "%s, torch %s; device events on a side stream, 3 warm-up rounds, window >= %.1f s of device time per kind; fieldlap: the two kernels "
              "of a call, mean of 20 calls" % (torch.cuda.get_device_name(0), torch.__version__, args.seconds),
-             "%-28s %-14s %6s %10s %10s %10s %8s %8s %12s" % ("layout", "kind", "calls", "mean ms", "min ms", "max ms", "x copy", "x dss", "fieldlap ms")]
+             "%-28s %-14s %6s %10s %10s %10s %10s %8s %8s %12s" % ("layout", "kind", "calls", "median ms", "mean ms", "min ms", "max ms", "x copy", "x dss", "fieldlap ms")]
     for k, v in times.items():
         dss = mean.get((k[0], "dss_view weak"))
-        lines.append("%-28s %-14s %6d %10.4f %10.4f %10.4f %8.3f %8s %12s" % (k[0], k[1], len(v), mean[k], min(v), max(v), mean[k] / base,
+        lines.append("%-28s %-14s %6d %10.4f %10.4f %10.4f %10.4f %8.3f %8s %12s" % (k[0], k[1], len(v), float(np.median(v)), mean[k], min(v), max(v), mean[k] / base,
                                                                              "%.3f" % (mean[k] / dss) if dss else "-", "%.4f" % group[k] if k in group else "-"))
     text = "\n".join(lines)
     print(text)

@@ -3,11 +3,13 @@
 
     python tools/kernel_digest.py transport_se_amd/libtransport_se_hip.so > table.txt
 
-A line is: the code object's index in the file (the translation units in link order: tse_api.hip, tse_stage3.hip, tse_column.hip), the kernel's symbol,
+A line is: the code object's index in the file (the translation units in link order: tse_api.hip, tse_stage3.hip, tse_column.hip,
+tse_views_api.hip -- units 0 and 1 are the tracer path, 2 and 3 the operators on a resident host's arrays), the kernel's symbol,
 the sha256 of its machine code (the bytes of the function symbol in .text) and its resource record from the code object's metadata note
 (VGPR, AGPR and SGPR counts, LDS, scratch, kernarg size, maximum workgroup size).  Two builds with the same table run the same device
 code with the same resources; the kernel descriptors are not compared, their entry offsets follow the layout of the code object.  A
-host-side change of the library must leave the table as it is: diff the tables of the two builds."""
+host-side change of the library must leave the table as it is: diff the tables of the two builds.  A change of the view kernels must leave
+units 0 and 1 as they are, a change of the path units 2 and 3 (profiles/view_unit_digests.txt: the comparison that split them)."""
 import hashlib
 import struct
 import sys

@@ -10,13 +10,15 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libtransport_se_hip.so")
-SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_column.hip", "tse_tables.cpp", "tse_views.cpp", "tse_kernels.h", "tse_device.h",
-                                             "tse_launch.h", "tse_layout.h", "tse_tables.h", "tse_views.h", "tse_remap_check.h")]
-# the translation units and the extra compiler flags of each (tse_stage3.hip says why it has a scheduler strategy of its own,
-# tse_column.hip why k_column_view has a code object of its own;
-# tse_tables.cpp and tse_views.cpp are host C++, which hipcc would otherwise compile as HIP)
-UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_column.hip", []), ("tse_tables.cpp", ["-x", "c++"]),
-         ("tse_views.cpp", ["-x", "c++"])]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("tse_api.hip", "tse_stage3.hip", "tse_column.hip", "tse_views_api.hip", "tse_tables.cpp", "tse_views.cpp", "tse_kernels.h",
+                                             "tse_view_kernels.h", "tse_device.h", "tse_ctx.h", "tse_launch.h", "tse_view_launch.h", "tse_layout.h", "tse_tables.h",
+                                             "tse_views.h", "tse_remap_check.h")]
+# the translation units in link order and the extra compiler flags of each.  The code objects of the library follow that order: the
+# tracer path (tse_api.hip; tse_stage3.hip says why it has a scheduler strategy of its own), then the operators on a resident host's
+# arrays (tse_column.hip says why k_column_view has a code object of its own; tse_views_api.hip, the other view kernels, comes last).
+# tse_tables.cpp and tse_views.cpp are host C++, which hipcc would otherwise compile as HIP
+UNITS = [("tse_api.hip", []), ("tse_stage3.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]), ("tse_column.hip", []), ("tse_views_api.hip", []),
+         ("tse_tables.cpp", ["-x", "c++"]), ("tse_views.cpp", ["-x", "c++"])]
 # -fno-honor-nans: value-preserving (no reassociation, no reciprocal tricks); it only lets the compiler drop the
 # v_max_f64 x,x "canonicalize" it otherwise puts in front of every fmin/fmax operand (6 per limiter iteration)
 CFLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-honor-nans", "-fPIC"]

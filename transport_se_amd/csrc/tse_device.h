@@ -173,7 +173,7 @@ __device__ __forceinline__ void laplace_lean_row(const Dvv_t& D, const LapGeo& L
 
 // vlaplace_sphere_wk_contra (derivative_mod.F90:2545-2591: the constant-coefficient vector Laplacian, grad_wk(nu_ratio * div) - curl_wk(vor)
 // + 2 * spheremp * v * rrearth^2) of v = (v1, v2) at the lane's 4 points.  The metric products are folded once per point into 14 tables
-// (k_vec_fold, tse_kernels.h; index a + 2b of a 2x2 entry (a,b) as in Fortran memory):
+// (k_vec_fold, tse_view_kernels.h; index a + 2b of a 2x2 entry (a,b) as in Fortran memory):
 //   gDi = rrearth * metdet * Dinv                 divergence_sphere's contravariant flux (:2364-2414)
 //   Dr  = rrearth * D                             vorticity_sphere's covariant components (:2250-2301: D^T v) and the contra -> lat/lon
 //                                                 map of curl_sphere_wk_testcov (:1703-1762)

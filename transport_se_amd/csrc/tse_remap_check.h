@@ -1,9 +1,9 @@
 // tse_remap_check.h -- the precondition of remap_Q_ppm's bracket search for ONE column, as one function for the host
-// (check_remap_grids, tse_tables.cpp) and the device (k_remap_view_check, tse_kernels.h).  No HIP include: a host C++ unit
+// (check_remap_grids, tse_tables.cpp) and the device (k_remap_view_check, tse_view_kernels.h).  No HIP include: a host C++ unit
 // compiles it as plain C++.  tse_tables.h says what is refused and why.
 #pragma once
 
-#if defined(__HIP__)   // compiled as HIP (tse_api.hip); a host C++ unit sees a plain inline function
+#if defined(__HIP__)   // compiled as HIP (the .hip units); a host C++ unit sees a plain inline function
 #define TSE_HOST_DEVICE __host__ __device__
 #else
 #define TSE_HOST_DEVICE

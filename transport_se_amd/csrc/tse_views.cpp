@@ -134,10 +134,8 @@ int remap_view_overlap(const tse_view* field, const tse_view* dp_src, const tse_
   const char* who = "tse_remap_view";
   const tse_view* v[3] = {field, dp_src, dp_tgt};
   const char* name[3] = {"field", "dp_src", "dp_tgt"};
-  const __int128 f0 = (__int128)(uintptr_t)field->ptr + (__int128)out[0].lo * 8, f1 = (__int128)(uintptr_t)field->ptr + (__int128)out[0].hi * 8;
   for (int i = 1; i < 3; i++) {
-    const __int128 g0 = (__int128)(uintptr_t)v[i]->ptr + (__int128)out[i].lo * 8, g1 = (__int128)(uintptr_t)v[i]->ptr + (__int128)out[i].hi * 8;
-    if (f0 < g1 && g0 < f1)
+    if (Footprint(field, out[0]).meets(Footprint(v[i], out[i])))
       return refuse(err, "%s: the field [%p%+lld, %p%+lld doubles) overlaps %s [%p%+lld, %p%+lld doubles): it is remapped in place while the grids are read", who,
                     field->ptr, out[0].lo, field->ptr, out[0].hi, name[i], v[i]->ptr, out[i].lo, v[i]->ptr, out[i].hi);
   }
@@ -188,9 +186,7 @@ bool biharmonic_view_in_place(const tse_view* in, const tse_view* out) {
 
 int biharmonic_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err, const char* who) {
   if (biharmonic_view_in_place(in, out)) return 0;
-  const __int128 f0 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].lo * 8, f1 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].hi * 8;
-  const __int128 g0 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].lo * 8, g1 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].hi * 8;
-  if (f0 < g1 && g0 < f1)
+  if (Footprint(in, plan[0]).meets(Footprint(out, plan[1])))
     return refuse(err, "%s: out [%p%+lld, %p%+lld doubles) overlaps in [%p%+lld, %p%+lld doubles) without being the same view (the same "
                   "pointer and strides: in place)", who, out->ptr, plan[1].lo, out->ptr, plan[1].hi, in->ptr, plan[0].lo, in->ptr, plan[0].hi);
   return 0;
@@ -224,9 +220,7 @@ int sphere_op_view_plan(int nelemd, int nk, int op, const tse_view* in, const ts
 }
 
 int sphere_op_view_overlap(const tse_view* in, const tse_view* out, const ViewPlan plan[2], std::string* err) {
-  const __int128 f0 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].lo * 8, f1 = (__int128)(uintptr_t)in->ptr + (__int128)plan[0].hi * 8;
-  const __int128 g0 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].lo * 8, g1 = (__int128)(uintptr_t)out->ptr + (__int128)plan[1].hi * 8;
-  if (f0 < g1 && g0 < f1)
+  if (Footprint(in, plan[0]).meets(Footprint(out, plan[1])))
     return refuse(err, "tse_sphere_op_view: out [%p%+lld, %p%+lld doubles) overlaps in [%p%+lld, %p%+lld doubles): the shapes differ, there is no in-place form",
                   out->ptr, plan[1].lo, out->ptr, plan[1].hi, in->ptr, plan[0].lo, in->ptr, plan[0].hi);
   return 0;
@@ -282,11 +276,9 @@ int column_view_plan(int nelemd, int op, const tse_view* dp, const tse_view* p, 
 }
 
 int column_view_overlap(const tse_view* const v[5], const ViewPlan plan[5], std::string* err) {
-  const __int128 g0 = (__int128)(uintptr_t)v[4]->ptr + (__int128)plan[4].lo * 8, g1 = (__int128)(uintptr_t)v[4]->ptr + (__int128)plan[4].hi * 8;
   for (int i = 0; i < 4; i++) {
     if (!v[i]) continue;
-    const __int128 f0 = (__int128)(uintptr_t)v[i]->ptr + (__int128)plan[i].lo * 8, f1 = (__int128)(uintptr_t)v[i]->ptr + (__int128)plan[i].hi * 8;
-    if (f0 < g1 && g0 < f1)
+    if (Footprint(v[i], plan[i]).meets(Footprint(v[4], plan[4])))
       return refuse(err, "tse_column_view: out [%p%+lld, %p%+lld doubles) overlaps %s [%p%+lld, %p%+lld doubles): a column is read while it is written", v[4]->ptr,
                     plan[4].lo, v[4]->ptr, plan[4].hi, COLUMN_ROLE[i], v[i]->ptr, plan[i].lo, v[i]->ptr, plan[i].hi);
   }

@@ -1,8 +1,9 @@
 // tse_views.h -- the descriptor logic of the strided device views (tse_view_put / tse_view_get / tse_view_plan): which fields a view may
 // name in which direction, their extents and their dense internal layout, the conversion path a set of strides takes, its footprint and
-// the overlap test of a destination view.  Plain host C++ (tse_views.cpp: no HIP header); tse_api.hip adds the checks that need the
-// device and launches the kernels of tse_kernels.h.
+// the overlap test of a destination view.  Plain host C++ (tse_views.cpp: no HIP header); tse_views_api.hip adds the checks that need the
+// device and launches the kernels of tse_view_kernels.h.
 #pragma once
+#include <cstdint>
 #include <string>
 
 #include "../../include/transport_se_hip.h"
@@ -21,10 +22,20 @@ struct ViewPlan {
   long long lo = 0, hi = 0;   // footprint [lo, hi) of the view in doubles relative to ptr
 };
 
+// The addresses a view or a dense range may touch, [lo, hi) in bytes: a view's are its ptr and the footprint of its plan, in 128 bits (a
+// stride may carry the sum below zero or past 2^64).  The one statement of "meets" and "inside" for every overlap and allocation rule.
+struct Footprint {
+  __int128 lo, hi;
+  Footprint(const tse_view* v, const ViewPlan& p) : lo((__int128)(uintptr_t)v->ptr + (__int128)p.lo * 8), hi((__int128)(uintptr_t)v->ptr + (__int128)p.hi * 8) {}
+  Footprint(const void* base, size_t bytes) : lo((__int128)(uintptr_t)base), hi(lo + (__int128)bytes) {}
+  bool meets(const Footprint& o) const { return lo < o.hi && o.lo < hi; }   // (touching is disjoint)
+  bool inside(const Footprint& o) const { return lo >= o.lo && hi <= o.hi; }
+};
+
 // Whether a kernel may move 16 bytes per lane on the view side: on path 0 the double2 parts of every (e, q, k) slab, on path 1 the level
 // pairs of every row of every (e, q) tile.  The base 16-byte aligned, the element and q strides even, and the stride between the units
 // even: the level stride on path 0, the i stride (the pitch of the rows) on path 1.  Never on path 2.  The one statement of the rule:
-// every launch of a kernel with a WIDE parameter asks here (tse_launch.h: with_view_path).  It does not see the extents, so it also
+// every launch of a kernel with a WIDE parameter asks here (tse_view_launch.h: with_view_path).  It does not see the extents, so it also
 // refuses a view whose only odd stride belongs to an axis of extent 1.
 bool view_wide(int path, const tse_view* v);
 
@@ -74,7 +85,7 @@ int column_view_plan(int nelemd, int op, const tse_view* dp, const tse_view* p, 
                      std::string* err);
 int column_view_overlap(const tse_view* const v[5], const ViewPlan plan[5], std::string* err);
 
-// the message of tse_last_error (tse_api.hip), for the C entries defined outside that unit
+// the message of tse_last_error, for the C entries of this host C++ unit: a call of tse::fail (tse_ctx.h; defined in tse_api.hip)
 int set_last_error(const char* msg);
 
 }  // namespace tse
