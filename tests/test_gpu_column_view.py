@@ -19,15 +19,32 @@ import pytest
 
 import column_model as cm
 import dss_view_model as dm
+import view_common as vc
 from stats_layouts import Strided, layout
-from test_gpu_dss_view import _Fake, _hip, _make, _oracle, _raw
+from view_common import FakeArray as _Fake, raw_field as _raw
 
 pytestmark = pytest.mark.gpu
+QSIZE = 2
 NE = 2
 LAYOUTS = ("dense", "dense_odd8", "dense_odd_e", "dense_odd_k", "lev0", "lev_even", "lev_odd", "ij")
 INPUTS = ("dense", "lev0", "lev_even", "ij", "lev_odd", "dense_odd_k")     # role r of out layout i takes INPUTS[(i + r) % 6]: mixed pairs
 ROLES = ("dp", "p", "tv", "phis", "vgrad_p", "divdp")
 SENTINEL = -7.25e33
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(ne):
+    return vc.oracle(ne, QSIZE)
+
+
+def _make(ne, nlev=72):
+    return vc.make_hip(_oracle(ne), QSIZE, nlev)
+
+
+@functools.lru_cache(maxsize=None)
+def _hip(ne, nlev=72):
+    """a context of qsize 2 on the oracle's mesh (kept for the session: contexts are small)"""
+    return _make(ne, nlev)
 
 
 @functools.lru_cache(maxsize=None)
@@ -327,13 +344,8 @@ def test_streams_and_refusals():
 
     def view(strides, ptr):
         return _lib.View(ptr, (C.c_longlong * 5)(*strides))
-    hiprt = C.CDLL("libamdhip64.so")
-    raw, nraw = C.c_void_p(), host.size * 8
-    assert hiprt.hipMalloc(C.byref(raw), C.c_size_t(nraw)) == 0
-    abase, asize = C.c_void_p(), C.c_size_t()
-    assert hiprt.hipMemGetAddressRange(C.byref(abase), C.byref(asize), raw) == 0
-    assert abase.value == raw.value and asize.value >= nraw and asize.value % 8 == 0
-    beyond = abase.value + asize.value - nraw + 8
+    raw = vc.RawAllocation(host.size * 8)
+    beyond = raw.beyond
     dense, surf = [plane, 0, 16, 4, 1], [16, 0, 0, 4, 1]
     vd, vo, vt, vs = view(dense, buf.data_ptr()), view(dense, out.data_ptr()), view(dense, tv.data_ptr()), view(surf, phis.data_ptr())
     rawcall = lambda op, ptop_, rgas_, *v: h._chk(h.L.tse_column_view(h.h, op, ptop_, rgas_, *[None if x is None else C.byref(x) for x in v], None))
@@ -373,25 +385,18 @@ def test_streams_and_refusals():
         assert h.kernel_time("fieldcol")[1] == 0, text
     # a stream that is being captured
     torch.cuda.synchronize()
-    assert hiprt.hipStreamBeginCapture(C.c_void_p(s.cuda_stream), C.c_int(2)) == 0     # hipStreamCaptureModeRelaxed
-    try:
+    with vc.capturing(s):
         with pytest.raises(TseError, match="captured"):
             h.column_view("pmid", dp=buf, out=out, ptop=ptop, stream=s)
-    finally:
-        graph = C.c_void_p()
-        assert hiprt.hipStreamEndCapture(C.c_void_p(s.cuda_stream), C.byref(graph)) == 0
-        if graph.value:
-            hiprt.hipGraphDestroy(graph)
     assert h.kernel_time("fieldcol")[1] == 0
     assert torch.equal(buf.view(torch.int64), keep.view(torch.int64))
     # out that fits its allocation exactly is served
-    h.column_view("pmid", dp=buf, out=_Fake(host.shape, dense[:1] + dense[2:], raw.value), ptop=ptop)
-    back = np.empty_like(host)
+    h.column_view("pmid", dp=buf, out=_Fake(host.shape, dense[:1] + dense[2:], raw.ptr), ptop=ptop)
     h.synchronize()
-    assert hiprt.hipMemcpy(C.c_void_p(back.ctypes.data), raw, C.c_size_t(nraw), C.c_int(2)) == 0
+    back = raw.read(host.shape)
     assert cm.same(back, want) and h.kernel_time("fieldcol")[1] == 1
     h.timing(False)
-    assert hiprt.hipFree(raw) == 0
+    raw.free()
 
 
 def _true_fma(a, b, c):

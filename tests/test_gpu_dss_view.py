@@ -20,42 +20,21 @@ import numpy as np
 import pytest
 
 import dss_view_model as dm
+import view_common as vc
+from view_common import FakeArray as _Fake, raw_field as _raw
 
 pytestmark = pytest.mark.gpu
 QSIZE = 2
 
 
-class _Fake:
-    def __init__(self, shape, strides_doubles, ptr):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f8", data=(int(ptr), False), strides=tuple(8 * s for s in strides_doubles),
-                                             version=3)
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(ne):
-    import pyoracle as po
-    return po.Oracle(ne, QSIZE, nu_q=1e19)
+    return vc.oracle(ne, QSIZE)
 
 
 def _make(ne, nlev=72, weights=None):
     """weights: (spheremp, rspheremp) in place of the mesh's own"""
-    from gpu_common import elem_from_oracle
-    from transport_se_amd.hip_mod import HipMod
-    o = _oracle(ne)
-    if nlev == 72:
-        hv = (o.hyai, o.hybi, 1.0e5)
-    else:
-        import remap_ld
-        if nlev == 80:
-            import nlev80_common  # noqa: F401  (teaches remap_ld the 80-level grid)
-        v = remap_ld.hvcoord(nlev)
-        hv = (v.hyai, v.hybi, v.ps0)
-    elem = elem_from_oracle(o)
-    if weights is not None:
-        elem["spheremp"], elem["rspheremp"] = np.ascontiguousarray(weights[0]), np.ascontiguousarray(weights[1])
-    h = HipMod(elem, o.Dvv, hv, QSIZE, 1e19, device=0, nlev=nlev)
-    assert h.nlev == nlev and h.nelemd == o.nelem
-    return h
+    return vc.make_hip(_oracle(ne), QSIZE, nlev, weights=weights)
 
 
 @functools.lru_cache(maxsize=None)
@@ -170,14 +149,6 @@ LIB_FIELDS = ("qdp1", "qdp2", "dp", "divdp", "divdp_proj", "dp3d", "ps_v", "qmin
 GROUPS = ("dss", "view", "level", "fieldremap", "remap", "advance", "minmax")
 
 
-def _raw(h, name):
-    p, nbytes = h.device_ptr(name)
-    out = np.empty(nbytes // 8)
-    h.synchronize()
-    assert C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(p), C.c_size_t(nbytes), C.c_int(2)) == 0
-    return out
-
-
 def test_the_library_is_untouched():
     ne, nlev, dt = 2, 72, 1800.0
     o = _oracle(ne)
@@ -252,17 +223,10 @@ def test_stream_order_and_capture():
     # a stream that is being captured
     h.timing(True)
     keep = ref.clone()
-    hiprt = C.CDLL("libamdhip64.so")
     torch.cuda.synchronize()
-    assert hiprt.hipStreamBeginCapture(C.c_void_p(s.cuda_stream), C.c_int(2)) == 0     # hipStreamCaptureModeRelaxed
-    try:
+    with vc.capturing(s):
         with pytest.raises(TseError, match="captured"):
             h.dss_view(ref, "eqjik", stream=s)
-    finally:
-        graph = C.c_void_p()
-        assert hiprt.hipStreamEndCapture(C.c_void_p(s.cuda_stream), C.byref(graph)) == 0
-        if graph.value:
-            hiprt.hipGraphDestroy(graph)
     assert h.kernel_time("fielddss")[1] == 0
     h.timing(False)
     assert torch.equal(ref.view(torch.int64), keep.view(torch.int64))
@@ -327,19 +291,8 @@ def test_refusals_launch_nothing():
     assert nbytes == E * QSIZE * plane * 8
     # an allocation of the field's size made with the runtime itself, and the range the runtime reports for it (it may round the size
     # up): a view of the field's shape that ends one double beyond that range is refused, the one at the allocation's start is served
-    hiprt = C.CDLL("libamdhip64.so")
-    raw, nraw = C.c_void_p(), f.size * 8
-    assert hiprt.hipMalloc(C.byref(raw), C.c_size_t(nraw)) == 0
-    assert hiprt.hipMemcpy(raw, C.c_void_p(host.ctypes.data), C.c_size_t(nraw), C.c_int(1)) == 0
-    abase, asize = C.c_void_p(), C.c_size_t()
-    assert hiprt.hipMemGetAddressRange(C.byref(abase), C.byref(asize), raw) == 0
-    assert abase.value == raw.value and asize.value >= nraw and asize.value % 8 == 0
-    beyond = abase.value + asize.value - nraw + 8
-
-    def raw_now():
-        out = np.empty(f.shape)
-        assert hiprt.hipMemcpy(C.c_void_p(out.ctypes.data), raw, C.c_size_t(nraw), C.c_int(2)) == 0
-        return out
+    raw = vc.RawAllocation(f.size * 8, fill=host)
+    beyond, raw_now = raw.beyond, lambda: raw.read(f.shape)
     cases = [
         ("device", lambda: h.dss_view(_Fake(f.shape, dense, host.ctypes.data), "eqkji")),
         ("outside its allocation", lambda: h.dss_view(_Fake(f.shape, dense, beyond), "eqkji")),                        # one double beyond
@@ -364,7 +317,7 @@ def test_refusals_launch_nothing():
     assert L.tse_dss_view(h.h, nf, nlev, 0, None, None) != 0 and b"null" in L.tse_last_error()
     h.dss_view(buf, "eqkji")
     assert h.kernel_time("fielddss")[1] == 2 and dm.same(buf.cpu().numpy(), want)
-    h.dss_view(_Fake(f.shape, dense, raw.value), "eqkji")                      # the view that fits exactly is served
+    h.dss_view(_Fake(f.shape, dense, raw.ptr), "eqkji")                        # the view that fits exactly is served
     assert dm.same(raw_now(), want)
     h.timing(False)
-    assert hiprt.hipFree(raw) == 0
+    raw.free()

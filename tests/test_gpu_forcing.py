@@ -16,7 +16,9 @@ import numpy as np
 import pytest
 
 import forcing_model as fm
+import view_common
 import view_model as vm
+from view_common import FakeArray as _Fake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VC = os.path.join(ROOT, "tests", "golden", "vcoord")
@@ -33,13 +35,6 @@ def _bits(x):
 
 def _same(a, b):
     return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-class _Fake:
-    """a device array described by hand: an address inside a real tensor with strides (in doubles) of our choosing"""
-    def __init__(self, shape, strides_doubles, ptr):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f8", data=(int(ptr), False), strides=tuple(8 * s for s in strides_doubles),
-                                             version=3)
 
 
 def _hv(nlev):
@@ -419,18 +414,11 @@ def test_stream_contract(ctx):
     torch.cuda.synchronize()
     assert _same(ctx.qdp(1), res["new"]) and not src.any().item()
 
-    hiprt = C.CDLL("libamdhip64.so")
     before = ctx.qdp(1)
     torch.cuda.synchronize()
-    assert hiprt.hipStreamBeginCapture(C.c_void_p(s.cuda_stream), C.c_int(2)) == 0     # hipStreamCaptureModeRelaxed
-    try:
+    with view_common.capturing(s):
         with pytest.raises(TseError, match="captured"):
             hip.apply_forcing(src, "eqjik", 1, dt=case.dt, stream=s)
-    finally:
-        graph = C.c_void_p()
-        assert hiprt.hipStreamEndCapture(C.c_void_p(s.cuda_stream), C.byref(graph)) == 0
-        if graph.value:
-            hiprt.hipGraphDestroy(graph)
     assert _same(ctx.qdp(1), before)
 
 

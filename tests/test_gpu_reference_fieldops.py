@@ -15,17 +15,12 @@ import dss_view_model as dm
 import elem_ops_ld as ld
 import fieldops_ref as fr
 from conftest import record_margin
+from view_common import FakeArray as _Fake
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -7.25
 LAYOUTS = ("dense", "lev_even")          # point-fastest; level-fastest (rows of levels, padded to an even pitch)
 KEYS = tuple(fr.cases(dict(nu_ratio=(1.0, 2.5))))
-
-
-class _Fake:
-    def __init__(self, shape, strides_doubles, ptr):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f8", data=(int(ptr), False), strides=tuple(8 * s for s in strides_doubles),
-                                             version=3)
 
 
 @pytest.fixture(scope="module")

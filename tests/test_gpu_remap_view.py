@@ -20,6 +20,9 @@ import functools
 import numpy as np
 import pytest
 
+import view_common as vc
+from view_common import FakeArray as _Fake, raw_field as _raw
+
 pytestmark = pytest.mark.gpu
 NLEVS = (72, 64, 80)
 PAYLOAD = 0x7FF8DEAD00000000   # quiet NaNs that carry their own index
@@ -72,12 +75,6 @@ def _ref(nlev, alg, nf):
     out = h.remap_q_ppm(Q, dp1, dp2)
     out.setflags(write=False)
     return out
-
-
-class _Fake:
-    def __init__(self, shape, strides_doubles, ptr):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f8", data=(int(ptr), False), strides=tuple(8 * s for s in strides_doubles),
-                                             version=3)
 
 
 # ---- layouts: (strides of e, q, k, j, i; base; size) in doubles for a field of nf slots; nf = 0: a grid (no q axis) ----
@@ -252,14 +249,6 @@ def test_mean_mode(nlev):
 LIB_FIELDS = ("qdp1", "qdp2", "dp", "divdp", "divdp_proj", "dp3d", "ps_v", "qmin", "qmax")
 
 
-def _raw(h, name):
-    p, nbytes = h.device_ptr(name)
-    out = np.empty(nbytes // 8)
-    h.synchronize()
-    assert C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(p), C.c_size_t(nbytes), C.c_int(2)) == 0
-    return out
-
-
 def _state_after_one_step(h, dt=1800.0):
     from transport_se_amd import cube_mesh as cm
     geo = cm.geometry(2, cm.topology(2))
@@ -384,17 +373,10 @@ def test_refusals_launch_nothing():
     assert L.tse_remap_view(None, nf, 0, 0, None, None, None, None) != 0 and b"null" in L.tse_last_error()
     # a stream that is being captured
     s = torch.cuda.Stream()
-    hiprt = C.CDLL("libamdhip64.so")
     torch.cuda.synchronize()
-    assert hiprt.hipStreamBeginCapture(C.c_void_p(s.cuda_stream), C.c_int(2)) == 0     # hipStreamCaptureModeRelaxed
-    try:
+    with vc.capturing(s):
         with pytest.raises(TseError, match="captured"):
             h.remap_view(*F.args(), *S.args(), *T.args(), stream=s)
-    finally:
-        graph = C.c_void_p()
-        assert hiprt.hipStreamEndCapture(C.c_void_p(s.cuda_stream), C.byref(graph)) == 0
-        if graph.value:
-            hiprt.hipGraphDestroy(graph)
     assert h.kernel_time("fieldremap")[1] == n0 and h.kernel_time("remap")[1] == 0
     h.timing(False)
     assert torch.equal(F.buf.view(torch.int64), after.view(torch.int64)) and _same(F.result(), _ref(nlev, 0, nf))

@@ -24,6 +24,8 @@ import pytest
 
 import dss_view_model as dm
 import sphere_ops_model as sm
+import view_common as vc
+from view_common import FakeArray as _Fake, raw_field as _raw
 
 pytestmark = pytest.mark.gpu
 QSIZE = 2
@@ -31,12 +33,6 @@ NE = 2
 LAUNCHES = 2   # per call, either mode: k_sphere_op_stage, then k_dss_view_sum (C0) or k_lap_view_out<., ., 1> (LOCAL)
 SENTINEL = -7.25
 MODES = (False, True)
-
-
-class _Fake:
-    def __init__(self, shape, strides_doubles, ptr):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f8", data=(int(ptr), False), strides=tuple(8 * s for s in strides_doubles),
-                                             version=3)
 
 
 def layout(name, E, nf, nk):
@@ -75,8 +71,7 @@ class Strided(dm.Strided):
 
 @functools.lru_cache(maxsize=None)
 def _oracle(ne=NE):
-    import pyoracle as po
-    return po.Oracle(ne, QSIZE, nu_q=1e19)
+    return vc.oracle(ne, QSIZE)
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,22 +81,7 @@ def _host(ne=NE):
 
 
 def _make(nlev=72, setup=True, ne=NE):
-    from gpu_common import elem_from_oracle
-    from transport_se_amd.hip_mod import HipMod
-    o = _oracle(ne)
-    if nlev == 72:
-        hv = (o.hyai, o.hybi, 1.0e5)
-    else:
-        import remap_ld
-        if nlev == 80:
-            import nlev80_common  # noqa: F401  (teaches remap_ld the 80-level grid)
-        v = remap_ld.hvcoord(nlev)
-        hv = (v.hyai, v.hybi, v.ps0)
-    h = HipMod(elem_from_oracle(o), o.Dvv, hv, QSIZE, 1e19, device=0, nlev=nlev)
-    assert h.nlev == nlev and h.nelemd == o.nelem
-    if setup:
-        h.vector_setup(*_host(ne))
-    return h
+    return vc.make_hip(_oracle(ne), QSIZE, nlev, setup=_host(ne) if setup else None)
 
 
 @functools.lru_cache(maxsize=None)
@@ -283,15 +263,6 @@ def test_other_level_counts(nlev):
 GROUPS = ("dss", "lap", "view", "level", "fielddss", "fieldlap", "fieldvlap", "fieldremap", "remap", "advance", "minmax", "forcing", "stateq")
 
 
-def _raw(h, name):
-    p, nbytes = h.device_ptr(name)
-    assert p and nbytes, name
-    out = np.empty(nbytes // 8)
-    h.synchronize()
-    assert C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(p), C.c_size_t(nbytes), C.c_int(2)) == 0
-    return out
-
-
 def test_the_library_is_untouched():
     import call_sequences as cs
     nlev, dt = 72, 1800.0
@@ -369,17 +340,10 @@ def test_stream_order_and_capture():
     # a stream that is being captured
     h.timing(True)
     keep = ref.clone()
-    hiprt = C.CDLL("libamdhip64.so")
     torch.cuda.synchronize()
-    assert hiprt.hipStreamBeginCapture(C.c_void_p(s.cuda_stream), C.c_int(2)) == 0     # hipStreamCaptureModeRelaxed
-    try:
+    with vc.capturing(s):
         with pytest.raises(TseError, match="captured"):
             h.sphere_op_view(src, "eqjik", ref, "ejik", op="vorticity", c0=True, stream=s)
-    finally:
-        graph = C.c_void_p()
-        assert hiprt.hipStreamEndCapture(C.c_void_p(s.cuda_stream), C.byref(graph)) == 0
-        if graph.value:
-            hiprt.hipGraphDestroy(graph)
     assert h.kernel_time("fieldop")[1] == 0
     h.timing(False)
     assert torch.equal(ref.view(torch.int64), keep.view(torch.int64))

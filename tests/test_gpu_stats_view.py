@@ -18,10 +18,30 @@ import pytest
 
 import dss_view_model as dm
 import stats_model as sm
-from test_gpu_dss_view import _Fake, _hip, _make, _oracle, _raw
+import view_common as vc
+from view_common import FakeArray as _Fake, raw_field as _raw
 
 pytestmark = pytest.mark.gpu
 QSIZE = 2
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(ne):
+    return vc.oracle(ne, QSIZE)
+
+
+def _make(ne, nlev=72, weights=None):
+    """weights: (spheremp, rspheremp) in place of the mesh's own"""
+    return vc.make_hip(_oracle(ne), QSIZE, nlev, weights=weights)
+
+
+@functools.lru_cache(maxsize=None)
+def _hip(ne, nlev=72):
+    """a context of qsize 2 on the oracle's mesh (kept for the session: contexts are small)"""
+    return _make(ne, nlev)
+
+
+
 # the layouts of dss_view_model -- point-fastest wide (dense) and narrow by its base (dense_odd8: 8 but not 16 bytes aligned), level-fastest
 # unpadded (lev0), padded to an even pitch (lev_even) and to an odd one (lev_odd: narrow rows), a generic view (ij) -- and two point-fastest
 # layouts that are narrow by ONE ODD STRIDE (stats_layouts: dense_odd_e the element stride, dense_odd_k the level stride)
@@ -312,21 +332,15 @@ def test_streams_and_refusals():
 
     def view(strides, ptr):
         return _lib.View(ptr, (C.c_longlong * 5)(*strides))
-    hiprt = C.CDLL("libamdhip64.so")
-    raw, nraw = C.c_void_p(), hh.size * 8
-    assert hiprt.hipMalloc(C.byref(raw), C.c_size_t(nraw)) == 0
-    assert hiprt.hipMemcpy(raw, C.c_void_p(host.ctypes.data), C.c_size_t(nraw), C.c_int(1)) == 0
-    abase, asize = C.c_void_p(), C.c_size_t()
-    assert hiprt.hipMemGetAddressRange(C.byref(abase), C.byref(asize), raw) == 0
-    assert abase.value == raw.value and asize.value >= nraw and asize.value % 8 == 0
-    beyond = abase.value + asize.value - nraw + 8
+    raw = vc.RawAllocation(hh.size * 8, fill=host)
+    beyond = raw.beyond
     fv = view(dense, buf.data_ptr())
     out = np.zeros((E, nf, 16))
     cases = [
         ("device", lambda: h.stats_view(_Fake(hh.shape, dense, host.ctypes.data), "eqkji")),
         (r"\(ref\).*device", lambda: h.stats_view(buf, "eqkji", ref=_Fake(hh.shape, dense, host.ctypes.data))),
         (r"\(field\).*outside its allocation", lambda: h.stats_view(_Fake(hh.shape, dense, beyond), "eqkji")),
-        (r"\(weight\).*outside its allocation", lambda: h.stats_view(buf, "eqkji", weight=_Fake(w.shape, [plane, 16, 4, 1], abase.value + asize.value - w.nbytes + 8),
+        (r"\(weight\).*outside its allocation", lambda: h.stats_view(buf, "eqkji", weight=_Fake(w.shape, [plane, 16, 4, 1], raw.end - w.nbytes + 8),
                                                         weight_axes="ekji")),
         ("per_level=2", lambda: h._chk(h.L.tse_stats_view(h.h, nf, nlev, 2, C.byref(fv), None, None, None, out.ctypes.data))),
         ("null out", lambda: h._chk(h.L.tse_stats_view(h.h, nf, nlev, 0, C.byref(fv), None, None, None, None))),
@@ -346,21 +360,15 @@ def test_streams_and_refusals():
         assert h.kernel_time("fieldstats")[1] == 0, text
     # a stream that is being captured
     torch.cuda.synchronize()
-    assert hiprt.hipStreamBeginCapture(C.c_void_p(s.cuda_stream), C.c_int(2)) == 0     # hipStreamCaptureModeRelaxed
-    try:
+    with vc.capturing(s):
         with pytest.raises(TseError, match="captured"):
             h.stats_view(buf, "eqkji", stream=s)
-    finally:
-        graph = C.c_void_p()
-        assert hiprt.hipStreamEndCapture(C.c_void_p(s.cuda_stream), C.byref(graph)) == 0
-        if graph.value:
-            hiprt.hipGraphDestroy(graph)
     assert h.kernel_time("fieldstats")[1] == 0
     assert torch.equal(buf.view(torch.int64), keep.view(torch.int64))
     # the view that fits its allocation exactly is served
-    assert sm.same(h.stats_view(_Fake(hh.shape, dense, raw.value), "eqkji"), want) and h.kernel_time("fieldstats")[1] == 1
+    assert sm.same(h.stats_view(_Fake(hh.shape, dense, raw.ptr), "eqkji"), want) and h.kernel_time("fieldstats")[1] == 1
     h.timing(False)
-    assert hiprt.hipFree(raw) == 0
+    raw.free()
 
 
 def test_a_stream_of_another_device_is_refused():

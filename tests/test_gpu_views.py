@@ -14,7 +14,9 @@ import sys
 import numpy as np
 import pytest
 
+import view_common
 import view_model as vm
+from view_common import FakeArray as _Fake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VC = os.path.join(ROOT, "tests", "golden", "vcoord")
@@ -398,21 +400,14 @@ def test_stream_contract(ctx):
     want = np.ascontiguousarray(np.moveaxis(expect, -1, -3))
     assert _same(sync, want) and _same(side, sync)
 
-    hiprt = C.CDLL("libamdhip64.so")
     s = torch.cuda.Stream()
     t = torch.zeros((n, qs, 72, 4, 4), dtype=torch.float64, device="cuda")
     torch.cuda.synchronize()
     before = hip.fetch("qdp1", (n, qs, 72, 4, 4))
-    assert hiprt.hipStreamBeginCapture(C.c_void_p(s.cuda_stream), C.c_int(2)) == 0     # hipStreamCaptureModeRelaxed
-    try:
+    with view_common.capturing(s):
         for call in (hip.put, hip.get):
             with pytest.raises(TseError, match="captured"):
                 call("qdp", t, "eqkji", nt=1, stream=s)
-    finally:
-        graph = C.c_void_p()
-        assert hiprt.hipStreamEndCapture(C.c_void_p(s.cuda_stream), C.byref(graph)) == 0
-        if graph.value:
-            hiprt.hipGraphDestroy(graph)
     assert _same(hip.fetch("qdp1", (n, qs, 72, 4, 4)), before) and not t.any().item()
 
 
@@ -439,13 +434,6 @@ def test_views_at_other_level_counts(nlev):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-class _Fake:
-    """a device array described by hand: the pointer of a real tensor with strides of our choosing"""
-    def __init__(self, shape, strides_doubles, ptr):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f8", data=(int(ptr), False), strides=tuple(8 * s for s in strides_doubles),
-                                             version=3)
-
-
 def test_refusals_launch_nothing(ctx):
     """7: every refused call leaves the launch count of the "view" group and the library's fields as they were"""
     import torch

@@ -36,6 +36,19 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _ref(v):
+    return None if v is None else C.byref(v)
+
+
+def _named(who, kind, plural, table, value):
+    """`value` by its name in `table`, or the header's integer as it is (the library refuses one it does not know)"""
+    if isinstance(value, str):
+        if value not in table:
+            raise TseError("%s: unknown %s %r (the %s are %s)" % (who, kind, value, plural, ", ".join(table)))
+        return table[value]
+    return int(value)
+
+
 # ---- strided device views (tse_view_put / tse_view_get / tse_view_plan) ----
 VIEW_AXES = "eqkji"   # the axis letters, in the order of tse_view.stride: element, q (tracer / wind component), level, j, i
 # field: (its axes, extent of q, level extent for put, for get) -- "q": qsize, "n": nlev, "p": nlev + 1, None: not served in that direction;
@@ -46,6 +59,48 @@ VIEW_FIELDS = {
     "divdp_proj": ("ekji", 1, "n", "n"), "dp3d": ("ekji", 1, None, "n"), "ps_v": ("eji", 1, None, 1), "q": ("eqkji", "q", None, "n"),
     "lnps": ("eji", 1, None, 1),
 }
+
+
+def _describe(who, array, axes, no_interface, check_axes, read_only, want, of=""):
+    """The description step of build_view and build_dss_view: (_lib.View, {axis letter: extent}) of `array`, whose dimensions the letters
+    of `axes` name in order.  In this order it refuses: an array without __cuda_array_interface__ (`no_interface`: the words after
+    "needed"), an unknown or repeated letter, what check_axes(axes) refuses, an element type other than <f8, a rank that is not the
+    number of letters, a read-only array (`read_only`: the whole message, None where the array is only read), and then axis by axis an
+    extent other than `want` has for that letter (`of`: what the message says after the letter) and a byte stride that is no multiple
+    of 8.  An array that gives no strides is C-contiguous."""
+    cai = getattr(array, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TseError("%s: the array has no __cuda_array_interface__ (a device array is needed%s)" % (who, no_interface))
+    axes = str(axes)
+    for a in axes:
+        if a not in VIEW_AXES:
+            raise TseError("%s: unknown axis letter %r in %r (the letters are %s)" % (who, a, axes, " ".join(VIEW_AXES)))
+        if axes.count(a) > 1:
+            raise TseError("%s: axis %r appears twice in %r" % (who, a, axes))
+    check_axes(axes)
+    if cai["typestr"] != "<f8":
+        raise TseError("%s: element type %s, the library moves <f8 only" % (who, cai["typestr"]))
+    shape = tuple(int(x) for x in cai["shape"])
+    if len(shape) != len(axes):
+        raise TseError("%s: %d axes named for an array of %d dimensions" % (who, len(axes), len(shape)))
+    ptr, readonly = cai["data"]
+    if readonly and read_only:
+        raise TseError(read_only)
+    strides = cai.get("strides")
+    if strides is None:   # C-contiguous
+        strides, acc = [], 8
+        for n in reversed(shape):
+            strides.insert(0, acc); acc *= n
+    v, ext = _lib.View(), {}
+    v.ptr = int(ptr)
+    for a, n, sb in zip(axes, shape, strides):
+        if a in want and n != want[a]:
+            raise TseError("%s: axis %r%s has extent %d, the array has %d" % (who, a, of, want[a], n))
+        if int(sb) % 8:
+            raise TseError("%s: the byte stride %d of axis %r is not a multiple of 8" % (who, sb, a))
+        ext[a] = n
+        v.stride[VIEW_AXES.index(a)] = int(sb) // 8
+    return v, ext
 
 
 def build_view(field, array, axes, nelemd, qsize, nlev, for_get=False):
@@ -60,40 +115,35 @@ def build_view(field, array, axes, nelemd, qsize, nlev, for_get=False):
     lev = lev_get if for_get else lev_put
     if lev is None:
         raise TseError("%s: field %r cannot be %s through a view" % (who, field, "read" if for_get else "written"))
-    cai = getattr(array, "__cuda_array_interface__", None)
-    if cai is None:
-        raise TseError("%s: the array has no __cuda_array_interface__ (a device array is needed; host arrays go through the copy entries)" % who)
-    axes = str(axes)
-    for a in axes:
-        if a not in VIEW_AXES:
-            raise TseError("%s: unknown axis letter %r in %r (the letters are %s)" % (who, a, axes, " ".join(VIEW_AXES)))
-        if axes.count(a) > 1:
-            raise TseError("%s: axis %r appears twice in %r" % (who, a, axes))
-    if sorted(axes) != sorted(f_axes):
-        raise TseError("%s: field %r has the axes %r, the array is described as %r" % (who, field, f_axes, axes))
-    if cai["typestr"] != "<f8":
-        raise TseError("%s: element type %s, the library moves <f8 only" % (who, cai["typestr"]))
-    shape = tuple(int(x) for x in cai["shape"])
-    if len(shape) != len(axes):
-        raise TseError("%s: %d axes named for an array of %d dimensions" % (who, len(axes), len(shape)))
-    ptr, readonly = cai["data"]
-    if for_get and readonly:
-        raise TseError("get: the destination array is read-only")
-    strides = cai.get("strides")
-    if strides is None:   # C-contiguous
-        strides, acc = [], 8
-        for n in reversed(shape):
-            strides.insert(0, acc); acc *= n
+
+    def the_fields(axes):
+        if sorted(axes) != sorted(f_axes):
+            raise TseError("%s: field %r has the axes %r, the array is described as %r" % (who, field, f_axes, axes))
     want = dict(e=nelemd, q=qsize if qext == "q" else qext, k={"n": nlev, "p": nlev + 1, 1: 1}[lev], j=NP, i=NP)
-    v = _lib.View()
-    v.ptr = int(ptr)
-    for a, n, sb in zip(axes, shape, strides):
-        if n != want[a]:
-            raise TseError("%s: axis %r of field %r has extent %d, the array has %d" % (who, a, field, want[a], n))
-        if int(sb) % 8:
-            raise TseError("%s: the byte stride %d of axis %r is not a multiple of 8" % (who, sb, a))
-        v.stride[VIEW_AXES.index(a)] = int(sb) // 8
-    return v
+    return _describe(who, array, axes, "; host arrays go through the copy entries", the_fields,
+                     "get: the destination array is read-only" if for_get else None, want, " of field %r" % field)[0]
+
+
+def _as_view(x, ptr=None):
+    """a view argument of the plan functions -> _lib.View or None: a ready _lib.View, its five strides (doubles, in the order of
+    VIEW_AXES), a pair (strides, address), or None for an absent view"""
+    if x is None or isinstance(x, _lib.View):
+        return x
+    if isinstance(x, tuple) and len(x) == 2:
+        return _as_view(*x)
+    return _lib.View(ptr, (C.c_longlong * 5)(*[int(s) for s in x]))
+
+
+def _plan(L, fn, lead, views, tail=()):
+    """one tse_*_view_plan call: fn(the integers `lead`, the views, the integers `tail`, path, lo, hi) -> [dict(path=, lo=, hi=) of each
+    view, None for an absent one]; raises TseError with the library's message"""
+    v = [_as_view(x) for x in views]
+    n = len(v)
+    out = (C.c_int * n)(), (C.c_longlong * n)(), (C.c_longlong * n)()
+    # (the entries of one view take plain pointers, the others pointers to arrays of n)
+    if fn(*[int(x) for x in lead], *[_ref(x) for x in v], *[int(x) for x in tail], *[a if n == 1 else C.byref(a) for a in out]):
+        raise TseError(L.tse_last_error().decode())
+    return [None if v[i] is None else dict(path=out[0][i], lo=out[1][i], hi=out[2][i]) for i in range(n)]
 
 
 def view_plan(field, nelemd, qsize, strides, for_get=False, nlev=None):
@@ -101,11 +151,7 @@ def view_plan(field, nelemd, qsize, strides, for_get=False, nlev=None):
     (0 point-fastest, 1 level-fastest, 2 generic) and its footprint [lo, hi) in doubles relative to the view's pointer.  Needs no device.
     Raises TseError for a view put / get would refuse."""
     L = _lib.lib(nlev=nlev)
-    v = strides if isinstance(strides, _lib.View) else _lib.View(None, (C.c_longlong * 5)(*[int(x) for x in strides]))
-    path, lo, hi = C.c_int(), C.c_longlong(), C.c_longlong()
-    if L.tse_view_plan(field.encode(), int(nelemd), int(qsize), C.byref(v), int(bool(for_get)), C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return dict(path=path.value, lo=lo.value, hi=hi.value)
+    return _plan(L, lambda *a: L.tse_view_plan(field.encode(), *a), (nelemd, qsize), [strides], (bool(for_get),))[0]
 
 
 def _stream_handle(stream):
@@ -115,56 +161,17 @@ def _stream_handle(stream):
     return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
 
 
-FORCING_MODES = {"tendency": 0, "adjust": 1}   # TSE_FORCING_TENDENCY, TSE_FORCING_ADJUST
-
-
-def _forcing_mode(mode):
-    """the mode names, or the header's integer as it is (the library refuses one it does not know)"""
-    if isinstance(mode, str):
-        if mode not in FORCING_MODES:
-            raise TseError("apply_forcing: unknown mode %r (the modes are %s)" % (mode, ", ".join(FORCING_MODES)))
-        return FORCING_MODES[mode]
-    return int(mode)
-
-
-REMAP_MODES = {"mass": 0, "mean": 1}   # TSE_REMAP_MASS, TSE_REMAP_MEAN
-
-
-def _remap_mode(mode):
-    """the mode names, or the header's integer as it is (the library refuses one it does not know)"""
-    if isinstance(mode, str):
-        if mode not in REMAP_MODES:
-            raise TseError("remap_view: unknown mode %r (the modes are %s)" % (mode, ", ".join(REMAP_MODES)))
-        return REMAP_MODES[mode]
-    return int(mode)
-
-
-def _raw_view(strides, ptr=None):
-    return strides if isinstance(strides, _lib.View) else _lib.View(ptr, (C.c_longlong * 5)(*[int(x) for x in strides]))
-
-
-def remap_view_plan(nelemd, nf, field, dp_src, dp_tgt, nlev=None):
-    """tse_remap_view_plan: [dict(path=, lo=, hi=)] of the three views of HipMod.remap_view -- field, dp_src, dp_tgt, each a _lib.View or
-    its five strides (doubles, in the order of VIEW_AXES), or a pair (strides, offset in bytes into one common allocation) so that the
-    overlap of the field with a grid is tested as well.  Needs no device.  Raises TseError for views remap_view would refuse."""
-    L = _lib.lib(nlev=nlev)
-    v = [_raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x) for x in (field, dp_src, dp_tgt)]
-    path, lo, hi = (C.c_int * 3)(), (C.c_longlong * 3)(), (C.c_longlong * 3)()
-    if L.tse_remap_view_plan(int(nelemd), int(nf), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(3)]
-
-
-DSS_MODES = {"average": 0, "weak": 1}   # TSE_DSS_AVERAGE, TSE_DSS_WEAK
-
-
-def _dss_mode(mode):
-    """the mode names, or the header's integer as it is (the library refuses one it does not know)"""
-    if isinstance(mode, str):
-        if mode not in DSS_MODES:
-            raise TseError("dss_view: unknown mode %r (the modes are %s)" % (mode, ", ".join(DSS_MODES)))
-        return DSS_MODES[mode]
-    return int(mode)
+# the names of the header's integers: a mode, order or op may be given by name or as the integer itself (_named)
+FORCING_MODES = {"tendency": 0, "adjust": 1}                    # TSE_FORCING_TENDENCY, TSE_FORCING_ADJUST
+REMAP_MODES = {"mass": 0, "mean": 1}                            # TSE_REMAP_MASS, TSE_REMAP_MEAN
+DSS_MODES = {"average": 0, "weak": 1}                           # TSE_DSS_AVERAGE, TSE_DSS_WEAK
+LAP_ORDERS = {"laplace": 1, "biharmonic": 2}                    # TSE_LAPLACE, TSE_BIHARMONIC
+VLAP_ORDERS = {"vlaplace": 1, "vbiharmonic": 2}                 # TSE_VLAPLACE, TSE_VBIHARMONIC
+SPHERE_OPS = {"gradient": 0, "divergence": 1, "vorticity": 2}   # TSE_OP_GRADIENT, TSE_OP_DIVERGENCE, TSE_OP_VORTICITY
+SPHERE_OP_FIELDS = {0: (1, 2), 1: (2, 1), 2: (2, 1)}            # op -> (fields of in, fields of out)
+COLUMN_OPS = {"pint": 0, "pmid": 1, "phi": 2, "omega": 3}       # TSE_COL_PINT, TSE_COL_PMID, TSE_COL_PHI, TSE_COL_OMEGA
+COLUMN_VIEWS = ("dp", "p", "a", "b", "out")
+STATS = 16   # TSE_STATS: doubles per share of HipMod.stats_view
 
 
 def build_dss_view(array, axes, nelemd, who="dss_view", written=True):
@@ -172,93 +179,38 @@ def build_dss_view(array, axes, nelemd, who="dss_view", written=True):
     letters of `axes` over e q k j i; e, j and i are needed, a missing q or k letter means extent 1 and stride 0; nf and nk are the
     array's own extents.  Raises TseError as build_view does.  The device is not touched.  who: the call the messages name;
     written=False: an array that is only read may be read-only."""
-    cai = getattr(array, "__cuda_array_interface__", None)
-    if cai is None:
-        raise TseError("%s: the array has no __cuda_array_interface__ (a device array is needed)" % who)
-    axes = str(axes)
-    for a in axes:
-        if a not in VIEW_AXES:
-            raise TseError("%s: unknown axis letter %r in %r (the letters are %s)" % (who, a, axes, " ".join(VIEW_AXES)))
-        if axes.count(a) > 1:
-            raise TseError("%s: axis %r appears twice in %r" % (who, a, axes))
-    for a in "eji":
-        if a not in axes:
-            raise TseError("%s: the axes %r lack %r" % (who, axes, a))
-    if cai["typestr"] != "<f8":
-        raise TseError("%s: element type %s, the library moves <f8 only" % (who, cai["typestr"]))
-    shape = tuple(int(x) for x in cai["shape"])
-    if len(shape) != len(axes):
-        raise TseError("%s: %d axes named for an array of %d dimensions" % (who, len(axes), len(shape)))
-    ptr, readonly = cai["data"]
-    if readonly and written:
-        raise TseError("%s: the array is read-only and would be written in place" % who)
-    strides = cai.get("strides")
-    if strides is None:   # C-contiguous
-        strides, acc = [], 8
-        for n in reversed(shape):
-            strides.insert(0, acc); acc *= n
-    want = dict(e=nelemd, j=NP, i=NP)
-    ext = dict(q=1, k=1)
-    v = _lib.View()
-    v.ptr = int(ptr)
-    for a, n, sb in zip(axes, shape, strides):
-        if a in want and n != want[a]:
-            raise TseError("%s: axis %r has extent %d, the array has %d" % (who, a, want[a], n))
-        if int(sb) % 8:
-            raise TseError("%s: the byte stride %d of axis %r is not a multiple of 8" % (who, sb, a))
-        ext[a] = n
-        v.stride[VIEW_AXES.index(a)] = int(sb) // 8
-    return v, ext["q"], ext["k"]
+    def e_j_and_i(axes):
+        for a in "eji":
+            if a not in axes:
+                raise TseError("%s: the axes %r lack %r" % (who, axes, a))
+    v, ext = _describe(who, array, axes, "", e_j_and_i, "%s: the array is read-only and would be written in place" % who if written else None,
+                       dict(e=nelemd, j=NP, i=NP))
+    return v, ext.get("q", 1), ext.get("k", 1)
+
+
+# ---- the plans of the view entries; _as_view names the forms a view may be given in ----
+def remap_view_plan(nelemd, nf, field, dp_src, dp_tgt, nlev=None):
+    """tse_remap_view_plan: [dict(path=, lo=, hi=)] of the three views of HipMod.remap_view -- field, dp_src, dp_tgt, each in a form
+    _as_view takes; the address of a pair is an offset in bytes into one common allocation, so that the overlap of the field with a grid
+    is tested as well.  Needs no device.  Raises TseError for views remap_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    return _plan(L, L.tse_remap_view_plan, (nelemd, nf), (field, dp_src, dp_tgt))
 
 
 def dss_view_plan(nelemd, nf, nk, field, nlev=None):
-    """tse_dss_view_plan: dict(path=, lo=, hi=) of the view HipMod.dss_view would be given -- `field` a _lib.View or its five strides
-    (doubles, in the order of VIEW_AXES).  Needs no device.  Raises TseError for a view dss_view would refuse."""
+    """tse_dss_view_plan: dict(path=, lo=, hi=) of the view HipMod.dss_view would be given, `field` in a form _as_view takes.  Needs no
+    device.  Raises TseError for a view dss_view would refuse."""
     L = _lib.lib(nlev=nlev)
-    path, lo, hi = C.c_int(), C.c_longlong(), C.c_longlong()
-    v = None if field is None else C.byref(_raw_view(field))
-    if L.tse_dss_view_plan(int(nelemd), int(nf), int(nk), v, C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return dict(path=path.value, lo=lo.value, hi=hi.value)
-
-
-LAP_ORDERS = {"laplace": 1, "biharmonic": 2}   # TSE_LAPLACE, TSE_BIHARMONIC
-
-
-def _lap_order(order):
-    """the order names, or the header's integer as it is (the library refuses one it does not know)"""
-    if isinstance(order, str):
-        if order not in LAP_ORDERS:
-            raise TseError("biharmonic_view: unknown order %r (the orders are %s)" % (order, ", ".join(LAP_ORDERS)))
-        return LAP_ORDERS[order]
-    return int(order)
+    return _plan(L, L.tse_dss_view_plan, (nelemd, nf, nk), [field])[0]
 
 
 def biharmonic_view_plan(nelemd, nf, nk, field, out=None, nlev=None):
-    """tse_biharmonic_view_plan: [dict(path=, lo=, hi=)] of the two views of HipMod.biharmonic_view, in and out -- each a _lib.View, its
-    five strides (doubles, in the order of VIEW_AXES), or a pair (strides, address) so that the overlap rule is tested as well; out=None:
-    in place (the same view).  Needs no device.  Raises TseError for views biharmonic_view would refuse."""
+    """tse_biharmonic_view_plan: [dict(path=, lo=, hi=)] of the two views of HipMod.biharmonic_view, in and out, each in a form
+    _as_view takes (a pair: so that the overlap rule is tested as well); out=None: in place (the same view).  Needs no device.  Raises
+    TseError for views biharmonic_view would refuse."""
     L = _lib.lib(nlev=nlev)
-    raw = lambda x: _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
-    vi = None if field is None else raw(field)
-    vo = vi if out is None else raw(out)
-    path, lo, hi = (C.c_int * 2)(), (C.c_longlong * 2)(), (C.c_longlong * 2)()
-    if L.tse_biharmonic_view_plan(int(nelemd), int(nf), int(nk), None if vi is None else C.byref(vi), None if vo is None else C.byref(vo),
-                                  C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
-
-
-VLAP_ORDERS = {"vlaplace": 1, "vbiharmonic": 2}   # TSE_VLAPLACE, TSE_VBIHARMONIC
-
-
-def _vlap_order(order):
-    """the order names, or the header's integer as it is (the library refuses one it does not know)"""
-    if isinstance(order, str):
-        if order not in VLAP_ORDERS:
-            raise TseError("vlaplace_view: unknown order %r (the orders are %s)" % (order, ", ".join(VLAP_ORDERS)))
-        return VLAP_ORDERS[order]
-    return int(order)
+    vi = _as_view(field)
+    return _plan(L, L.tse_biharmonic_view_plan, (nelemd, nf, nk), (vi, vi if out is None else out))
 
 
 def vlaplace_view_plan(nelemd, nk, field, out=None, nlev=None):
@@ -266,27 +218,8 @@ def vlaplace_view_plan(nelemd, nk, field, out=None, nlev=None):
     biharmonic_view_plan (nf is 2: the q axis is the wind component); out=None: in place.  Needs no device.  Raises TseError for views
     vlaplace_view would refuse."""
     L = _lib.lib(nlev=nlev)
-    raw = lambda x: _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
-    vi = None if field is None else raw(field)
-    vo = vi if out is None else raw(out)
-    path, lo, hi = (C.c_int * 2)(), (C.c_longlong * 2)(), (C.c_longlong * 2)()
-    if L.tse_vlaplace_view_plan(int(nelemd), int(nk), None if vi is None else C.byref(vi), None if vo is None else C.byref(vo),
-                                C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
-
-
-SPHERE_OPS = {"gradient": 0, "divergence": 1, "vorticity": 2}   # TSE_OP_GRADIENT, TSE_OP_DIVERGENCE, TSE_OP_VORTICITY
-SPHERE_OP_FIELDS = {0: (1, 2), 1: (2, 1), 2: (2, 1)}            # op -> (fields of in, fields of out)
-
-
-def _sphere_op(op):
-    """the operator names, or the header's integer as it is (the library refuses one it does not know)"""
-    if isinstance(op, str):
-        if op not in SPHERE_OPS:
-            raise TseError("sphere_op_view: unknown op %r (the operators are %s)" % (op, ", ".join(SPHERE_OPS)))
-        return SPHERE_OPS[op]
-    return int(op)
+    vi = _as_view(field)
+    return _plan(L, L.tse_vlaplace_view_plan, (nelemd, nk), (vi, vi if out is None else out))
 
 
 def sphere_op_view_plan(nelemd, nk, op, field, out, nlev=None):
@@ -294,55 +227,25 @@ def sphere_op_view_plan(nelemd, nk, op, field, out, nlev=None):
     biharmonic_view_plan (there is no in-place form: out is needed).  Needs no device.  Raises TseError for views sphere_op_view would
     refuse."""
     L = _lib.lib(nlev=nlev)
-    raw = lambda x: _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
-    vi = None if field is None else raw(field)
-    vo = None if out is None else raw(out)
-    path, lo, hi = (C.c_int * 2)(), (C.c_longlong * 2)(), (C.c_longlong * 2)()
-    if L.tse_sphere_op_view_plan(int(nelemd), int(nk), _sphere_op(op), None if vi is None else C.byref(vi), None if vo is None else C.byref(vo),
-                                 C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return [dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(2)]
-
-
-STATS = 16   # TSE_STATS: doubles per share of HipMod.stats_view
+    views = [_as_view(x) for x in (field, out)]   # (before the op's name is looked up, as ever)
+    return _plan(L, L.tse_sphere_op_view_plan, (nelemd, nk, _named("sphere_op_view", "op", "operators", SPHERE_OPS, op)), views)
 
 
 def stats_view_plan(nelemd, nf, nk, field, ref=None, weight=None, nlev=None):
-    """tse_stats_view_plan: [dict(path=, lo=, hi=)] of the three views of HipMod.stats_view -- field, ref, weight, each a _lib.View or its
-    five strides (doubles, in the order of VIEW_AXES); an absent ref or weight gives None in its place.  Needs no device.  Raises TseError
-    for views stats_view would refuse."""
+    """tse_stats_view_plan: [dict(path=, lo=, hi=)] of the three views of HipMod.stats_view -- field, ref, weight, each in a form
+    _as_view takes; an absent ref or weight gives None in its place.  Needs no device.  Raises TseError for views stats_view would
+    refuse."""
     L = _lib.lib(nlev=nlev)
-    v = [None if x is None else _raw_view(x) for x in (field, ref, weight)]
-    path, lo, hi = (C.c_int * 3)(), (C.c_longlong * 3)(), (C.c_longlong * 3)()
-    if L.tse_stats_view_plan(int(nelemd), int(nf), int(nk), *[None if x is None else C.byref(x) for x in v], C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return [None if v[i] is None else dict(path=path[i], lo=lo[i], hi=hi[i]) for i in range(3)]
-
-
-COLUMN_OPS = {"pint": 0, "pmid": 1, "phi": 2, "omega": 3}   # TSE_COL_PINT, TSE_COL_PMID, TSE_COL_PHI, TSE_COL_OMEGA
-COLUMN_VIEWS = ("dp", "p", "a", "b", "out")
-
-
-def _column_op(op):
-    """the op names, or the header's integer as it is (the library refuses one it does not know)"""
-    if isinstance(op, str):
-        if op not in COLUMN_OPS:
-            raise TseError("column_view: unknown op %r (the ops are %s)" % (op, ", ".join(COLUMN_OPS)))
-        return COLUMN_OPS[op]
-    return int(op)
+    return _plan(L, L.tse_stats_view_plan, (nelemd, nf, nk), (field, ref, weight))
 
 
 def column_view_plan(nelemd, op, dp=None, p=None, a=None, b=None, out=None, nlev=None):
-    """tse_column_view_plan: dict(dp=, p=, a=, b=, out=) of dict(path=, lo=, hi=), None for an absent view -- each view a _lib.View, its
-    five strides (doubles, in the order of VIEW_AXES), or a pair (strides, address) so that the overlap rule is tested as well.  Needs no
-    device.  Raises TseError for views column_view would refuse."""
+    """tse_column_view_plan: dict(dp=, p=, a=, b=, out=) of dict(path=, lo=, hi=), None for an absent view -- each view in a form
+    _as_view takes (a pair: so that the overlap rule is tested as well).  Needs no device.  Raises TseError for views column_view would
+    refuse."""
     L = _lib.lib(nlev=nlev)
-    raw = lambda x: None if x is None else _raw_view(*x) if isinstance(x, tuple) and len(x) == 2 else _raw_view(x)
-    v = [raw(x) for x in (dp, p, a, b, out)]
-    path, lo, hi = (C.c_int * 5)(), (C.c_longlong * 5)(), (C.c_longlong * 5)()
-    if L.tse_column_view_plan(int(nelemd), _column_op(op), *[None if x is None else C.byref(x) for x in v], C.byref(path), C.byref(lo), C.byref(hi)):
-        raise TseError(L.tse_last_error().decode())
-    return {n: None if v[i] is None else dict(path=path[i], lo=lo[i], hi=hi[i]) for i, n in enumerate(COLUMN_VIEWS)}
+    views = [_as_view(x) for x in (dp, p, a, b, out)]   # (before the op's name is looked up, as ever)
+    return dict(zip(COLUMN_VIEWS, _plan(L, L.tse_column_view_plan, (nelemd, _named("column_view", "op", "ops", COLUMN_OPS, op)), views)))
 
 
 class HipMod:
@@ -675,7 +578,8 @@ class HipMod:
         order) and makes the call complete on return."""
         v = build_view("qdp", fq, axes, self.nelemd, self.qsize, self.nlev, False)
         out = np.empty((self.nelemd, self.qsize, 2)) if budget else None
-        self._chk(self.L.tse_apply_forcing(self.h, int(nt), float(dt), _forcing_mode(mode), C.byref(v), _stream_handle(stream), _vp(out)))
+        self._chk(self.L.tse_apply_forcing(self.h, int(nt), float(dt), _named("apply_forcing", "mode", "modes", FORCING_MODES, mode), C.byref(v),
+                                           _stream_handle(stream), _vp(out)))
         return out
 
     def apply_forcing_host(self, elem_fq, nt, dt, mode, budget=False):
@@ -683,8 +587,23 @@ class HipMod:
         copy_qdp_h2d takes Qdp; complete on return"""
         f = elem_fq; assert f.dtype == np.float64 and f.flags.c_contiguous and f.ndim == 5
         out = np.empty((self.nelemd, self.qsize, 2)) if budget else None
-        self._chk(self.L.tse_apply_forcing_host(self.h, int(nt), float(dt), _forcing_mode(mode), _vp(f), f.strides[0], f.shape[1], _vp(out)))
+        self._chk(self.L.tse_apply_forcing_host(self.h, int(nt), float(dt), _named("apply_forcing", "mode", "modes", FORCING_MODES, mode), _vp(f),
+                                                f.strides[0], f.shape[1], _vp(out)))
         return out
+
+    def _operand(self, who, x, axes, written=True, nf=None, nk=None, need="", default=None, field=None):
+        """(view, nf, nk) of one operand of a view entry: a device array described by `axes` (default: `default`) through build_dss_view
+        -- nf and nk are then the array's own extents -- or through build_view as the library field `field` (remap_view); a ready
+        _lib.View, which comes back with the nf and nk given (None: not known, nothing to compare), refused where `need`
+        ("nf and nk are" / "nk is") names one that is None.  who and written: as in build_dss_view."""
+        if isinstance(x, _lib.View):
+            if need and (nk is None or (nf is None and "nf" in need)):
+                raise TseError("%s: %s needed with a ready view" % (who, need))
+            return x, nf, nk
+        axes = default if axes is None else axes
+        if field is not None:
+            return build_view(field, x, axes, self.nelemd, nf, self.nlev, written), nf, self.nlev
+        return build_dss_view(x, axes, self.nelemd, who=who, written=written)
 
     # ---- vertical remap of the host's own level fields (tse_remap_view / tse_remap_view_status) ----
     def remap_view(self, field, axes, dp_src, src_axes, dp_tgt, tgt_axes, mode="mass", alg=0, stream=None, nf=None):
@@ -694,18 +613,16 @@ class HipMod:
         library's state is touched (include/transport_se_hip.h names the one exception).  stream orders as in put.  Returns the
         library's code: 0, or with stream=None 2 when some element's grids were refused on the device (those elements keep every bit;
         last_error() names the first); every other failure raises.  An argument may also be a ready _lib.View (then nf is needed)."""
-        if isinstance(field, _lib.View):
-            vf = field
-        else:
-            cai = getattr(field, "__cuda_array_interface__", None)
-            if cai is not None and "q" in str(axes) and len(cai["shape"]) == len(str(axes)):
-                nf = int(cai["shape"][str(axes).index("q")])
-            vf = build_view("qdp", field, axes, self.nelemd, nf, self.nlev, True)
-        vs = dp_src if isinstance(dp_src, _lib.View) else build_view("dp", dp_src, src_axes, self.nelemd, 1, self.nlev, False)
-        vt = dp_tgt if isinstance(dp_tgt, _lib.View) else build_view("dp", dp_tgt, tgt_axes, self.nelemd, 1, self.nlev, False)
+        cai = getattr(field, "__cuda_array_interface__", None)   # (a ready view has none)
+        if cai is not None and "q" in str(axes) and len(cai["shape"]) == len(str(axes)):
+            nf = int(cai["shape"][str(axes).index("q")])
+        vf = self._operand("remap_view", field, axes, True, nf, field="qdp")[0]
+        vs = self._operand("remap_view", dp_src, src_axes, False, 1, field="dp")[0]
+        vt = self._operand("remap_view", dp_tgt, tgt_axes, False, 1, field="dp")[0]
         if nf is None:
             raise TseError("remap_view: nf is needed with a ready view")
-        rc = self.L.tse_remap_view(self.h, int(nf), _remap_mode(mode), int(alg), C.byref(vf), C.byref(vs), C.byref(vt), _stream_handle(stream))
+        rc = self.L.tse_remap_view(self.h, int(nf), _named("remap_view", "mode", "modes", REMAP_MODES, mode), int(alg), C.byref(vf), C.byref(vs),
+                                   C.byref(vt), _stream_handle(stream))
         if rc not in (0, 2):
             self._chk(rc)
         return rc
@@ -725,34 +642,21 @@ class HipMod:
         do not depend on the view's path or on the number of ranks.  COLLECTIVE on a context with neighbour ranks: every rank calls
         with the same nf, nk and mode.  Nothing of the library's state is touched.  stream orders as in put.  `field` may also be a
         ready _lib.View (then nf and nk are needed)."""
-        if isinstance(field, _lib.View):
-            if nf is None or nk is None:
-                raise TseError("dss_view: nf and nk are needed with a ready view")
-            v = field
-        else:
-            v, nf, nk = build_dss_view(field, axes, self.nelemd)
-        self._chk(self.L.tse_dss_view(self.h, int(nf), int(nk), _dss_mode(mode), C.byref(v), _stream_handle(stream)))
+        v, nf, nk = self._operand("dss_view", field, axes, True, nf, nk, "nf and nk are")
+        self._chk(self.L.tse_dss_view(self.h, int(nf), int(nk), _named("dss_view", "mode", "modes", DSS_MODES, mode), C.byref(v), _stream_handle(stream)))
 
     # ---- weak Laplacian / biharmonic of the host's own scalar fields (tse_biharmonic_view) ----
     def _view_pair(self, who, field, axes, out, out_axes, nf, nk, wind=False):
         """(in view, out view, nf, nk) of biharmonic_view and vlaplace_view: `field` and `out` device arrays (build_dss_view) or ready
         _lib.Views, out=None in place, out_axes=None the axes of `field`; wind: the q axis is the wind component (nf = 2)"""
-        if isinstance(field, _lib.View):
-            if nf is None or nk is None:
-                raise TseError("%s: %s needed with a ready view" % (who, "nk is" if wind else "nf and nk are"))
-            vi = field
-        else:
-            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=out is None)
-            if wind and nf != 2:
-                raise TseError("%s: the q axis is the wind component and has extent %d, not 2" % (who, nf))
+        vi, nf, nk = self._operand(who, field, axes, out is None, nf, nk, "nk is" if wind else "nf and nk are")
+        if wind and nf != 2:   # (an array's own extent: a ready view comes with nf = 2)
+            raise TseError("%s: the q axis is the wind component and has extent %d, not 2" % (who, nf))
         if out is None:
-            vo = vi
-        elif isinstance(out, _lib.View):
-            vo = out
-        else:
-            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
-            if (onf, onk) != (nf, nk):
-                raise TseError("%s: out has %d %s of %d levels, field has %d of %d" % (who, onf, "components" if wind else "fields", onk, nf, nk))
+            return vi, vi, nf, nk
+        vo, onf, onk = self._operand(who, out, out_axes, default=axes)
+        if onf is not None and (onf, onk) != (nf, nk):
+            raise TseError("%s: out has %d %s of %d levels, field has %d of %d" % (who, onf, "components" if wind else "fields", onk, nf, nk))
         return vi, vo, nf, nk
 
     def biharmonic_view(self, field, axes, out=None, out_axes=None, order=2, stream=None, nf=None, nk=None):
@@ -765,7 +669,8 @@ class HipMod:
         ranks, as dss_view.  Nothing of the library's state is touched.  stream orders as in put.  `field` and `out` may also be ready
         _lib.Views (then nf and nk are needed)."""
         vi, vo, nf, nk = self._view_pair("biharmonic_view", field, axes, out, out_axes, nf, nk)
-        self._chk(self.L.tse_biharmonic_view(self.h, int(nf), int(nk), _lap_order(order), C.byref(vi), C.byref(vo), _stream_handle(stream)))
+        self._chk(self.L.tse_biharmonic_view(self.h, int(nf), int(nk), _named("biharmonic_view", "order", "orders", LAP_ORDERS, order), C.byref(vi),
+                                             C.byref(vo), _stream_handle(stream)))
 
     # ---- weak vector Laplacian / biharmonic of the host's own wind (tse_vector_setup, tse_vlaplace_view) ----
     def vector_setup(self, D, metinv, mp):
@@ -786,7 +691,8 @@ class HipMod:
         COLLECTIVE on a context with neighbour ranks, as dss_view.  Needs vector_setup.  stream orders as in put.  `field` and `out` may
         also be ready _lib.Views (then nk is needed)."""
         vi, vo, _, nk = self._view_pair("vlaplace_view", field, axes, out, out_axes, 2, nk, wind=True)
-        self._chk(self.L.tse_vlaplace_view(self.h, int(nk), _vlap_order(order), float(nu_ratio), C.byref(vi), C.byref(vo), _stream_handle(stream)))
+        self._chk(self.L.tse_vlaplace_view(self.h, int(nk), _named("vlaplace_view", "order", "orders", VLAP_ORDERS, order), float(nu_ratio), C.byref(vi),
+                                           C.byref(vo), _stream_handle(stream)))
 
     # ---- gradient, divergence, vorticity of the host's own fields, element-local or C0 (tse_sphere_op_view) ----
     def sphere_op_view(self, field, axes, out, out_axes=None, op="vorticity", c0=False, stream=None, nk=None):
@@ -798,26 +704,18 @@ class HipMod:
         `field`.  c0=True has the bits of c0=False followed by dss_view(out, mode="average").  "vorticity" needs vector_setup.  stream
         orders as in put.  `field` and `out` may also be ready _lib.Views (then nk is needed)."""
         who = "sphere_op_view"
-        o = _sphere_op(op)
+        o = _named(who, "op", "operators", SPHERE_OPS, op)
         nfi, nfo = SPHERE_OP_FIELDS.get(o, (None, None))
         side = lambda n, want: ("the q axis is the component and has extent %d, not 2" if want == 2 else
                                 "a scalar field has a q axis of extent %d (the letter q is absent or has extent 1)") % n
-        if isinstance(field, _lib.View):
-            if nk is None:
-                raise TseError("%s: nk is needed with a ready view" % who)
-            vi = field
-        else:
-            vi, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=False)
-            if nfi is not None and nf != nfi:
-                raise TseError("%s: field: %s" % (who, side(nf, nfi)))
-        if isinstance(out, _lib.View):
-            vo = out
-        else:
-            vo, onf, onk = build_dss_view(out, axes if out_axes is None else out_axes, self.nelemd, who=who)
-            if onk != nk:
-                raise TseError("%s: out has %d levels, field has %d" % (who, onk, nk))
-            if nfo is not None and onf != nfo:
-                raise TseError("%s: out: %s" % (who, side(onf, nfo)))
+        vi, nf, nk = self._operand(who, field, axes, False, None, nk, "nk is")
+        if None not in (nf, nfi) and nf != nfi:
+            raise TseError("%s: field: %s" % (who, side(nf, nfi)))
+        vo, onf, onk = self._operand(who, out, out_axes, default=axes)
+        if onk is not None and onk != nk:
+            raise TseError("%s: out has %d levels, field has %d" % (who, onk, nk))
+        if None not in (onf, nfo) and onf != nfo:
+            raise TseError("%s: out: %s" % (who, side(onf, nfo)))
         self._chk(self.L.tse_sphere_op_view(self.h, int(nk), o, int(c0), C.byref(vi), C.byref(vo), _stream_handle(stream)))
 
     # ---- min, max, sums and integrals of the host's fields from element partials (tse_stats_view) ----
@@ -831,28 +729,18 @@ class HipMod:
         the library's own (device_ptr).  Not collective.  A stream is waited for; the call is complete on return.  The arrays may also be
         ready _lib.Views (then nf and nk are needed)."""
         who = "stats_view"
-        if isinstance(field, _lib.View):
-            if nf is None or nk is None:
-                raise TseError("%s: nf and nk are needed with a ready view" % who)
-            vf = field
-        else:
-            vf, nf, nk = build_dss_view(field, axes, self.nelemd, who=who, written=False)
+        vf, nf, nk = self._operand(who, field, axes, False, nf, nk, "nf and nk are")
         vr = vw = None
-        if isinstance(ref, _lib.View):
-            vr = ref
-        elif ref is not None:
-            vr, rnf, rnk = build_dss_view(ref, axes if ref_axes is None else ref_axes, self.nelemd, who=who, written=False)
-            if (rnf, rnk) != (nf, nk):
+        if ref is not None:
+            vr, rnf, rnk = self._operand(who, ref, ref_axes, False, default=axes)
+            if rnf is not None and (rnf, rnk) != (nf, nk):
                 raise TseError("%s: ref has %d fields of %d levels, field has %d of %d" % (who, rnf, rnk, nf, nk))
-        if isinstance(weight, _lib.View):
-            vw = weight
-        elif weight is not None:
-            vw, wnf, wnk = build_dss_view(weight, str(axes).replace("q", "") if weight_axes is None else weight_axes, self.nelemd, who=who, written=False)
-            if (wnf, wnk) != (1, nk):
+        if weight is not None:
+            vw, wnf, wnk = self._operand(who, weight, weight_axes, False, default=str(axes).replace("q", ""))
+            if wnf is not None and (wnf, wnk) != (1, nk):
                 raise TseError("%s: weight has %d fields of %d levels, one field of %d is needed" % (who, wnf, wnk, nk))
         out = np.empty((self.nelemd, int(nf)) + ((int(nk),) if per_level else ()) + (STATS,), dtype=np.float64)
-        self._chk(self.L.tse_stats_view(self.h, int(nf), int(nk), int(bool(per_level)), C.byref(vf), None if vr is None else C.byref(vr),
-                                        None if vw is None else C.byref(vw), _stream_handle(stream), _vp(out)))
+        self._chk(self.L.tse_stats_view(self.h, int(nf), int(nk), int(bool(per_level)), C.byref(vf), _ref(vr), _ref(vw), _stream_handle(stream), _vp(out)))
         return out
 
     # ---- pressure, geopotential and omega / p of the host's columns (tse_column_view) ----
@@ -866,7 +754,7 @@ class HipMod:
         may also be a ready _lib.View; inputs may be the library's own fields (device_ptr), out may not, and out may not overlap an
         input.  Not collective.  stream orders as in put."""
         who = "column_view"
-        o = _column_op(op)
+        o = _named(who, "op", "ops", COLUMN_OPS, op)
         nlev = self.nlev
         surface = o == COLUMN_OPS["phi"]
         want = dict(dp=nlev, p=nlev, a=nlev, b=1 if surface else nlev, out=nlev + 1 if o == COLUMN_OPS["pint"] else nlev)
@@ -874,18 +762,15 @@ class HipMod:
                     b=b_axes or (str(dp_axes).replace("k", "") if surface else dp_axes))
         views = {}
         for name, x in (("dp", dp), ("p", p), ("a", a), ("b", b), ("out", out)):
-            if x is None or isinstance(x, _lib.View):
-                views[name] = x
+            if x is None:
+                views[name] = None
                 continue
-            v, nf, nk = build_dss_view(x, axes[name], self.nelemd, who=who, written=name == "out")
-            if nf != 1:
+            views[name], nf, nk = self._operand(who, x, axes[name], name == "out")
+            if nf is not None and nf != 1:
                 raise TseError("%s: %s: a q axis of extent %d (one field per call)" % (who, name, nf))
-            if nk != want[name]:
+            if nk is not None and nk != want[name]:
                 raise TseError("%s: %s has %d levels, %s wants %d" % (who, name, nk, op, want[name]))
-            views[name] = v
-        ref = lambda x: None if x is None else C.byref(x)
-        self._chk(self.L.tse_column_view(self.h, o, float(ptop), float(rgas), ref(views["dp"]), ref(views["p"]), ref(views["a"]), ref(views["b"]),
-                                         ref(views["out"]), _stream_handle(stream)))
+        self._chk(self.L.tse_column_view(self.h, o, float(ptop), float(rgas), *[_ref(views[name]) for name in COLUMN_VIEWS], _stream_handle(stream)))
 
     def last_error(self):
         return self.L.tse_last_error().decode()
