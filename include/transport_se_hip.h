@@ -434,6 +434,46 @@ int tse_vlaplace_view(tse_ctx *ctx, int nk, int order, double nu_ratio, const ts
 /* the paths and footprints of in ([0]) and out ([1]) and every refusal that needs no device, as tse_biharmonic_view_plan with nf = 2 */
 int tse_vlaplace_view_plan(int nelemd, int nk, const tse_view *in, const tse_view *out, int path[2], long long lo[2], long long hi[2]);
 
+/* ---- one hyperviscosity sub-step of a GPU-resident host's OWN scalars and wind in one call: the body of advance_hypervis's subcycle
+ * loop for hypervis_scaling == 0 -- biharmonic_wk_dp3d (viscosity_mod.F90:229-279: ONE edge buffer for ptens, vtens and dptens, one
+ * bndry_exchangeV), the factors -nu * dt / hypervis_subcycle, the final DSS (a second single exchange) and the update of the state ----
+ *   per point of scalar field f (x = s) and of each wind component (x = v), one fixed sequence of roundings, nothing contracted:
+ *     w = lap(x)                                  the staged first Laplacian of tse_biharmonic_view / tse_vlaplace_view
+ *     b = lap(rspheremp * (((w + c0) + c1) + c2)) the bits of tse_biharmonic_view(TSE_BIHARMONIC) / tse_vlaplace_view(TSE_VBIHARMONIC, nu_ratio)
+ *     t = coef * b                                one product, always formed: coef[f] for scalar field f, coef[nf] for the wind
+ *     d = rspheremp * (((t + c0) + c1) + c2)      the bits of tse_dss_view(TSE_DSS_WEAK) on t
+ *     in place (s_out and v_out NULL): x <- x + d, one addition;  with out views: out <- d, x keeps every bit
+ * so the call has the bits of tse_biharmonic_view -> product -> tse_dss_view(TSE_DSS_WEAK) -> addition (and the same with
+ * tse_vlaplace_view), on every path of every view, for a level alone or among others, on one rank or many.
+ * s: nf >= 0 scalar fields of nk levels under the rules of tse_biharmonic_view's `in` (E3SM's T and dp3d, two members of elem(:) at one
+ * element stride, are ONE view whose q stride is the distance between the members); nf <= TSE_HYPERVIS_MAX_FIELDS.  v: the wind under
+ * the rules of tse_vlaplace_view's `in`; it needs tse_vector_setup.  Either may be absent -- nf = 0 with s = NULL, or v = NULL -- not both.
+ * 1 <= nk <= nlev + 1; each view takes its own path.  coef: nf + 1 doubles of the host, formed there in double (-nu_s * dt /
+ * hypervis_subcycle, -nu_p * ... for dp3d, the wind's last), each finite; coef[nf] is not read when v is NULL.
+ * s_out, v_out: both NULL, or given for exactly the inputs that are present (a host that needs vtens itself: E3SM's frictional heating
+ * -(v . vtens) / cp); views of the shape of their input.  Every two views of a call are disjoint: their footprints do not meet, or --
+ * members of one elem(:), which interleave -- they have the same element stride and their footprints within one element are disjoint
+ * and lie together inside one element stride.  Only addresses of s and v (in place) or of the out views are written.
+ * Not in this call: the heating itself, nu_top, hypervis_scaling > 0, subcell_Laplace_fluxes, two different nu_ratios.
+ * Refused, with nonzero return, tse_last_error() and nothing enqueued: everything tse_biharmonic_view or tse_vlaplace_view refuses for
+ * any of the views, the overlap and presence rules above, v before tse_vector_setup, a coef or nu_ratio that is not finite, a stream
+ * under capture or of another device, a view inside an allocation of the library, nelemd * (nf + 2) * nk >= 2^27.
+ * Device: at most five launches (the two first Laplacians, the two second ones, ONE final kernel for both halves) and, on a context with
+ * neighbour ranks, exactly TWO exchanges (kind 0) of nl = (nf + 2) * nk layers (nf * nk without v) -- the loop of the separate entries
+ * makes four.  COLLECTIVE there: every rank calls with the same nf, nk and presence of v, in the same order among the exchanging calls.
+ * The first staging field and the halo buffers are tse_dss_view's ("view_stage"); the second staging field ("hypervis_stage") is this
+ * call's own; both grow when a call brings more layers, so a steady-state call allocates nothing.  Both exchanges are ordered on the
+ * compute stream, so the second cannot reach the receive buffer before the kernel that reads the first has finished.  No library state
+ * is read or written except the tables of tse_vector_setup.  stream orders as in tse_dss_view.  Timer group "fieldhv" (one count per
+ * launch); pack and exchange count under comm_pack_q / comm_exchange_q / comm_wait. */
+#define TSE_HYPERVIS_MAX_FIELDS 64
+int tse_hypervis_view(tse_ctx *ctx, int nf, int nk, const double *coef, double nu_ratio, const tse_view *s, const tse_view *v,
+                      const tse_view *s_out, const tse_view *v_out, void *stream);
+/* the paths and footprints of s ([0]), v ([1]), s_out ([2]) and v_out ([3]) -- path -1 and an empty footprint for an absent view -- and
+ * every refusal that needs no device; the overlap rule is applied when any ptr is not null.  Host only: no context, no device. */
+int tse_hypervis_view_plan(int nelemd, int nf, int nk, const tse_view *s, const tse_view *v, const tse_view *s_out, const tse_view *v_out,
+                           int path[4], long long lo[4], long long hi[4]);
+
 /* ---- first-order sphere operators of a GPU-resident host's OWN fields, element-local or continuous (C0): gradient_sphere,
  * divergence_sphere and vorticity_sphere of derivative_mod.F90 on nk levels of one view, 1 <= nk <= nlev + 1, and with TSE_OP_C0 the
  * make_C0 / make_C0_vector of viscosity_mod.F90:445-535 behind them -- compute_zeta_C0, compute_div_C0 (:542-745), the continuous
@@ -598,11 +638,12 @@ int tse_mix_partials(tse_ctx *ctx, int nt, int qa, int qb, double xmin, double x
  * (both null before the first tse_state_q; "q" is also the staging field of tse_apply_forcing_host, which allocates it), "qref" [nelemd][nlev][16] (null before the first tse_norm_reference),
  * "remap_status" [nelemd][4] ints (null before the first tse_remap_view), "view_stage" [nelemd][layers][16] the staging field tse_dss_view,
  * tse_biharmonic_view, tse_vlaplace_view and tse_sphere_op_view share (null before the first call of any; it moves only when a call brings more layers than any before),
+ * "hypervis_stage" the second staging field of tse_hypervis_view (null before its first call; the same shape and growth rule),
  * "stats_partials" the partials buffer of tse_stats_view (null before its first call; it moves only when a call needs more than any before) */
 void *tse_device_ptr(tse_ctx *ctx, const char *name, size_t *nbytes);
 /* accumulated HIP-event time (ms) and launch count of a named kernel group since the last reset; names:
  * "advance" (= "advance0" + "advance1" + "advance2", the three RK stages), "dss", "lap", "minmax", "remap", "level", "dcmip", "avg", "stateq", "norms"
- * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), "fieldop" (tse_sphere_op_view: its stage kernel and the sum or copy kernel behind it), "fieldstats" (tse_stats_view: its one kernel), "fieldcol" (tse_column_view: its one kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
+ * (tse_norm_reference and tse_norm_partials), "mixing" (tse_mix_partials), "view" (tse_view_put and tse_view_get), "forcing" (tse_apply_forcing and tse_apply_forcing_host), "fieldremap" (tse_remap_view: its check kernel and its remap kernel), "fielddss" (tse_dss_view: its stage and its sum kernel), "fieldlap" (tse_biharmonic_view: its stage and its out kernel), "fieldvlap" (tse_vlaplace_view: its stage and its out kernel), "fieldhv" (tse_hypervis_view: one count per launch, at most five), "fieldop" (tse_sphere_op_view: its stage kernel and the sum or copy kernel behind it), "fieldstats" (tse_stats_view: its one kernel), "fieldcol" (tse_column_view: its one kernel), and the comm_* groups of tse_comm_timing.  A name matches every group it is a prefix of. */
 int tse_kernel_time(tse_ctx *ctx, const char *name, double *ms, long *launches);
 int tse_timing(tse_ctx *ctx, int enable); /* enable/disable + reset per-kernel event timing (not the comm_* groups) */
 /* enable/disable + reset the timers of the halo exchange, read through tse_kernel_time like the kernel groups (and reset by this call

@@ -151,6 +151,7 @@ SYMBOLS = ["tse_init", "tse_finalize", "tse_last_error", "tse_nlev", "tse_synchr
            "tse_view_put", "tse_view_get", "tse_view_plan", "tse_apply_forcing", "tse_apply_forcing_host",
            "tse_remap_view", "tse_remap_view_status", "tse_remap_view_plan", "tse_dss_view", "tse_dss_view_plan",
            "tse_biharmonic_view", "tse_biharmonic_view_plan", "tse_vector_setup", "tse_vlaplace_view", "tse_vlaplace_view_plan",
+           "tse_hypervis_view", "tse_hypervis_view_plan",
            "tse_sphere_op_view", "tse_sphere_op_view_plan", "tse_stats_view", "tse_stats_view_plan",
            "tse_column_view", "tse_column_view_plan"]
 COMM_ID_BYTES = 128
@@ -248,6 +249,8 @@ def lib(path=None, nlev=None):
     L.tse_vector_setup.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
     L.tse_vlaplace_view.argtypes = [vp, i, i, d, C.POINTER(View), C.POINTER(View), vp]
     L.tse_vlaplace_view_plan.argtypes = [i, i, C.POINTER(View), C.POINTER(View), C.POINTER(i * 2), C.POINTER(C.c_longlong * 2), C.POINTER(C.c_longlong * 2)]
+    L.tse_hypervis_view.argtypes = [vp, i, i, vp, d] + [C.POINTER(View)] * 4 + [vp]
+    L.tse_hypervis_view_plan.argtypes = [i, i, i] + [C.POINTER(View)] * 4 + [C.POINTER(i * 4), C.POINTER(C.c_longlong * 4), C.POINTER(C.c_longlong * 4)]
     L.tse_sphere_op_view.argtypes = [vp, i, i, i, C.POINTER(View), C.POINTER(View), vp]
     L.tse_sphere_op_view_plan.argtypes = [i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(i * 2), C.POINTER(C.c_longlong * 2), C.POINTER(C.c_longlong * 2)]
     L.tse_stats_view.argtypes = [vp, i, i, i, C.POINTER(View), C.POINTER(View), C.POINTER(View), vp, vp]

@@ -306,7 +306,7 @@ std::vector<void*> tse::device_allocations(const tse_ctx* c) {
                   c->nbr, c->mm_send_src, c->qlev[0], c->qlev[1], c->vn0, c->dp, c->divdp, c->divdp_proj, c->eta, c->omega_p, c->dp3d, c->ps_v,
                   c->lvl_tmp, c->eta2, c->sink, c->order, c->qmin, c->qmax, c->qmin2, c->qmax2, c->qmix, c->lnps, c->norm_owner, c->norm_colw, c->norm_dh, c->qref, c->bad, c->lat, c->lon, c->zm, c->zi, c->pint, c->dph,
                   c->sendbuf, c->recvbuf, c->sendbuf_mm, c->recvbuf_mm, c->ord_bnd, c->ord_int, c->slot_of, c->send_src_s, c->pperm, c->pexp, c->etab, c->rl_all, c->rl_bnd, c->rl_int,
-                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc, c->dv_stage, c->dv_send, c->dv_recv, c->vec_tab, c->st_part};
+                  c->T, c->B, c->C, P.pslots, P.plist_bnd, P.plist_int, P.pering, P.pring, P.plds, P.pnb, c->rv_status, c->rv_detail, c->rv_acc, c->dv_stage, c->dv_send, c->dv_recv, c->hv_stage, c->vec_tab, c->st_part};
   std::vector<void*> out;
   for (void* p : ptrs) if (p) out.push_back(p);
   return out;
@@ -1466,6 +1466,7 @@ void* tse_device_ptr(tse_ctx* c, const char* name, size_t* nbytes) {
                 {"recvbuf", c->recvbuf, (size_t)c->ncol_recv * c->nlyr_halo * 8}, {"sendbuf_mm", c->sendbuf_mm, (size_t)c->nmm_send * m2},
                 {"recvbuf_mm", c->recvbuf_mm, (size_t)c->nmm_recv * m2}, {"remap_status", c->rv_status, (size_t)c->nelemd * c->rv_status_ints * sizeof(int)},
                 {"view_stage", c->dv_stage, (size_t)c->nelemd * c->dv_layers * 16 * 8},   // (the staging field of tse_dss_view / tse_biharmonic_view: null before their first call)
+                {"hypervis_stage", c->hv_stage, (size_t)c->nelemd * c->hv_layers * 16 * 8},   // (the second staging field of tse_hypervis_view: null before its first call)
                 {"stats_partials", c->st_part, c->st_cap * 8}};                           // (the partials buffer of tse_stats_view: null before its first call)
   for (auto& e : ents) if (!strcmp(e.n, name)) { if (nbytes) *nbytes = e.p ? e.b : 0; return e.p; }
   if (nbytes) *nbytes = 0;

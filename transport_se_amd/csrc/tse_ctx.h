@@ -99,6 +99,9 @@ struct tse_ctx {
   // rank with neighbours, its own send and receive buffers [columns][dv_layers] -- the context's own are sized by qsize
   double *dv_stage = nullptr, *dv_send = nullptr, *dv_recv = nullptr;
   size_t dv_layers = 0;
+  // tse_hypervis_view (allocated by its first call, grown like dv_stage): the second staging field [nelemd][hv_layers][16]
+  double* hv_stage = nullptr;
+  size_t hv_layers = 0;
   // tse_stats_view (allocated by its first call, grown when a call needs more): the element or level shares before they go to the host
   double* st_part = nullptr;
   size_t st_cap = 0;   // doubles

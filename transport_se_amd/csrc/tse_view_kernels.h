@@ -4,6 +4,7 @@
 // tse_api.hip: a view kernel lives in their code objects and no kernel of the tracer path does (DESIGN.md says why).  tse_kernels.h
 // comes along for the remap and DSS device functions the view kernels reuse; a template nobody instantiates costs nothing.
 #pragma once
+#include "../../include/transport_se_hip.h"   // (TSE_HYPERVIS_MAX_FIELDS)
 #include "tse_kernels.h"
 
 namespace tse {
@@ -500,7 +501,9 @@ __global__ __launch_bounds__(REMAP_THREADS) void k_remap_view(int nf, RemapViewA
 //           with the lane mapping of k_view_levels (WIDE as there).
 // Every sum is ((w + c0) + c1) + c2 with +0.0 for an absent contribution and nothing contracted: the three paths, and any cut of the mesh
 // into ranks, give the same bits.
-struct DssViewArgs { long long vs[5]; int nf, nk; };
+// base, nl: where a stage kernel that shares the staging field with another (tse_hypervis_view) puts its layers -- layer base + f * nk + k
+// of nl per element; every other call has base 0 and nl = nf * nk.  Read by k_lap_view_stage, k_vlap_view_stage and k_dss_view_final alone.
+struct DssViewArgs { long long vs[5]; int nf, nk, base, nl; };
 
 // the view side of a level-fastest tile, as k_view_levels moves it: 16 rows of K consecutive levels at pitch S <-> tile[p][VIEW_PITCH]
 template <bool WIDE, int K>
@@ -735,7 +738,7 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_lap_view_stage(int nelemd, Dss
     make_lap_geo(L, g);
     dss_rows_to_tile<WIDE, K>(view + (long long)e * a.vs[0] + f * a.vs[1], a.vs[4], tile, tid);
     __syncthreads();
-    double* S = stage + ((size_t)e * nl + (size_t)f * K) * 16 + 4 * j;
+    double* S = stage + ((size_t)e * a.nl + a.base + (size_t)f * K) * 16 + 4 * j;
     for (int k = tid >> 2; k < K; k += VIEW_THREADS / 4) {
       double s[4], r[4];
 #pragma unroll
@@ -760,7 +763,7 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_lap_view_stage(int nelemd, Dss
       double s[4], r[4];
       lap_view_load_row<PATH, WIDE>(view + (long long)e * a.vs[0] + f * a.vs[1] + k * a.vs[2], a, j, s);
       laplace_lean_row(D, L, s, r);
-      if (live && l0 + u < nl) store4(stage + ((size_t)e * nl + layer) * 16 + 4 * j, r);
+      if (live && l0 + u < nl) store4(stage + ((size_t)e * a.nl + a.base + layer) * 16 + 4 * j, r);
     }
   }
 }
@@ -877,7 +880,7 @@ template <int PATH, bool WIDE>
 __global__ __launch_bounds__(VIEW_THREADS) void k_vlap_view_stage(int nelemd, DssViewArgs a, Dvv_t D, GeoPtrs G, const double* __restrict__ vtab, double nu_ratio,
                                                                   const double* __restrict__ view, double* __restrict__ stage) {
 #pragma clang fp contract(off)
-  const int nk = a.nk, nl = 2 * nk, tid = threadIdx.x, j = tid & 3;
+  const int nk = a.nk, nl = a.nl, tid = threadIdx.x, j = tid & 3;   // (nl = 2 * nk unless the call shares the staging field: DssViewArgs)
   VecGeo V;
   if (PATH == 1) {
     __shared__ __attribute__((aligned(16))) double tile[2][16 * VIEW_PITCH];
@@ -887,7 +890,7 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_vlap_view_stage(int nelemd, Ds
     dss_rows_to_tile<WIDE, K>(view + (long long)e * a.vs[0], a.vs[4], tile[0], tid);
     dss_rows_to_tile<WIDE, K>(view + (long long)e * a.vs[0] + a.vs[1], a.vs[4], tile[1], tid);
     __syncthreads();
-    double* S = stage + (size_t)e * nl * 16 + 4 * j;
+    double* S = stage + ((size_t)e * nl + a.base) * 16 + 4 * j;
     for (int k = tid >> 2; k < K; k += VIEW_THREADS / 4) {
       double v1[4], v2[4], r1[4], r2[4];
 #pragma unroll
@@ -914,8 +917,8 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_vlap_view_stage(int nelemd, Ds
       lap_view_load_row<PATH, WIDE>(P + a.vs[1], a, j, v2);
       vlaplace_row(D, V, nu_ratio, v1, v2, r1, r2);
       if (live && k0 + u < nk) {
-        store4(stage + ((size_t)e * nl + k) * 16 + 4 * j, r1);
-        store4(stage + ((size_t)e * nl + nk + k) * 16 + 4 * j, r2);
+        store4(stage + ((size_t)e * nl + a.base + k) * 16 + 4 * j, r1);
+        store4(stage + ((size_t)e * nl + a.base + nk + k) * 16 + 4 * j, r2);
       }
     }
   }
@@ -998,6 +1001,175 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_vlap_view_out(int nelemd, DssV
 inline long long vlap_view_groups(long long nk) { return (nk + VLAP_VIEW_LEVELS - 1) / VLAP_VIEW_LEVELS; }
 // blocks of k_vlap_view_out<0 | 2>: 8 XCD ranges of ceil(nelemd / 8) element slots, one quad per VLAP_VIEW_LEVELS levels of an element
 inline long long vlap_view_out_blocks(int nelemd, long long nk) { return dss_view_sum_blocks(nelemd, 4 * vlap_view_groups(nk)); }
+
+// ---- one hyperviscosity sub-step of a host's own scalars and wind through strided views (tse_hypervis_view) --------------------------
+// x <- x + rspheremp * DSS(coef * biharmonic(x)) for nf scalar fields and the wind, both halves through ONE staging field of
+// nl = (nf + 2) * nk layers -- the scalars' layers f * nk + k first, then the wind's nf * nk + c * nk + k -- so that a sub-step costs two
+// exchanges of nl layers, biharmonic_wk_dp3d's one and advance_hypervis_dp's one, whatever it holds:
+//   k_lap_view_stage, k_vlap_view_stage   x -> lap -> stage (DssViewArgs::base / nl place each half)
+//   (pack, halo_exchange)
+//   k_lap_view_mid, k_vlap_view_mid           stage -> [sum, rspheremp, second Laplacian, times coef] -> stage2: k_lap_view_out<., ., 2> and
+//                                         k_vlap_view_out<., ., 2> on their flattened path with a dense destination and one product more.
+//                                         A second field, not the first in place: the neighbours' lines of the first are still being read.
+//   (pack, halo_exchange)
+//   k_dss_view_final<ADD>                       stage2 -> [sum, rspheremp] -> x + d (ADD: in place, x is read and written once) or -> the out views;
+//                                         ONE launch for both halves: blocks [0, blocks0) serve side 0, the others side 1, and each side
+//                                         brings the form of its own view (HvForm: the view side of k_dss_view_sum's three paths).
+// Every step is the statement of the kernel it is taken from, so a point's result has the bits of tse_biharmonic_view / tse_vlaplace_view
+// (order 2) -> one product -> tse_dss_view(TSE_DSS_WEAK) -> one addition.
+constexpr int HV_MAX_FIELDS = TSE_HYPERVIS_MAX_FIELDS;
+struct HvCoef { double c[HV_MAX_FIELDS]; };   // the scalars' factors, by value: no buffer to fill, nothing for a later call to overwrite
+
+template <int = 0>
+__global__ __launch_bounds__(VIEW_THREADS) void k_lap_view_mid(int nelemd, int nf, int nk, int nlt, HvCoef cf, Dvv_t D, GeoPtrs G, const int2* __restrict__ tab,
+                                                             const double* __restrict__ stage, const double* __restrict__ recvbuf,
+                                                             const int* __restrict__ order, double* __restrict__ stage2) {
+#pragma clang fp contract(off)
+  const int nl = nf * nk, tid = threadIdx.x, j = tid & 3;
+  const int S8 = (nelemd + 7) >> 3, xcd = blockIdx.x & 7;   // contiguous ranges of `order` per XCD, as in k_dss_view_sum
+  const unsigned it = blockIdx.x >> 3;
+  RowGeo g;
+  LapGeo L;
+  const int groups = (nl + LAP_VIEW_LAYERS - 1) / LAP_VIEW_LAYERS;
+  const long long qd = ((long long)it * VIEW_THREADS + tid) >> 2;
+  const long long idx = qd / groups;
+  const int grp = (int)(qd - idx * groups);
+  const long long slot = (long long)xcd * S8 + idx;
+  const bool live = idx < S8 && slot < nelemd;
+  const int e = order[live ? slot : nelemd - 1];
+  load_row_geo(g, G.dvv, G.Dinv, G.metdet, G.rmetdet, G.spheremp, e, j);
+  make_lap_geo(L, g);
+  const int l0 = grp * LAP_VIEW_LAYERS;
+#pragma unroll
+  for (int u = 0; u < LAP_VIEW_LAYERS; u++) {
+    const int layer = min(l0 + u, nl - 1);
+    const double cl = cf.c[layer / nk];
+    double m[4], r[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      double rs;
+      const double x = dss_view_point(tab, stage, recvbuf, nlt, e, 4 * j + i, layer, rs, G.rspheremp);
+      m[i] = rs * x;
+    }
+    laplace_lean_row(D, L, m, r);
+#pragma unroll
+    for (int i = 0; i < 4; i++) r[i] = cl * r[i];
+    if (live && l0 + u < nl) store4(stage2 + ((size_t)e * nlt + layer) * 16 + 4 * j, r);
+  }
+}
+
+template <int = 0>
+__global__ __launch_bounds__(VIEW_THREADS) void k_vlap_view_mid(int nelemd, int nk, int base, int nlt, double cv, Dvv_t D, GeoPtrs G, const double* __restrict__ vtab,
+                                                              double nu_ratio, const int2* __restrict__ tab, const double* __restrict__ stage,
+                                                              const double* __restrict__ recvbuf, const int* __restrict__ order, double* __restrict__ stage2) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, j = tid & 3;
+  const int S8 = (nelemd + 7) >> 3, xcd = blockIdx.x & 7;
+  const unsigned it = blockIdx.x >> 3;
+  VecGeo V;
+  const int groups = (nk + VLAP_VIEW_LEVELS - 1) / VLAP_VIEW_LEVELS;
+  const long long qd = ((long long)it * VIEW_THREADS + tid) >> 2;
+  const long long idx = qd / groups;
+  const int grp = (int)(qd - idx * groups);
+  const long long slot = (long long)xcd * S8 + idx;
+  const bool live = idx < S8 && slot < nelemd;
+  const int e = order[live ? slot : nelemd - 1];
+  load_vec_geo(V, G.dvv, vtab, e, j);
+  const int k0 = grp * VLAP_VIEW_LEVELS;
+#pragma unroll
+  for (int u = 0; u < VLAP_VIEW_LEVELS; u++) {
+    const int k = min(k0 + u, nk - 1);
+    double m1[4], m2[4], r1[4], r2[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      double rs;
+      const double x1 = dss_view_point(tab, stage, recvbuf, nlt, e, 4 * j + i, base + k, rs, G.rspheremp);
+      const double x2 = dss_view_point(tab, stage, recvbuf, nlt, e, 4 * j + i, base + nk + k, rs, G.rspheremp);
+      m1[i] = rs * x1; m2[i] = rs * x2;
+    }
+    vlaplace_row(D, V, nu_ratio, m1, m2, r1, r2);
+#pragma unroll
+    for (int i = 0; i < 4; i++) { r1[i] = cv * r1[i]; r2[i] = cv * r2[i]; }
+    if (live && k0 + u < nk) {
+      store4(stage2 + ((size_t)e * nlt + base + k) * 16 + 4 * j, r1);
+      store4(stage2 + ((size_t)e * nlt + base + nk + k) * 16 + 4 * j, r2);
+    }
+  }
+}
+
+// the view side of k_dss_view_final, chosen per side at run time (uniform over a block): 16-byte parts of a point-fastest line, one address per
+// entry (path 2, and path 0 without the alignment), the rows of a level-fastest tile with 16 or 8 bytes per lane
+enum HvForm { HV_LINES_WIDE = 0, HV_POINTS = 1, HV_ROWS_WIDE = 2, HV_ROWS = 3 };
+struct HvSide { DssViewArgs a; int form; double* x; };   // a.nf fields of a.nk levels on layers a.base + f * a.nk + k of a.nl; x: s / v (ADD) or the out view
+struct HvFinalArgs { HvSide side[2]; unsigned blocks0; };
+
+template <bool ADD>
+__global__ __launch_bounds__(VIEW_THREADS) void k_dss_view_final(int nelemd, HvFinalArgs A, const int2* __restrict__ tab, const double* __restrict__ rspheremp,
+                                                           const double* __restrict__ stage, const double* __restrict__ recvbuf, const int* __restrict__ order) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) double tile[16 * VIEW_PITCH];
+  const bool second = blockIdx.x >= A.blocks0;   // (blocks0 is a multiple of 8: the XCD of a block is that of its index within the side)
+  const HvSide& S = A.side[second ? 1 : 0];
+  const DssViewArgs& a = S.a;
+  const unsigned bid = blockIdx.x - (second ? A.blocks0 : 0u);
+  const int nl = a.nl, own = a.nf * a.nk, form = S.form;
+  const int S8 = (nelemd + 7) >> 3, xcd = bid & 7;
+  const unsigned it = bid >> 3;
+  double* __restrict__ view = S.x;
+  if (form >= HV_ROWS_WIDE) {
+    constexpr int K = NLEV, NL = (8 * K + VIEW_THREADS - 1) / VIEW_THREADS;
+    const int idx = (int)(it / (unsigned)a.nf), f = (int)(it % (unsigned)a.nf), slot = xcd * S8 + idx;
+    if (idx >= S8 || slot >= nelemd) return;   // (uniform over the block: before the barrier)
+    const int e = order[slot], tid = threadIdx.x, h = tid & 7;
+    double* V = view + (long long)e * a.vs[0] + f * a.vs[1];
+    if (ADD) {
+      if (form == HV_ROWS_WIDE) dss_rows_to_tile<true, K>(V, a.vs[4], tile, tid); else dss_rows_to_tile<false, K>(V, a.vs[4], tile, tid);
+      __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < NL; u++) {
+      const int i2 = u * VIEW_THREADS + tid;
+      if (i2 < 8 * K) {
+        const int k = i2 >> 3;
+        double r0, r1;
+        const double x0 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * h, a.base + f * K + k, r0, rspheremp);
+        const double x1 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * h + 1, a.base + f * K + k, r1, rspheremp);
+        double* s = tile + 2 * h * VIEW_PITCH + k;
+        const double d0 = r0 * x0, d1 = r1 * x1;
+        if (ADD) { s[0] = s[0] + d0; s[VIEW_PITCH] = s[VIEW_PITCH] + d1; }
+        else { s[0] = d0; s[VIEW_PITCH] = d1; }
+      }
+    }
+    __syncthreads();
+    if (form == HV_ROWS_WIDE) dss_tile_to_rows<true, K>(tile, V, a.vs[4], tid); else dss_tile_to_rows<false, K>(tile, V, a.vs[4], tid);
+  } else {
+    const int PARTS = form == HV_LINES_WIDE ? 8 : 16;
+    const long long units = (long long)own * PARTS;
+    const long long gl = (long long)it * VIEW_THREADS + threadIdx.x;
+    const long long idx = gl / units;
+    const int r = (int)(gl - idx * units);
+    const long long slot = (long long)xcd * S8 + idx;
+    if (idx >= S8 || slot >= nelemd) return;
+    const int e = order[slot], layer = r / PARTS, part = r - layer * PARTS;
+    const int f = layer / a.nk, k = layer - f * a.nk;
+    double* V = view + (long long)e * a.vs[0] + f * a.vs[1] + k * a.vs[2];
+    if (form == HV_LINES_WIDE) {
+      double r0, r1;
+      const double x0 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * part, a.base + layer, r0, rspheremp);
+      const double x1 = dss_view_point(tab, stage, recvbuf, nl, e, 2 * part + 1, a.base + layer, r1, rspheremp);
+      double2 d = make_double2(r0 * x0, r1 * x1);
+      if (ADD) { const double2 x = *(const double2*)(V + 2 * part); d.x = x.x + d.x; d.y = x.y + d.y; }
+      *(double2*)(V + 2 * part) = d;
+    } else {
+      double r0;
+      const double x0 = dss_view_point(tab, stage, recvbuf, nl, e, part, a.base + layer, r0, rspheremp);
+      double* P = V + (part >> 2) * a.vs[3] + (part & 3) * a.vs[4];
+      double d = r0 * x0;
+      if (ADD) d = *P + d;
+      *P = d;
+    }
+  }
+}
 
 // ---- first-order sphere operators of a host's own fields through strided views (tse_sphere_op_view) ---------------------------------
 // OP 0: gradient_sphere of a scalar (1 field -> 2 components), OP 1: divergence_sphere, OP 2: vorticity_sphere of a wind (2 components ->

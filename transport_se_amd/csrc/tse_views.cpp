@@ -285,6 +285,73 @@ int column_view_overlap(const tse_view* const v[5], const ViewPlan plan[5], std:
   return 0;
 }
 
+// tse_hypervis_view's up to four views -- s, v, s_out, v_out: s and s_out views of tse_dss_view with nf fields, v and v_out with 2 (the q
+// axis is the wind component).  s is absent exactly when nf == 0, v may be absent, not both; the out views are both absent (the update is
+// in place) or given for exactly the inputs that are present.  An absent view leaves path -1 and an empty footprint.
+static const char* const HYPERVIS_ROLE[4] = {"s", "v", "s_out", "v_out"};
+
+int hypervis_view_plan(int nelemd, int nf, int nk, const tse_view* s, const tse_view* v, const tse_view* s_out, const tse_view* v_out, ViewPlan out[4],
+                       std::string* err) {
+  const char* who = "tse_hypervis_view";
+  if (!out) return refuse(err, "%s: null plan", who);
+  if (nf < 0) return refuse(err, "%s: nf = %d (the number of scalar fields: 0 or more)", who, nf);
+  if (nf > HYPERVIS_MAX_FIELDS) return refuse(err, "%s: nf = %d (at most %d scalar fields in one call: their factors travel as kernel arguments)", who, nf, HYPERVIS_MAX_FIELDS);
+  if ((nf == 0) != (s == nullptr)) return refuse(err, nf ? "%s: nf = %d needs the view s" : "%s: nf = %d takes no view s: pass null", who, nf);
+  if (!s && !v) return refuse(err, "%s: neither scalar fields (nf = 0, s null) nor a wind (v null): nothing to do", who);
+  const tse_view* x[4] = {s, v, s_out, v_out};
+  if (s_out || v_out)
+    for (int i = 0; i < 2; i++) {
+      if (x[i] && !x[i + 2]) return refuse(err, "%s: %s is given and %s is not: the out views are both null (in place) or given for exactly the inputs", who, HYPERVIS_ROLE[i], HYPERVIS_ROLE[i + 2]);
+      if (!x[i] && x[i + 2]) return refuse(err, "%s: %s is given and %s is not: an out view belongs to an input", who, HYPERVIS_ROLE[i + 2], HYPERVIS_ROLE[i]);
+    }
+  for (int i = 0; i < 4; i++) {
+    out[i] = ViewPlan();
+    out[i].path = -1;
+    if (!x[i]) continue;
+    std::string e;
+    if (dss_view_plan(nelemd, i & 1 ? 2 : nf, nk, x[i], &out[i], &e, who)) return refuse(err, "%s (%s)", e.c_str(), HYPERVIS_ROLE[i]);
+  }
+  const long long nl = (long long)(nf + (v ? 2 : 0)) * nk;
+  if ((long long)nelemd * nl >= (1ll << 27)) return refuse(err, "%s: %d elements x %lld layers (the launches count 32-bit blocks)", who, nelemd, nl);
+  return 0;
+}
+
+// Whether two views may share an address.  Not when their footprints, each taken from its ptr, are disjoint (touching is disjoint).  Two
+// members of one elem(:) -- T, dp3d and state%v of E3SM -- interleave, so their footprints meet although no address is shared: two views
+// of the same element stride are also disjoint when their footprints within ONE element (the axes q, level, j, i) are disjoint and lie
+// together inside one element stride -- element e of one and element e' of the other then sit in windows a whole stride apart.
+static bool views_may_meet(const tse_view* a, const ViewPlan& pa, const tse_view* b, const ViewPlan& pb) {
+  if (!Footprint(a, pa).meets(Footprint(b, pb))) return false;
+  const __int128 es = a->stride[0] < 0 ? -(__int128)a->stride[0] : (__int128)a->stride[0];
+  if (a->stride[0] != b->stride[0] || es == 0 || pa.ext[0] != pb.ext[0]) return true;
+  __int128 lo[2], hi[2];
+  const tse_view* v[2] = {a, b};
+  const ViewPlan* p[2] = {&pa, &pb};
+  for (int i = 0; i < 2; i++) {
+    lo[i] = hi[i] = (__int128)(uintptr_t)v[i]->ptr;
+    for (int ax = 1; ax < 5; ax++) {
+      const __int128 span = (__int128)v[i]->stride[ax] * (p[i]->ext[ax] - 1) * 8;
+      if (span < 0) lo[i] += span; else hi[i] += span;
+    }
+    hi[i] += 8;
+  }
+  if (lo[0] < hi[1] && lo[1] < hi[0]) return true;
+  return std::max(hi[0], hi[1]) - std::min(lo[0], lo[1]) > es * 8;
+}
+
+// Every pair of the views that are given is disjoint (views_may_meet): in place both s and v are written, and an out view is written
+// while both inputs are still read.
+int hypervis_view_overlap(const tse_view* const x[4], const ViewPlan plan[4], std::string* err) {
+  for (int i = 0; i < 4; i++)
+    for (int j = i + 1; j < 4; j++) {
+      if (!x[i] || !x[j]) continue;
+      if (views_may_meet(x[i], plan[i], x[j], plan[j]))
+        return refuse(err, "tse_hypervis_view: %s [%p%+lld, %p%+lld doubles) overlaps %s [%p%+lld, %p%+lld doubles): the views of one call are disjoint",
+                      HYPERVIS_ROLE[j], x[j]->ptr, plan[j].lo, x[j]->ptr, plan[j].hi, HYPERVIS_ROLE[i], x[i]->ptr, plan[i].lo, x[i]->ptr, plan[i].hi);
+    }
+  return 0;
+}
+
 }  // namespace tse
 
 // the C plan entries: an error becomes the message of tse_last_error; n plans go out as path[] / lo[] / hi[], each of them optional
@@ -368,6 +435,19 @@ extern "C" int tse_column_view_plan(int nelemd, int op, const tse_view* dp, cons
   for (const tse_view* x : v) placed = placed || (x && x->ptr);
   if (placed && tse::column_view_overlap(v, pl, &err)) return refused(err);
   return plans_out(pl, 5, path, lo, hi);
+}
+
+extern "C" int tse_hypervis_view_plan(int nelemd, int nf, int nk, const tse_view* s, const tse_view* v, const tse_view* s_out, const tse_view* v_out, int path[4],
+                                      long long lo[4], long long hi[4]) {
+  tse::ViewPlan p[4];
+  std::string err;
+  if (tse::hypervis_view_plan(nelemd, nf, nk, s, v, s_out, v_out, p, &err)) return refused(err);
+  // strides alone (every ptr null): nothing is known of where the views lie
+  const tse_view* x[4] = {s, v, s_out, v_out};
+  bool placed = false;
+  for (const tse_view* y : x) placed = placed || (y && y->ptr);
+  if (placed && tse::hypervis_view_overlap(x, p, &err)) return refused(err);
+  return plans_out(p, 4, path, lo, hi);
 }
 
 #ifdef TSE_AB_HOOKS

@@ -85,6 +85,17 @@ int column_view_plan(int nelemd, int op, const tse_view* dp, const tse_view* p, 
                      std::string* err);
 int column_view_overlap(const tse_view* const v[5], const ViewPlan plan[5], std::string* err);
 
+// The up to four views of tse_hypervis_view / tse_hypervis_view_plan -> out[0..3] = the plans of s, v, s_out, v_out: s and s_out views of
+// tse_dss_view with nf fields, v and v_out with 2.  s is absent exactly when nf == 0, v may be absent (not both); the out views are both
+// absent or given for exactly the inputs.  An absent view: path -1 and an empty footprint.  Also refused: nf above HYPERVIS_MAX_FIELDS
+// (the factors travel as kernel arguments) and nelemd * (nf + 2) * nk >= 2^27.  hypervis_view_overlap: every two views that are given
+// are disjoint -- their footprints do not meet, or they have the same element stride and their footprints within one element are
+// disjoint and lie together inside one element stride (the members of one elem(:)).
+constexpr int HYPERVIS_MAX_FIELDS = TSE_HYPERVIS_MAX_FIELDS;
+int hypervis_view_plan(int nelemd, int nf, int nk, const tse_view* s, const tse_view* v, const tse_view* s_out, const tse_view* v_out, ViewPlan out[4],
+                       std::string* err);
+int hypervis_view_overlap(const tse_view* const x[4], const ViewPlan plan[4], std::string* err);
+
 // the message of tse_last_error, for the C entries of this host C++ unit: a call of tse::fail (tse_ctx.h; defined in tse_api.hip)
 int set_last_error(const char* msg);
 

@@ -1,6 +1,6 @@
 // tse_views_api.hip -- the entries of the C ABI that work on a resident host's own arrays through strided device views: tse_view_put /
 // tse_view_get, tse_apply_forcing, tse_remap_view, tse_dss_view, tse_biharmonic_view, tse_vector_setup / tse_vlaplace_view,
-// tse_sphere_op_view, tse_stats_view, tse_column_view.
+// tse_hypervis_view, tse_sphere_op_view, tse_stats_view, tse_column_view.
 //
 // A translation unit and a code object apart from the tracer path (tse_api.hip): the kernels of tse_view_kernels.h are instantiated
 // here (k_column_view in tse_column.hip) and nowhere else, and no kernel that tse_api.hip or tse_stage3.hip instantiates is launched
@@ -362,7 +362,15 @@ int tse_remap_view_status(tse_ctx* c, int* nrefused, int where[4]) {
 // tse_biharmonic_view and tse_vlaplace_view share: the stream order of tse_view_put, and on the compute stream
 // stage -> (pack -> halo_exchange kind 0 with nl = nf * nk layers, on a rank with neighbours) -> out.  The staging field and the halo
 // buffers are these calls' own; a steady-state call allocates nothing.
-static int dss_view_buffers(tse_ctx* c, size_t nl) {
+// second (tse_hypervis_view): the second staging field too, grown by the same rule
+static int dss_view_buffers(tse_ctx* c, size_t nl, bool second = false) {
+  if (second && nl > c->hv_layers) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->hv_stage) (void)hipFree(c->hv_stage);
+    c->hv_stage = nullptr; c->hv_layers = 0;
+    if (dalloc(&c->hv_stage, (size_t)c->nelemd * nl * 16)) return 1;
+    c->hv_layers = nl;
+  }
   if (nl <= c->dv_layers) return 0;
   HIPCHK(hipStreamSynchronize(c->stream));   // (an earlier call may still read the buffers that are given back)
   double** bufs[3] = {&c->dv_stage, &c->dv_send, &c->dv_recv};
@@ -376,13 +384,13 @@ static int dss_view_buffers(tse_ctx* c, size_t nl) {
 static DssViewArgs dss_view_args(int nf, int nk, const tse_view* v) {
   DssViewArgs a;
   for (int k = 0; k < 5; k++) a.vs[k] = v->stride[k];
-  a.nf = nf; a.nk = nk;
+  a.nf = nf; a.nk = nk; a.base = 0; a.nl = nf * nk;
   return a;
 }
-// the staged field's rank-boundary columns to the neighbour ranks and theirs into dv_recv
-static int stage_exchange(tse_ctx* c, size_t nl, unsigned pack_blocks) {
+// the staged field's rank-boundary columns to the neighbour ranks and theirs into dv_recv; staged: dv_stage, or tse_hypervis_view's second field
+static int stage_exchange(tse_ctx* c, size_t nl, unsigned pack_blocks, const double* staged = nullptr) {
   CommScope w(c, "comm_wait", c->stream);   // (on the compute stream: the whole exchange is exposed)
-  if (c->ncol_send && pack_staged(c, c->stream, c->dv_stage, (int)nl, pack_blocks, c->dv_send)) return 1;   // (k_pack<> is tse_api.hip's)
+  if (c->ncol_send && pack_staged(c, c->stream, staged ? staged : c->dv_stage, (int)nl, pack_blocks, c->dv_send)) return 1;   // (k_pack<> is tse_api.hip's)
   return halo_exchange(c, (int)nl, 0, c->stream, c->dv_send, c->dv_recv);
 }
 // What follows the checks of the three entries.  group: the timer group of the two kernels; exchange: whether the staged field goes to
@@ -550,6 +558,111 @@ int tse_vlaplace_view(tse_ctx* c, int nk, int order, double nu_ratio, const tse_
   return stage_exchange_out(c, "fieldvlap", nl, order == TSE_VBIHARMONIC && c->halo(), (hipStream_t)stream,
     [&] { launch_vlap_view_stage(c, p[0].path, wi, ai, nu_ratio, (const double*)in->ptr); },
     [&] { if (order == TSE_VLAPLACE) launch_vlap_view_out<1>(c, p[1].path, wo, ao, nu_ratio, (double*)out->ptr); else launch_vlap_view_out<2>(c, p[1].path, wo, ao, nu_ratio, (double*)out->ptr); });
+}
+
+// ---- one hyperviscosity sub-step of a resident host's scalars and wind (k_lap_view_mid, k_vlap_view_mid, k_dss_view_final: tse_view_kernels.h) ----
+// The plans and the overlap rule are host code (tse_views.cpp: hypervis_view_plan / hypervis_view_overlap); here the checks that need the
+// runtime, the stream order of tse_view_put and on the compute stream
+//   stage (scalars, wind) -> exchange -> mid (scalars, wind) -> exchange -> final
+// with the scalars' and the wind's layers in ONE staging field, so that each exchange is one halo_exchange of nl = (nf + 2) * nk layers.
+// Both exchanges use dv_send / dv_recv: every step is ordered on the compute stream (halo_exchange enqueues its receives and sends there,
+// or drains it before the callback), so the second pack follows the first exchange's sends and the second receive follows the mid
+// kernels, the only readers of what the first one brought.
+static HvSide hv_side(const DssViewArgs& a, int path, const tse_view* v) {
+  HvSide s;
+  s.a = a; s.x = (double*)v->ptr;
+  const bool wide = view_wide(path, v);
+  s.form = path == 1 ? (wide ? HV_ROWS_WIDE : HV_ROWS) : path == 0 && wide ? HV_LINES_WIDE : HV_POINTS;
+  return s;
+}
+static unsigned hv_side_blocks(int nelemd, const HvSide& s) {
+  if (s.form >= HV_ROWS_WIDE) return view_tiles(nelemd, s.a.nf, true).x;
+  return (unsigned)dss_view_sum_blocks(nelemd, (long long)s.a.nf * s.a.nk * (s.form == HV_LINES_WIDE ? 8 : 16));
+}
+
+int tse_hypervis_view(tse_ctx* c, int nf, int nk, const double* coef, double nu_ratio, const tse_view* s, const tse_view* v, const tse_view* s_out,
+                      const tse_view* v_out, void* stream) {
+  const char* who = "tse_hypervis_view";
+  if (!c) return fail("%s: null context", who);
+  if (!coef) return fail("%s: null coef", who);
+  if (!std::isfinite(nu_ratio)) return fail("%s: nu_ratio = %g is not finite", who, nu_ratio);
+  ViewPlan p[4];
+  { std::string err; if (hypervis_view_plan(c->nelemd, nf, nk, s, v, s_out, v_out, p, &err)) return fail("%s", err.c_str()); }
+  for (int f = 0; f < nf + (v ? 1 : 0); f++)
+    if (!std::isfinite(coef[f])) return fail("%s: coef[%d] = %g is not finite (%s)", who, f, coef[f], f < nf ? "a scalar field's factor" : "the wind's factor");
+  if (v && !c->vec_ready) return fail("%s: call tse_vector_setup first (elem%%D, elem%%metinv and elem%%mp are not part of tse_init_args)", who);
+  const tse_view* x[4] = {s, v, s_out, v_out};
+  static const char* const role[4] = {"s", "v", "s_out", "v_out"};
+  for (int i = 0; i < 4; i++)
+    if (x[i] && host_array_checks(c, {{who, role[i], &p[i], x[i]}}, stream)) return 1;
+  { std::string err; if (hypervis_view_overlap(x, p, &err)) return fail("%s", err.c_str()); }
+
+  const int ns = nf * nk, nlt = ns + (v ? 2 * nk : 0);
+  const size_t nl = (size_t)nlt;
+  const bool add = !s_out && !v_out, exchange = c->halo();
+  DssViewArgs as = {}, av = {};
+  if (s) { as = dss_view_args(nf, nk, s); as.nl = nlt; }
+  if (v) { av = dss_view_args(2, nk, v); av.base = ns; av.nl = nlt; }
+  HvCoef cf = {};
+  for (int f = 0; f < nf; f++) cf.c[f] = coef[f];
+  const double cv = v ? coef[nf] : 0.0;
+  // the final kernel's two sides: the views that are written
+  HvFinalArgs fa = {};
+  fa.blocks0 = 0;
+  if (s) {
+    const tse_view* w = add ? s : s_out;
+    DssViewArgs a = dss_view_args(nf, nk, w); a.nl = nlt;
+    fa.side[0] = hv_side(a, p[add ? 0 : 2].path, w);
+    fa.blocks0 = hv_side_blocks(c->nelemd, fa.side[0]);
+  }
+  unsigned blocks1 = 0;
+  if (v) {
+    const tse_view* w = add ? v : v_out;
+    DssViewArgs a = dss_view_args(2, nk, w); a.base = ns; a.nl = nlt;
+    fa.side[1] = hv_side(a, p[add ? 1 : 3].path, w);
+    blocks1 = hv_side_blocks(c->nelemd, fa.side[1]);
+  }
+
+  hipStream_t us = (hipStream_t)stream;
+  unsigned pack_blocks = 0;
+  if (exchange && c->ncol_send && halo_items((size_t)c->ncol_send * nl, &pack_blocks)) return 1;
+  if (dss_view_buffers(c, nl, true)) return 1;
+  if (order_in(c, us)) return 1;
+  if (s) {
+    Scope sc(c, "fieldhv");
+    launch_lap_view_stage(c, p[0].path, view_wide(p[0].path, s), as, (const double*)s->ptr);
+    LAUNCH_CHECK();
+  }
+  if (v) {
+    Scope sc(c, "fieldhv");
+    launch_vlap_view_stage(c, p[1].path, view_wide(p[1].path, v), av, nu_ratio, (const double*)v->ptr);
+    LAUNCH_CHECK();
+  }
+  if (exchange && stage_exchange(c, nl, pack_blocks)) return 1;
+  if (s) {
+    Scope sc(c, "fieldhv");
+    hipLaunchKernelGGL(k_lap_view_mid<>, dim3((unsigned)lap_view_out_blocks(c->nelemd, ns)), dim3(VIEW_THREADS), 0, c->stream, c->nelemd, nf, nk, nlt, cf, c->D, c->geo(),
+                       (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order, c->hv_stage);
+    LAUNCH_CHECK();
+  }
+  if (v) {
+    Scope sc(c, "fieldhv");
+    hipLaunchKernelGGL(k_vlap_view_mid<>, dim3((unsigned)vlap_view_out_blocks(c->nelemd, nk)), dim3(VIEW_THREADS), 0, c->stream, c->nelemd, nk, ns, nlt, cv, c->D, c->geo(),
+                       (const double*)c->vec_tab, nu_ratio, (const int2*)c->dss_tab, (const double*)c->dv_stage, (const double*)c->dv_recv, (const int*)c->order,
+                       c->hv_stage);
+    LAUNCH_CHECK();
+  }
+  if (exchange && stage_exchange(c, nl, pack_blocks, c->hv_stage)) return 1;
+  {
+    Scope sc(c, "fieldhv");
+    const dim3 grid(fa.blocks0 + blocks1);
+    if (add) hipLaunchKernelGGL(k_dss_view_final<true>, grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, fa, (const int2*)c->dss_tab, (const double*)c->rspheremp,
+                                (const double*)c->hv_stage, (const double*)c->dv_recv, (const int*)c->order);
+    else hipLaunchKernelGGL(k_dss_view_final<false>, grid, dim3(VIEW_THREADS), 0, c->stream, c->nelemd, fa, (const int2*)c->dss_tab, (const double*)c->rspheremp,
+                            (const double*)c->hv_stage, (const double*)c->dv_recv, (const int*)c->order);
+    LAUNCH_CHECK();
+  }
+  return order_out(c, us);
 }
 
 // ---- gradient, divergence and vorticity of a resident host's own fields, local or C0 (k_sphere_op_stage: tse_view_kernels.h) ------------

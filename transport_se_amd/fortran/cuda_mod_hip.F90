@@ -63,6 +63,8 @@ module cuda_mod
   integer, parameter, public :: lap_order1 = 1, lap_order2 = 2   ! TSE_LAPLACE, TSE_BIHARMONIC
   ! weak vector Laplacian / biharmonic of the host's own device-resident wind (tse_vector_setup, tse_vlaplace_view)
   public :: vector_setup_hip, vlaplace_view_hip
+  ! one hyperviscosity sub-step of the host's own device-resident scalars and wind in one call (tse_hypervis_view)
+  public :: hypervis_view_hip
   integer, parameter, public :: vlap_order1 = 1, vlap_order2 = 2   ! TSE_VLAPLACE, TSE_VBIHARMONIC
   ! gradient, divergence and vorticity of the host's own device-resident fields, element-local or C0 (tse_sphere_op_view)
   public :: sphere_op_view_hip
@@ -233,6 +235,10 @@ module cuda_mod
      integer(c_int) function tse_vlaplace_view(ctx, nk, order, nu_ratio, vin, vout, stream) bind(C, name='tse_vlaplace_view')
        import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nk, order; real(c_double), value :: nu_ratio
        type(tse_view), intent(in) :: vin, vout
+     end function
+     integer(c_int) function tse_hypervis_view(ctx, nf, nk, coef, nu_ratio, s, v, s_out, v_out, stream) bind(C, name='tse_hypervis_view')
+       import; type(c_ptr), value :: ctx, s, v, s_out, v_out, stream; integer(c_int), value :: nf, nk
+       real(c_double), intent(in) :: coef(*); real(c_double), value :: nu_ratio
      end function
      integer(c_int) function tse_sphere_op_view(ctx, nk, op, c0, vin, vout, stream) bind(C, name='tse_sphere_op_view')
        import; type(c_ptr), value :: ctx, stream; integer(c_int), value :: nk, op, c0
@@ -1045,6 +1051,45 @@ contains
     !$OMP END MASTER
     !$OMP BARRIER
   end subroutine vlaplace_view_hip
+
+  ! One sub-step of advance_hypervis on the host's DEVICE arrays (include/transport_se_hip.h: tse_hypervis_view):
+  !   x <- x + rspheremp * DSS(coef * biharmonic(x))
+  ! for the nf scalar fields s(:,:,1:nk,1:nf) at s_ptr -- T and dp3d of elem(:), two members at one element stride, are ONE view whose
+  ! q stride is the distance between the members -- and the wind v(:,:,1:2,1:nk) at v_ptr (state%v(np,np,2,nlev,tl): (/ s_e, 16, 32, 4, 1 /)),
+  ! with two exchanges where biharmonic_view_hip, vlaplace_view_hip and two dss_view_hip make four.  coef(1:nf+1): the host's
+  ! -nu*dt/hypervis_subcycle for each scalar field and, last, for the wind.  nu_ratio as in vlaplace_view_hip.  A half is absent with
+  ! nf = 0 and s_ptr = c_null_ptr, or v_ptr = c_null_ptr.  so_ptr / vo_ptr (optional, with their strides): device arrays that receive
+  ! the tendencies rspheremp * DSS(coef * biharmonic(x)) instead -- given for exactly the halves that are present; s and v then keep
+  ! every bit; absent or c_null_ptr: in place.  COLLECTIVE: every rank calls with the same nf, nk and presence of v.  Needs
+  ! vector_setup_hip with a wind.  stream as in view_put_hip.  A refusal aborts.
+  subroutine hypervis_view_hip(nf, nk, coef, nu_ratio, s_ptr, s_strides, v_ptr, v_strides, stream, so_ptr, so_strides, vo_ptr, vo_strides)
+    integer,              intent(in) :: nf, nk
+    real(c_double),       intent(in) :: coef(nf+1), nu_ratio
+    type(c_ptr),          intent(in) :: s_ptr, v_ptr, stream
+    integer(c_long_long), intent(in) :: s_strides(5), v_strides(5)
+    type(c_ptr),          intent(in), optional :: so_ptr, vo_ptr
+    integer(c_long_long), intent(in), optional :: so_strides(5), vo_strides(5)
+    type(tse_view), target :: vs, vv, vso, vvo
+    type(c_ptr) :: s, v, so, vo
+    vs%ptr = s_ptr; vs%stride = s_strides
+    vv%ptr = v_ptr; vv%stride = v_strides
+    s = c_null_ptr; v = c_null_ptr; so = c_null_ptr; vo = c_null_ptr
+    if (c_associated(s_ptr)) s = c_loc(vs)
+    if (c_associated(v_ptr)) v = c_loc(vv)
+    if (present(so_ptr) .and. present(so_strides)) then
+      vso%ptr = so_ptr; vso%stride = so_strides
+      if (c_associated(so_ptr)) so = c_loc(vso)
+    end if
+    if (present(vo_ptr) .and. present(vo_strides)) then
+      vvo%ptr = vo_ptr; vvo%stride = vo_strides
+      if (c_associated(vo_ptr)) vo = c_loc(vvo)
+    end if
+    !$OMP BARRIER
+    !$OMP MASTER
+    call check(tse_hypervis_view(ctx, int(nf,c_int), int(nk,c_int), coef, nu_ratio, s, v, so, vo, stream), 'hypervis_view_hip')
+    !$OMP END MASTER
+    !$OMP BARRIER
+  end subroutine hypervis_view_hip
 
   ! out at out_ptr <- op of nk levels of the host's DEVICE array at ptr (include/transport_se_hip.h: tse_sphere_op_view):
   !   op_gradient    s(:,:,1:nk)     -> out(:,:,1:2,1:nk)   gradient_sphere

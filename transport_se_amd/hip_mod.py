@@ -171,6 +171,7 @@ SPHERE_OPS = {"gradient": 0, "divergence": 1, "vorticity": 2}   # TSE_OP_GRADIEN
 SPHERE_OP_FIELDS = {0: (1, 2), 1: (2, 1), 2: (2, 1)}            # op -> (fields of in, fields of out)
 COLUMN_OPS = {"pint": 0, "pmid": 1, "phi": 2, "omega": 3}       # TSE_COL_PINT, TSE_COL_PMID, TSE_COL_PHI, TSE_COL_OMEGA
 COLUMN_VIEWS = ("dp", "p", "a", "b", "out")
+HYPERVIS_VIEWS = ("s", "v", "s_out", "v_out")
 STATS = 16   # TSE_STATS: doubles per share of HipMod.stats_view
 
 
@@ -220,6 +221,14 @@ def vlaplace_view_plan(nelemd, nk, field, out=None, nlev=None):
     L = _lib.lib(nlev=nlev)
     vi = _as_view(field)
     return _plan(L, L.tse_vlaplace_view_plan, (nelemd, nk), (vi, vi if out is None else out))
+
+
+def hypervis_view_plan(nelemd, nf, nk, s=None, v=None, s_out=None, v_out=None, nlev=None):
+    """tse_hypervis_view_plan: dict(s=, v=, s_out=, v_out=) of dict(path=, lo=, hi=), None for an absent view -- each view in a form
+    _as_view takes (a pair: so that the overlap rule is tested as well); s_out and v_out None: in place.  Needs no device.  Raises
+    TseError for views hypervis_view would refuse."""
+    L = _lib.lib(nlev=nlev)
+    return dict(zip(HYPERVIS_VIEWS, _plan(L, L.tse_hypervis_view_plan, (nelemd, nf, nk), (s, v, s_out, v_out))))
 
 
 def sphere_op_view_plan(nelemd, nk, op, field, out, nlev=None):
@@ -693,6 +702,47 @@ class HipMod:
         vi, vo, _, nk = self._view_pair("vlaplace_view", field, axes, out, out_axes, 2, nk, wind=True)
         self._chk(self.L.tse_vlaplace_view(self.h, int(nk), _named("vlaplace_view", "order", "orders", VLAP_ORDERS, order), float(nu_ratio), C.byref(vi),
                                            C.byref(vo), _stream_handle(stream)))
+
+    # ---- one hyperviscosity sub-step of the host's own scalars and wind (tse_hypervis_view) ----
+    def hypervis_view(self, s=None, s_axes=None, v=None, v_axes=None, coef=(), nu_ratio=1.0, s_out=None, v_out=None, s_out_axes=None,
+                      v_out_axes=None, stream=None, nf=None, nk=None):
+        """x <- x + rspheremp * DSS(coef * biharmonic(x)) for the nf scalar fields of the device array `s` (the array's own extent along
+        the letter q of `s_axes`; a missing letter: 1) and the wind `v` (its axis q, extent 2, is the component), nk levels each: the
+        body of advance_hypervis's subcycle loop in one call, with two exchanges where biharmonic_view, vlaplace_view and two dss_view
+        make four.  coef: nf + 1 factors, the host's -nu * dt / hypervis_subcycle for each scalar field and, last, for the wind (nf
+        of them will do without a wind).  nu_ratio: as in vlaplace_view.  Either of s and v may be None, not both.  s_out / v_out
+        (both None: in place): device arrays that receive the tendencies d = rspheremp * DSS(coef * biharmonic(x)) instead, given for
+        exactly the inputs that are present, axes `s_out_axes` / `v_out_axes` (default: those of the input); s and v then keep every
+        bit.  The bits are those of biharmonic_view / vlaplace_view (order 2) -> one product -> dss_view(mode="weak") -> one addition
+        on every path of every view and on any number of ranks.  COLLECTIVE on a context with neighbour ranks: every rank calls with the
+        same nf, nk and presence of v.  v needs vector_setup.  stream orders as in put.  The arrays may also be ready _lib.Views (then
+        nk, and with s also nf, are needed)."""
+        who = "hypervis_view"
+        vs = vso = vv = vvo = None
+        if s is not None:
+            vs, vso, nf, nk_s = self._view_pair(who, s, s_axes, s_out, s_out_axes, nf, nk)
+            vso = None if s_out is None else vso
+            nk = nk_s
+        elif s_out is not None:
+            raise TseError("%s: s_out is given and s is not" % who)
+        else:
+            nf = 0
+        if v is not None:
+            vv, vvo, _, nk_v = self._view_pair(who, v, v_axes, v_out, v_out_axes, 2, nk, wind=True)
+            vvo = None if v_out is None else vvo
+            if s is not None and nk_v != nk:
+                raise TseError("%s: v has %d levels, s has %d" % (who, nk_v, nk))
+            nk = nk_v
+        elif v_out is not None:
+            raise TseError("%s: v_out is given and v is not" % who)
+        if nk is None:
+            raise TseError("%s: neither s nor v is given" % who)
+        cf = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        if cf.size < nf + (v is not None) or cf.size > nf + 1:
+            raise TseError("%s: %d factors in coef for %d scalar fields%s" % (who, cf.size, nf, " and the wind" if v is not None else ""))
+        cf = np.concatenate([cf, np.zeros(nf + 1 - cf.size)])
+        self._chk(self.L.tse_hypervis_view(self.h, int(nf), int(nk), _vp(cf), float(nu_ratio), _ref(vs), _ref(vv), _ref(vso), _ref(vvo),
+                                           _stream_handle(stream)))
 
     # ---- gradient, divergence, vorticity of the host's own fields, element-local or C0 (tse_sphere_op_view) ----
     def sphere_op_view(self, field, axes, out, out_axes=None, op="vorticity", c0=False, stream=None, nk=None):
